@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py — whole-job throughput of the MI355X wavefront path tracer on BASELINE.json's metric.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, renders W warm-up steps, times the K steps and prints one JSON line (metric, value, unit, ms_per_step, ...).
+--dump-outputs DIR writes what the timed steps computed (the image of their film, the rays they traced) as DIR/*.npy.
+--full adds everything beyond the headline figure: the counting warm-up and the roofline / occupancy blocks, the rocprofv3 PMC
+child passes (--pmc-spp), the per-stage breakdown (--breakdown), the CPU baseline and the parity block (--cpu-spp).
 
 Workload (config.workload): BASELINE.json configs[2], "San Miguel 1080p 256spp on 1xMI355X" — the configuration the
 north_star's target is quoted on — on its synthetic stand-in at the SURVEY.md 8(d) specification (tools/make_scenes.py
@@ -19,7 +24,7 @@ strips r, r+N, ... for every step (pbrt-v4_amd/multigpu.py, wf_set_strips) — a
 go to rank 0 with one RCCL reduce inside the timed region (disjoint strips: a gather, bit-identical to the 1-GPU film).
 Total work is fixed as N grows: "scaling": "strong".  --partition samples selects the sample-index partition instead.
 
-The JSON line also carries
+With --full the JSON line also carries
   roofline      achieved algorithmic GB/s of the dominant kernel ("Intersect closest") vs the 8 TB/s HBM peak:
                 bytes per ray from SURVEY.md §8(d)'s formula with the kernel's own node/triangle visit
                 counters (collected during warm-up steps with the counting kernel variant), times the rays
@@ -67,6 +72,15 @@ def make_scene(path, spp, workload="sanmiguel-like", meshes=2000):
         make_scenes.cloud_like(path, (W, H), spp, n=512)   # a 512^3 density grid
     else:
         make_scenes.killeroo_like(path, (W, H), spp)
+
+
+def scene_files(workload, meshes, spp_total):
+    """(directory, scene file) of a generated stand-in, keyed by the generator's source and parameters"""
+    import hashlib
+    gen_src = open(os.path.join(ROOT, "tools", "make_scenes.py"), "rb").read()
+    key = hashlib.sha1(gen_src + ("%s %d %d" % (workload, meshes, spp_total)).encode()).hexdigest()[:16]
+    td = os.path.join(tempfile.gettempdir(), "wfbench_%s_%s" % (workload, key))
+    return td, os.path.join(td, workload + ".pbrt")
 
 
 def closest_bytes(c, stats_hits_emitter=0):
@@ -269,15 +283,35 @@ def shadow_bytes(c):
     return 124 * c["shadow_rays"] + 32 * c["shadow_nodes"] + 48 * c["shadow_tris"] + 32 * c["shadow_unoccluded"]
 
 
+DUMP_MAX_PIXELS = 1 << 21   # a larger image is dumped as a fixed sample of this many pixels: 24 MB of RGB + 16 MB of pixel indices
+
+
+def dump_outputs(out_dir, img, rays):
+    """--dump-outputs: what the timed steps computed.  image.npy = the film's image (float32 [H, W, 3]) — or, above DUMP_MAX_PIXELS pixels,
+    image_sample.npy (float32 [n, 3]) at the pixels of image_sample_pixels.npy (float64 y * W + x, a seeded choice, the same every run);
+    rays.npy = camera, indirect and shadow rays the timed steps traced (float64 [3])."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    img = np.ascontiguousarray(img, dtype=np.float32)
+    n = img.shape[0] * img.shape[1]
+    if n <= DUMP_MAX_PIXELS:
+        np.save(os.path.join(out_dir, "image.npy"), img)
+    else:
+        pix = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_PIXELS, replace=False))
+        np.save(os.path.join(out_dir, "image_sample.npy"), img.reshape(n, 3)[pix])
+        np.save(os.path.join(out_dir, "image_sample_pixels.npy"), pix.astype(np.float64))
+    np.save(os.path.join(out_dir, "rays.npy"), np.asarray(rays, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--cpu-spp", type=int, default=1, help="spp of the bounded CPU-baseline sample (0 = skip)")
+    ap.add_argument("--cpu-spp", type=int, default=1, help="--full: spp of the bounded CPU-baseline sample (0 = skip)")
     ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--pmc-spp", type=int, default=4, help="spp of the rocprofv3 PMC passes that measure roofline.traffic in this run (0 = use the committed profile)")
-    ap.add_argument("--breakdown", action="store_true", help="time EVERY launch of the timed region with HIP events and add the per-stage totals "
+    ap.add_argument("--pmc-spp", type=int, default=4, help="--full: spp of the rocprofv3 PMC passes that measure roofline.traffic in this run (0 = use the committed profile)")
+    ap.add_argument("--breakdown", action="store_true", help="--full: time EVERY launch of the timed region with HIP events and add the per-stage totals "
                     "(\"stage_ms\") to the JSON line; the near-tie re-trace of general-primitive scenes then runs on the main stream (no overlap)")
     ap.add_argument("--samples-per-pass", type=int, default=0, help="sample indices carried per pass (0 = automatic, ~64 M rays in flight)")
     ap.add_argument("--workload", choices=["killeroo-like", "sanmiguel-like", "cloud-like", "tm-like"], default="sanmiguel-like",
@@ -285,7 +319,15 @@ def main():
                          "killeroo-like = configs[1] stand-in; cloud-like = configs[3] stand-in; tm-like = configs[4] stand-in (3840x2160, maxdepth 50)")
     ap.add_argument("--partition", choices=["strips", "samples"], default="strips", help="N > 1: interleaved scanline strips (default) or sample indices")
     ap.add_argument("--meshes", type=int, default=2000, help="sanmiguel-like: number of 5000-triangle meshes (2000 = 10 M unique triangles)")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline figure does not need: counting warm-up, "
+                    "roofline / occupancy blocks, PMC child passes, --breakdown, CPU baseline and parity (a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what they computed as DIR/<name>.npy (float32 / float64, "
+                    "at most 64 MB: the whole image, or a fixed seeded sample of its pixels when it is larger)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.breakdown and not a.full:
+        ap.error("--breakdown is a --full measurement")
     global W, H
     if a.workload == "tm-like":
         W, H = 3840, 2160
@@ -315,11 +357,7 @@ def main():
         spp_total *= 2
     # the generated scene files are kept per box under /tmp (keyed by the generator's source and parameters): the driver's
     # N = 1, 2, 4, 8 runs and the N ranks of one run share them; rank 0 generates, the others wait for its marker file
-    import hashlib
-    gen_src = open(os.path.join(ROOT, "tools", "make_scenes.py"), "rb").read()
-    key = hashlib.sha1(gen_src + ("%s %d %d" % (a.workload, a.meshes, spp_total)).encode()).hexdigest()[:16]
-    td = os.path.join(tempfile.gettempdir(), "wfbench_%s_%s" % (a.workload, key))
-    scene_path = os.path.join(td, a.workload + ".pbrt")
+    td, scene_path = scene_files(a.workload, a.meshes, spp_total)
     marker = os.path.join(td, "_complete")
     t_gen0 = time.perf_counter()
     if not os.path.exists(marker):
@@ -355,10 +393,14 @@ def main():
 
     film_t = torch.zeros((info.height, info.width, 4), dtype=torch.float64, device="cuda") if world > 1 else None
 
-    # warm-up steps (sample indices 0..Wm-1, every rank renders all of them) with the counting kernels:
+    # warm-up steps (sample indices 0..Wm-1, every rank renders all of them); with --full through the counting kernels:
     # gives the per-ray node/triangle visit averages for the roofline
     counters = None
-    if Wm > 0:
+    if not a.full:
+        # plain run: the warm-up steps through the production kernels, nothing else
+        if Wm > 0:
+            multigpu.render_partition(scene, rank, world, 0, Wm, a.partition)
+    elif Wm > 0:
         scene.enable_counters(True)
         scene.render(0, Wm, 1)
         counters = scene.counters()
@@ -374,7 +416,7 @@ def main():
         film_t.zero_()
     rays_before = scene.total_rays()
     stats_before = scene.stats()
-    scene.enable_profile(1 if a.breakdown else (0 if a.no_roofline else 2))
+    scene.enable_profile(0 if not a.full else 1 if a.breakdown else (0 if a.no_roofline else 2))
 
     barrier()
     t0 = time.perf_counter()
@@ -408,6 +450,15 @@ def main():
         dist.all_gather(all_phases, phases)
     else:
         all_phases = [phases]
+    if a.dump_outputs:
+        st = scene.stats()
+        kinds = torch.tensor([st["camera_rays"] - stats_before["camera_rays"], sum(st["indirect_rays"][1:]) - sum(stats_before["indirect_rays"][1:]),
+                              sum(st["shadow_rays"]) - sum(stats_before["shadow_rays"])], dtype=torch.float64, device="cuda")
+        if dist is not None:
+            dist.all_reduce(kinds)
+        if rank == 0:
+            film = film_t.cpu().numpy() if dist is not None else scene.film()   # (rank 0 holds the whole film after the gather / reduce)
+            dump_outputs(a.dump_outputs, scene.film_to_rgb(film), kinds.cpu().numpy())
 
     if rank == 0:
         samples = float(info.width) * info.height * K
@@ -618,10 +669,10 @@ def main():
                     out["occupancy"] = {"code_object": {k: v for k, v in occ.items() if "<1, true, true>" in k or "<1, true>" in k or "<1, 1>" in k or "<1, false>" in k}}
         except Exception as ex:
             out["occupancy_error"] = str(ex)
-        if a.breakdown:
+        if a.full and a.breakdown:
             out["stage_ms"] = {e["name"]: {"launches": e["launches"], "total_ms": round(e["total_ms"], 3)} for e in scene.profile_report()}
         parity_fail = None
-        if world == 1 and a.cpu_spp > 0:
+        if a.full and world == 1 and a.cpu_spp > 0:
             out["cpu_baseline"], ref_img = cpu_baseline(scene_path, a.cpu_spp, wfpt.read_pfm)
             if ref_img is not None:
                 # parity on the benchmarked workload: the same scene file at the baseline's spp (the sampler's scrambling depends on
@@ -636,7 +687,8 @@ def main():
                 img = s1.image()
                 s1.close()
                 rel = np.abs(img.astype(np.float64) - ref_img) / np.maximum(np.abs(ref_img), 1e-2)
-                out["parity"] = {"against": "oracle/_ref/pbrt_ref --wavefront (the cpu_baseline render), same scene file, %d spp, seed 0" % a.cpu_spp,
+                against = "oracle/_ref/pbrt_ref --wavefront" if out["cpu_baseline"]["kind"] == "reference" else "oracle/_build/wf_cpu"
+                out["parity"] = {"against": against + " (the cpu_baseline render), same scene file, %d spp, seed 0" % a.cpu_spp,
                                  "max_rel": float(rel.max()), "bit_identical_fraction": float((img.view(np.uint32) == ref_img.view(np.uint32)).mean()),
                                  "tolerance": 1e-3, "values": int(img.size)}
                 if not (rel.max() <= 1e-3) or not np.isfinite(img).all():

@@ -923,8 +923,9 @@ def test_fuzz_corpus_vs_reference(wfpt, tmp_path, name):
 # ---------------------------------------------------------------------------------------------------------------------
 # Every BASELINE.json configuration in front of the driver's `pytest -m gpu`: configs[0] at its own size — the Cornell box
 # at 400 x 400, 16 spp, against the reference's render of that size — and the bench workloads of configs[1] and [3] through bench.py
-# itself (its in-run parity block compares the GPU render of the benchmarked scene file with the image pbrt_ref --wavefront just
-# wrote where the reference build exists — on the GPU box oracle/_ref travels with the repository).
+# itself (its in-run parity block compares the GPU render of the benchmarked scene file with the image the CPU baseline just wrote:
+# pbrt_ref --wavefront where the reference build exists, the CPU checker elsewhere; the image the timed steps computed is held to the
+# reference's render of the same scene file through its recorded hash, tests/golden/bench_line_ref_hashes.json).
 def test_config1_cornell_400x400_16spp(wfpt, tmp_path):
     path = os.path.join(GOLDEN, "cornell400.pbrt")
     s = wfpt.Scene(path=path, spp=16)
@@ -939,13 +940,27 @@ def test_config1_cornell_400x400_16spp(wfpt, tmp_path):
     assert_image_parity("cornell400", img, ref)
 
 
+def _bench_image_is_the_reference_render(workload, dump_dir):
+    """The image bench.py --steps 2 --dump-outputs wrote for `workload` against the reference's render of the same scene file at the same
+    2 spp, recorded as a hash (tools/make_bench_line_hashes.py): bit for bit."""
+    import make_bench_line_hashes as mh
+    want = json.load(open(os.path.join(GOLDEN, "bench_line_ref_hashes.json")))[workload]
+    _, scene = mh.load_bench().scene_files(workload, 2000, want["spp"])
+    assert mh.file_sha1(scene) == want["scene_sha1"], "the generator of %s drifted from the one its recorded reference render was made from" % workload
+    img = np.load(os.path.join(dump_dir, "image.npy"))
+    assert img.dtype == np.float32 and [img.shape[1], img.shape[0]] == want["resolution"] and img.shape[2] == 3 and np.isfinite(img).all()
+    assert mh.image_sha256(img) == want["image_sha256"], (workload, "not the reference's render: mean", float(img.astype(np.float64).mean()), want["image_mean"])
+
+
 # tm-like (round 5): BASELINE configs[4]'s scene at 3840x2160, one step — the 4K configuration in front of the driver's suite
 @pytest.mark.parametrize("workload", ["killeroo-like", "cloud-like", "tm-like"])
-def test_bench_workload_line(workload):
+def test_bench_workload_line(workload, tmp_path):
     # (the 4K scene's CPU baseline costs the reference 250 s on 256 cores at 1 spp: not in the suite; its parity is the tm_like_small golden
     # above and the in-run parity block of profiles/r0*_bench_tm-like.json)
     tm = workload == "tm-like"
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--steps", "1" if tm else "2", "--warmup", "1", "--cpu-spp", "0" if tm else "1", "--pmc-spp", "0"],
+    dump = str(tmp_path / "outputs")
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--workload", workload, "--steps", "1" if tm else "2", "--warmup", "1",
+                        "--cpu-spp", "0" if tm else "1", "--pmc-spp", "0", "--dump-outputs", dump],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])
@@ -954,16 +969,45 @@ def test_bench_workload_line(workload):
         assert line["config"]["resolution"] == [3840, 2160] and "Transparent Machines 4K" in line["config"]["workload"]
         assert line["roofline"]["bound"] == "hbm" and 0 < line["roofline"]["frac"] < 4
         assert line["roofline_material"]["items"] > 0
+        # the 4K image is dumped as a fixed sample of its pixels
+        sample, pix = np.load(os.path.join(dump, "image_sample.npy")), np.load(os.path.join(dump, "image_sample_pixels.npy"))
+        assert sample.dtype == np.float32 and sample.shape == (pix.shape[0], 3) and pix.dtype == np.float64 and 0 < pix.shape[0] < 3840 * 2160
+        assert (np.diff(pix) > 0).all() and pix[-1] < 3840 * 2160 and np.isfinite(sample).all() and sample.mean() > 0.01
         print(workload, line["value"], "Msamples/s")
         return
     assert workload.split("-")[0] in line["config"]["workload"].lower() or "cloud" in line["config"]["workload"].lower()
     assert line["roofline"]["bound"] == "hbm" and 0 < line["roofline"]["frac"] < 4 and line["roofline"]["peak"] == 8000.0
-    assert line["cpu_baseline"]["value"] > 0 and line["cpu_baseline"]["kind"] == "reference" and line["cpu_baseline"]["cores"] >= 1
+    # the CPU baseline is the reference's own CPU path where its build exists (it needs the reference sources at build time), else the checker
+    ref_built = os.path.exists(os.path.join(ROOT, "oracle", "_ref", "pbrt_ref"))
+    assert line["cpu_baseline"]["value"] > 0 and line["cpu_baseline"]["kind"] == ("reference" if ref_built else "port") and line["cpu_baseline"]["cores"] >= 1
     assert line["parity"]["max_rel"] <= REL_TOL and line["parity"]["bit_identical_fraction"] == 1.0, line["parity"]
+    # ... and, with or without the reference build, the image of the timed steps is the reference's render of the benchmarked scene file
+    _bench_image_is_the_reference_render(workload, dump)
     assert line["roofline_material"]["items"] > 0 and 0 < line["roofline_material"]["frac"] < 2, line.get("roofline_material_error")
     if workload == "cloud-like":
         assert line["roofline_medium"]["items"] > 0 and 0 < line["roofline_medium"]["frac"] < 2
     print(workload, line["value"], "Msamples/s", "parity", line["parity"]["max_rel"], line["parity"]["bit_identical_fraction"])
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain bench.py run (no --full: what every measurement of the project runs) times its steps and nothing else: the line carries the
+    headline fields and none of the --full blocks.  --dump-outputs writes what the timed steps computed: the image of the killeroo-like
+    stand-in at 2 spp — bit for bit the reference's render of that scene file — and the rays they traced (the line's mray_per_s)."""
+    dump = str(tmp_path / "outputs")
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "killeroo-like", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", dump], capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    line = json.loads(p.stdout.strip().splitlines()[-1])
+    assert line["unit"] == "Msamples/s" and line["higher_is_better"] is True and line["dtype"] == "f32" and "Msamples/sec" in line["metric"]
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["n_gpus"] == 1 and line["ms_per_step"] > 0
+    assert abs(line["value"] - 1920 * 1080 / (line["ms_per_step"] * 1e3)) <= 1e-9 * line["value"]
+    assert not {"roofline", "roofline_shadow", "roofline_material", "roofline_medium", "occupancy", "cpu_baseline", "parity", "stage_ms"} & set(line)
+    files = sorted(os.listdir(dump))
+    assert files == ["image.npy", "rays.npy"] and sum(os.path.getsize(os.path.join(dump, f)) for f in files) <= 64 << 20
+    rays = np.load(os.path.join(dump, "rays.npy"))
+    assert rays.dtype == np.float64 and rays.shape == (3,) and (rays > 0).all()
+    assert abs(rays.sum() / (2 * line["ms_per_step"] * 1e-3) / 1e6 - line["mray_per_s"]) <= 1e-9 * line["mray_per_s"]
+    _bench_image_is_the_reference_render("killeroo-like", dump)
 
 
 def test_config5_tm_like_4k_crop_window_vs_reference_run_here(wfpt, tmp_path):

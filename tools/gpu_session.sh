@@ -4,9 +4,9 @@
 #     gpurun --timeout 1500 -- 'bash tools/gpu_session.sh tests bench prof sm16'
 # Steps (any subset, in the order given):
 #   tests            pytest -m gpu + smoke()                                    -> gpurun_out/<TAG>_pytest_gpu.txt
-#   bench            the driver's command, bench.py --steps $STEPS --warmup 5   -> gpurun_out/<TAG>_bench_k$STEPS.json
+#   bench            the driver's command with every measurement, bench.py --full --steps $STEPS --warmup 5   -> <TAG>_bench_k$STEPS.json in the output folder
 #   prof             rocprofv3 --kernel-trace --stats of the same command       -> gpurun_out/<TAG>_bench_k$STEPS_rocprofv3_kernel_stats.csv
-#   workloads        bench.py --workload killeroo-like / cloud-like / tm-like   -> gpurun_out/<TAG>_bench_<workload>.json
+#   workloads        bench.py --full --workload killeroo-like / cloud-like / tm-like   -> <TAG>_bench_<workload>.json in the output folder
 #   sm16             per-kernel times (pbrt_amd --stats) of the spec scene at $SPP spp for _build and every _exp* build (same-box A/B)
 #   pmc              rocprofv3 PMC passes (SQ / TCP / TCC / FETCH / WRITE, one pass each) over the spec scene at $PMC_SPP spp
 #   soak             $SOAK renders of the spec scene at 4 spp: every image must be the first one (the near-tie queue's guard)
@@ -45,17 +45,17 @@ for step in "$@"; do
     bench)
       # the box itself (the pool's boxes differ by up to 17 % on the same binary: clocks / power cap recorded beside every bench line)
       (rocm-smi --showclocks --showpower --showmaxpower --showperflevel 2>/dev/null | grep -E "clk|Power|Perf" | head -12) > $OUT/${TAG}_box.txt
-      timeout 900 python bench.py --steps $STEPS --warmup 5 2> $OUT/${TAG}_bench_err.txt | tee $OUT/${TAG}_bench_k$STEPS.json
+      timeout 900 python bench.py --full --steps $STEPS --warmup 5 2> $OUT/${TAG}_bench_err.txt | tee $OUT/${TAG}_bench_k$STEPS.json
       tail -3 $OUT/${TAG}_bench_err.txt;;
     prof)
       rm -rf /tmp/prof
-      (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -o bench -- python $ROOT/bench.py --steps $STEPS --warmup 5 --cpu-spp 0 \
+      (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -o bench -- python $ROOT/bench.py --full --steps $STEPS --warmup 5 --cpu-spp 0 \
           > $OUT/${TAG}_bench_k${STEPS}_under_rocprofv3.json 2> /tmp/rocprof_err.txt)
       for f in $(find /tmp/prof -name "*kernel_stats.csv"); do cp $f $OUT/${TAG}_bench_k${STEPS}_rocprofv3_kernel_stats.csv; done
       head -14 $OUT/${TAG}_bench_k${STEPS}_rocprofv3_kernel_stats.csv | cut -c1-200;;
     workloads)
       for w in ${WORKLOADS:-killeroo-like cloud-like}; do
-        timeout 900 python bench.py --workload $w --steps ${WSTEPS:-16} --warmup 2 2>> $OUT/${TAG}_bench_err.txt | tee $OUT/${TAG}_bench_$w.json
+        timeout 900 python bench.py --full --workload $w --steps ${WSTEPS:-16} --warmup 2 2>> $OUT/${TAG}_bench_err.txt | tee $OUT/${TAG}_bench_$w.json
       done;;
     sm16)
       f=$(scene_file)
