@@ -40,7 +40,7 @@ enum {
     CNT_CURSOR_SHADOW,                  // the any-hit launch's work cursor (CNT_CURSOR: the closest-hit launch's)
     CNT_MEDIUM_ROUTE,                   // medium-sample items that reached their surface (KMediumRoute)
     CNT_DEFER, CNT_DEFER_SHADOW,        // rays the triangle walk handed to the general-primitive walk (round 6, wf_backend.hip "TWO-CLASS TRAVERSAL")
-    CNT_CURSOR_MEDIUM,                  // the medium-sample launch's work cursor (round 6: k_medium_sample with wave-level refill)
+    CNT_CURSOR_MEDIUM,                  // (unused: the work cursor of k_medium_sample's wave-level refill, measured and dropped in round 6)
     CNT_COUNT
 };
 // every counter sits alone in its own 256-byte line: same-line atomics serialise at one L2 channel
@@ -608,14 +608,13 @@ __device__ inline void KRouteHitBlock(const SceneView &sv, const WorkState &ws, 
 // (escaped, emitter hit, material evaluation, medium scattering) see the medium-attenuated values.
 // Round 6: the delta-tracking loop as an explicit state (MediumTrack) with three pieces — Begin (load the item, seed the RNG, set up the
 // majorant iterator), Step (at most one majorant segment fetched and one tentative collision taken; false = the item is finished) and End
-// (write-back and routing) — so that the HIP kernel can run it with WAVE-LEVEL REFILL (k_medium_sample, wf_backend.hip: a wave whose items
-// are mostly finished retires them and takes new ones instead of idling until the longest walk of its 64 ends; the lever the traversal
-// kernels use).  SampleT_maj's two nested loops (media.h:724-800) are the same sequence of operations per item: the
+// (write-back and routing).  It was written for a HIP kernel with WAVE-LEVEL REFILL (a wave whose items are mostly finished retires them
+// and takes new ones), which was measured and dropped; the state machine stayed, faster than the nested loops of rounds
+// 1-5 (k_medium_sample, wf_backend.hip).  SampleT_maj's two nested loops (media.h:724-800) are the same sequence of operations per item: the
 // outer loop's "next segment" and the inner loop's "next exponential step" are the two halves of Step.  The CPU checker and the
 // reference-order path run Begin; while (Step); End — the same code.
-#ifndef WF_MEDIUM_SPEC
-#define WF_MEDIUM_SPEC 0   // measured and LEFT OFF (round 6, cloud scene, 16 spp, same box, profiles/r06_medium_two_collisions_per_step_ab_cloud16.txt): 46.3 against 36.4 ms
-#endif
+// (Measured and dropped, round 6: two tentative collisions per Step for the grid media, their density gathers issued together — bit-identical
+//  but slower, 46.3 against 36.4 ms on the cloud scene, profiles/r06_medium_two_collisions_per_step_ab_cloud16.txt.)
 struct MediumTrack {
     int i;               // ray slot (-1: the lane holds no item)
     int pixelIndex, depth, medium;
@@ -727,41 +726,13 @@ WF_HD bool MediumTrackStep(const SceneView &sv, const WorkState &ws, int cur, Me
         s.T_maj = s.T_maj * FastExp(-(t - s.tMin) * s.seg.sigma_maj);
         V3 p = s.o + s.d * t;
         const wf_medium &M = sv.media[s.medium];
-#if WF_MEDIUM_SPEC
-        // TWO tentative collisions per step for the grid media (round 6; bit-identical, but slower: the walks of the dense cloud are short — one or two
-        // events — so most second lookups are wasted, and the step's code doubles).  Where the NEXT exponential step lands depends only on this one's
-        // position and on the sample value already drawn (s.u) — not on the density here — so its position is known now, and the density
-        // gathers of both points (two dependent-free pairs of 16-byte loads out of a multi-GB table: what this kernel waits for 79 % of its
-        // time at two waves per SIMD) are issued together.  If this event ends the walk the second lookup is wasted (once per item);
-        // otherwise the second event runs exactly as the next step would: the same operands, the RNG draws in the same order.
-        const bool gridMedium = M.type == WF_MEDIUM_GRID || M.type == WF_MEDIUM_RGB_GRID || M.type == WF_MEDIUM_NANOVDB;
-        const float t2 = t + SampleExponential(s.u, s.seg.sigma_maj[0]);   // (the next step's `tMin + SampleExponential(u, ...)` with tMin = t)
-        const bool spec = gridMedium && t2 < s.seg.tMax;
         MediumProps mp = MediumSamplePoint<LEAN>(sv, M, s.ml, p);
-        V3 p2 = p;
-        MediumProps mp2 = mp;
-        if (spec) { p2 = s.o + s.d * t2; mp2 = MediumSamplePoint<LEAN>(sv, M, s.ml, p2); }
-#else
-        MediumProps mp = MediumSamplePoint<LEAN>(sv, M, s.ml, p);
-#endif
         if (!MediumTrackEvent(sv, ws, cur, s, p, mp, s.seg.sigma_maj, s.T_maj)) {
             s.stopped = true;
             return false;
         }
         s.T_maj = S4c(1.f);
         s.tMin = t;
-#if WF_MEDIUM_SPEC
-        if (spec) {
-            s.u = s.rng.UniformFloat();
-            s.T_maj = s.T_maj * FastExp(-(t2 - s.tMin) * s.seg.sigma_maj);
-            if (!MediumTrackEvent(sv, ws, cur, s, p2, mp2, s.seg.sigma_maj, s.T_maj)) {
-                s.stopped = true;
-                return false;
-            }
-            s.T_maj = S4c(1.f);
-            s.tMin = t2;
-        }
-#endif
     } else {
         float dt = s.seg.tMax - s.tMin;
         if (IsInf(dt)) dt = WF_FLT_MAX;
@@ -1575,8 +1546,8 @@ WF_HD void MatNee(const SceneView &sv, const WorkState &ws, const NeeItem<MAT> &
     MatNeeFinish(sv, ws, it, pick, live);
 }
 
-// K9 fused: EvaluateMaterialAndBSDF<M, BasicTextureEvaluator>, wavefront/surfscatter.cpp:57-328 (the CPU checker; the HIP back end's
-// WF_MAT_SPLIT=0 kernels)
+// K9 fused: EvaluateMaterialAndBSDF<M, BasicTextureEvaluator>, wavefront/surfscatter.cpp:57-328 (the CPU checker's reference; the HIP back
+// end runs the two halves, MatShade and MatNee, as kernels of their own)
 template <int MAT, int VARIANT = 2>
 WF_HD void KEvalMaterial(const SceneView &sv, const WorkState &ws, int cur, int qi, bool valid) {
     NeeItem<MAT> it;

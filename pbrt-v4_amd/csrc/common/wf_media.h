@@ -51,23 +51,10 @@ WF_HD float GridLookup(const float *v, int nx, int ny, int nz, V3 p) {
 // The same lookup over the corner-packed copy of the grid (SceneView::gridCorners): cell (ix + 1, iy + 1, iz + 1) of an
 // (nx + 1)(ny + 1)(nz + 1) table holds v(ix.., iy.., iz..) for the eight corners in the order the lerps below take them, zeros outside the
 // grid as GridLookupI returns them.  The same eight values through the same expressions: bit-identical.
-// Where cell (cx, cy, cz) of the corner-packed table lives (round 6): the table is BRICKED — 8 x 8 x 8 cells of 32 bytes = one 16 KiB brick,
-// bricks in row-major order — so that lookups that are close in space (neighbouring rays, successive steps of one ray) fall into the same pages and
-// lines (in the row-major table a step along z moves 8.4 MB on a 512^3 grid).  Built on the suspicion that the delta-tracking kernel was TLB-bound; it was
-// not (see WF_GRID_BRICKS).
-#ifndef WF_GRID_BRICKS
-#define WF_GRID_BRICKS 0   // 1: the bricked table (A/B builds) — measured once the kernel's real bound (the scatter counter's atomics) was gone: 12.2 against 12.1 ms, no gain: the row-major table of round 4 stays
-#endif
-WF_HD size_t GridCornerBricks(int n) { return (size_t)((n + 1 + 7) >> 3); }   // bricks along an axis of n voxels (n + 1 cells)
-WF_HD size_t GridCornerCells(int nx, int ny, int nz) {   // cells the table holds, padding included
-    if (!WF_GRID_BRICKS) return (size_t)(nx + 1) * (ny + 1) * (nz + 1);
-    return GridCornerBricks(nx) * GridCornerBricks(ny) * GridCornerBricks(nz) * 512;
-}
-WF_HD size_t GridCornerIndex(int nx, int ny, int cx, int cy, int cz) {
-    if (!WF_GRID_BRICKS) return ((size_t)cz * (ny + 1) + cy) * (nx + 1) + cx;
-    const size_t brick = ((size_t)(cz >> 3) * GridCornerBricks(ny) + (size_t)(cy >> 3)) * GridCornerBricks(nx) + (size_t)(cx >> 3);
-    return brick * 512 + (size_t)(((cz & 7) << 6) | ((cy & 7) << 3) | (cx & 7));
-}
+// Where cell (cx, cy, cz) of the corner-packed table lives: row-major.  (Round 6, measured and dropped: a BRICKED table — 8 x 8 x 8 cells
+// of 32 bytes per 16 KiB brick — built on the suspicion that the delta-tracking kernel was TLB-bound; it was not: 12.2 against 12.1 ms.)
+WF_HD size_t GridCornerCells(int nx, int ny, int nz) { return (size_t)(nx + 1) * (ny + 1) * (nz + 1); }   // cells the table holds
+WF_HD size_t GridCornerIndex(int nx, int ny, int cx, int cy, int cz) { return ((size_t)cz * (ny + 1) + cy) * (nx + 1) + cx; }
 WF_HD float GridLookupPacked(const float *c, int nx, int ny, int nz, V3 p) {
     V3 ps{p.x * nx - .5f, p.y * ny - .5f, p.z * nz - .5f};
     int ix = (int)floor(ps.x), iy = (int)floor(ps.y), iz = (int)floor(ps.z);
@@ -428,9 +415,8 @@ WF_HD MajorantIter MediumSampleRay(const SceneView &sv, const wf_medium &M, cons
 //  same box, profiles/r06_sampleT_maj_flattened_for_transmittance_ab_cloud16.txt.  Their callback is a few multiplications: the nested form's
 //  tight inner loop is worth more than the lanes the flattening keeps busy.)
 // SampleT_maj, media.h:724-800.  callback(p, mp, sigma_maj, T_maj) -> continue?
-#ifndef WF_TMAJ_SPEC
-#define WF_TMAJ_SPEC 0   // measured and LEFT OFF (round 6, cloud scene: Intersect shadow (Tr) 19.2 against 19.0 ms, profiles/r06_sampleT_maj_two_collisions_ab_cloud16.txt)
-#endif
+// (Round 6, measured and dropped: two tentative collisions per iteration for the grid media — Intersect shadow (Tr) 19.2 against 19.0 ms on
+//  the cloud scene, profiles/r06_sampleT_maj_two_collisions_ab_cloud16.txt.)
 // MLEAN: the lean medium code (MediumSamplePoint<true>: homogeneous and non-emissive uniform-grid media only), for the transmittance kernels of scenes with no other medium type
 template <bool MLEAN = false, typename F>
 WF_HD S4 SampleT_maj(const SceneView &sv, int mediumId, V3 o, V3 d, float tMax, float u, RNG &rng, const Wavelengths &lambda, F callback) {
@@ -457,35 +443,6 @@ WF_HD S4 SampleT_maj(const SceneView &sv, int mediumId, V3 o, V3 d, float tMax, 
             if (t < seg.tMax) {
                 T_maj = T_maj * FastExp(-(t - tMin) * seg.sigma_maj);
                 V3 p = o + d * t;
-#if WF_TMAJ_SPEC
-                // TWO tentative collisions per iteration for the grid media (round 6): where the next exponential step lands depends only on
-                // this one's position and on the sample value already drawn (u), not on the density here, so both points' density gathers are
-                // issued together; the second event then runs exactly as the next iteration would (same operands, the RNG draws in the same
-                // order).  Bit-identical; no gain on the cloud scene's transmittance walks either.
-                const bool gridMedium = M.type == WF_MEDIUM_GRID || M.type == WF_MEDIUM_RGB_GRID || M.type == WF_MEDIUM_NANOVDB;
-                const float t2 = t + SampleExponential(u, seg.sigma_maj[0]);
-                const bool spec = gridMedium && t2 < seg.tMax;
-                MediumProps mp = MediumSamplePoint<MLEAN>(sv, M, ml, p);
-                V3 p2 = p;
-                MediumProps mp2 = mp;
-                if (spec) { p2 = o + d * t2; mp2 = MediumSamplePoint<MLEAN>(sv, M, ml, p2); }
-                if (!callback(p, mp, seg.sigma_maj, T_maj)) {
-                    done = true;
-                    break;
-                }
-                T_maj = S4c(1.f);
-                tMin = t;
-                if (spec) {
-                    u = rng.UniformFloat();
-                    T_maj = T_maj * FastExp(-(t2 - tMin) * seg.sigma_maj);
-                    if (!callback(p2, mp2, seg.sigma_maj, T_maj)) {
-                        done = true;
-                        break;
-                    }
-                    T_maj = S4c(1.f);
-                    tMin = t2;
-                }
-#else
                 MediumProps mp = MediumSamplePoint<MLEAN>(sv, M, ml, p);
                 if (!callback(p, mp, seg.sigma_maj, T_maj)) {
                     done = true;
@@ -493,7 +450,6 @@ WF_HD S4 SampleT_maj(const SceneView &sv, int mediumId, V3 o, V3 d, float tMax, 
                 }
                 T_maj = S4c(1.f);
                 tMin = t;
-#endif
             } else {
                 float dt = seg.tMax - tMin;
                 if (IsInf(dt)) dt = WF_FLT_MAX;

@@ -134,7 +134,7 @@ WF_HD const char *FatalMessage(int code) {
            : "fatal error raised by a kernel";
 }
 // On the device the flag is raised with an atomic and WITHOUT a null test (the back end always allocates the word).  The obvious form,
-// `if (sv.fatal) *sv.fatal = code;`, inlined into the light-sampling code of the material kernels, made k_eval_material<1, 0> corrupt memory
+// `if (sv.fatal) *sv.fatal = code;`, inlined into the light-sampling code of the material kernels, made the one-kernel material stage of type 1 (variant 0) corrupt memory
 // (round 4: cornell64 rendered a different image on every run and one build faulted; the same source with this body, with the store
 // through sv.self->fatal, or without the call in SphereSample / SpherePDF is bit-identical and repeatable — DESIGN.md 4.2).
 #if defined(__HIP_DEVICE_COMPILE__)

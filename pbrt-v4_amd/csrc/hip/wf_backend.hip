@@ -2,7 +2,7 @@
 //
 // What the reference does with one generic kernel template instantiated per lambda (gpu/util.h:77-114)
 // plus OptiX programs (gpu/optix/optix.cu), this file does with named, hand-written kernels:
-//   k_gen_camera_rays / k_gen_ray_samples / k_handle_escaped / k_handle_emissive / k_eval_material<M> /
+//   k_gen_camera_rays / k_gen_ray_samples / k_handle_escaped / k_handle_emissive / k_mat_shade<M> / k_mat_nee<M> /
 //   k_update_film            grid-stride "for all queued" kernels (sizes are read on the device; the host
 //                            never reads a queue size, as in wavefront/workqueue.h:118-137)
 //   k_intersect_closest      BVH closest hit, replaces OptiX __raygen__findClosest + closest-hit programs
@@ -63,7 +63,7 @@ constexpr int STACK_LDS = 24;   // LDS stack entries per lane: 24 x 4 B x 256 la
 constexpr int STACK_MAX = 64;   // nodesToVisit[64], cpu/aggregates.cpp:538
 constexpr int MAX_GRID = 256 * 8;  // 256 CUs x up to 8 resident 256-thread workgroups
 
-struct SpillArea { int *base; int rows; int *dbg; F4 *save; };   // the context's stackSpill rows + the debug words (kernel argument of the production traversal)
+struct SpillArea { int *base; int rows; int *dbg; };   // the context's stackSpill rows + the debug words (kernel argument of the production traversal)
 
 struct wf_ctx {
     int device = 0;
@@ -76,8 +76,7 @@ struct wf_ctx {
     int *stackSpill = nullptr;   // [rows][MAX_GRID*BLOCK], rows from the trees' depths (wf_scene_upload)
     int spillRows = 0;
     int *dbgWords = nullptr;     // [4] spilled stack entries, stack-overflow flag, inline near-tie re-traces, cursor path taken (wf_debug_counters)
-    F4 *walkSave = nullptr;      // [4][MAX_GRID*BLOCK]: every lane's render-space walk constants, reloaded when it leaves an instance (LdsStackT::loadWorld)
-    SpillArea spillArea() const { return SpillArea{stackSpill, spillRows, dbgWords, walkSave}; }
+    SpillArea spillArea() const { return SpillArea{stackSpill, spillRows, dbgWords}; }
     FastBVH fast{};              // production traversal layout (wf_traverse.h); built at upload
     bool fastOk = false;         // false: leaf sizes > 16 -> only the reference-order kernels are used
     hipStream_t stream2 = nullptr;   // the near-tie re-trace runs here, beside the routing pass and the next stage's sample generation
@@ -89,8 +88,7 @@ struct wf_ctx {
     // 31.4 ms (begin 3.3 + trace 3.7 + segment 24.1 + rest 0.3) — the time is the ratio tracking through the grid, not the walk, and the
     // per-lane loop keeps its state in registers; with object instances the per-lane alternative is the reference-order walk (1 wave / SIMD)
     int trWavefront = -1;
-    bool cursorDirty[3] = {false, false, false};   // the closest-hit / any-hit / medium-sample work cursor has been used since a k_reset last zeroed it
-    int mediumGrid = 512;        // resident workgroups of the persistent k_medium_sample
+    bool cursorDirty[2] = {false, false};   // the closest-hit / any-hit work cursor has been used since a k_reset last zeroed it
     bool mediumLean = false;     // every medium is homogeneous or a non-emissive uniform grid: k_medium_sample<true>
     int matStreams = 0;          // WF_MAT_STREAMS=0: the material kernels of one depth one after the other on the render stream
     hipStream_t matStream[WF_MAT_NTYPES] = {};
@@ -100,7 +98,6 @@ struct wf_ctx {
     // ... per MATERIAL TYPE since round 6: a type none of whose materials sits on a quadric / patch / curve keeps its lean shade kernel
     // when such shapes appear elsewhere in the scene (their hits are items of other types' queues)
     bool leanType[WF_MAT_NTYPES] = {};
-    bool matSplit = true;        // the material stage as two kernels per type (WF_MAT_SPLIT=0 with a MATFUSED build: the one-kernel stage)
     bool rareLights = false;     // the scene has a light type only the VARIANT 2 material kernels sample (portal infinite lights)
     int genMode = 0;             // general-primitive strength of the traversal kernels: 0 triangles only, 1 simple alpha, 2 anything but curves and alpha on quadrics, 3 anything (see GeneralPrims)
     int persistentGrid = 1024;   // resident workgroups for the persistent traversal kernels (closest-hit variant of the scene)
@@ -112,23 +109,12 @@ struct wf_ctx {
     bool animFast = false;       // the scene's AnimatedPrimitives are walked by the production kernels' ANIM variants (round 6; genMode <= 1 only)
     int persistentGridGen = 1024, persistentGridShadowGen = 1024;
     static bool splitRouteWanted() { return true; }
-    // ray-coherence pass (SortRayQueue): bit 0 sorts the ray queue before the closest-hit launch of depth >= 1, bit 1 the shadow queue
-    int raySort = 0;
     int cursorChunk = 2;         // 64-ray batches a closest-hit wave takes per cursor fetch (WF_CURSOR_CHUNK sets both)
     int cursorChunkShadow = 2;   // ... an any-hit wave (round 6, with the descent scheduling, 10 M-triangle scene: closest-hit 27.7 ms at 1, 26.7 at 3, 27.0 at 4, 27.4 at 8, 29.9 at 16;
                                  // any-hit 12.15 at 1, 12.16 at 3, 12.4 at 4, 13.0 at 8: profiles/r06_cursor_chunk_ab_sm16.txt)
                                  // (-3 %), but on a 30 k-triangle scene one fetch per 64 rays is 83 atomics/us on one counter: the kernel's bound
     int splitRoute = 2;          // WF_SPLIT_ROUTE: 0 = the closest-hit walk routes its hits per workgroup (KRouteHitBlock inside the walk);
                                  // 1 = walk without the workgroup barrier + k_route_hits; 2 (default) = 1 + waves draw their rays from a shared cursor
-    int sortMin = 4096;
-    int sortOriginBits = 6, sortDirBits = 4;  // per axis of the origin grid / per axis of the octahedral direction map
-    float sceneMin[3] = {0, 0, 0}, sceneMax[3] = {0, 0, 0};  // bounds of the top-level BVH
-    float sortBase[3] = {0, 0, 0}, sortScale[3] = {0, 0, 0};
-    uint32_t *sortKeys[2] = {nullptr, nullptr}, *sortVals[2] = {nullptr, nullptr};
-    void *sortTemp = nullptr;
-    size_t sortTempBytes = 0;
-    RayQueueV rqTmp{};
-    ShadowQueueV sqTmp{};
     int32_t *probeCursor = nullptr;
     bool matPresent[WF_MAT_NTYPES] = {};
     int W = 0, H = 0;
@@ -293,9 +279,8 @@ __global__ void __launch_bounds__(BLOCK) k_intersect_shadow(const SceneView sv, 
     }
 }
 
-// ---- production traversal: persistent waves over QNode/LeafTri with the tree top in LDS (wf_traverse.h) ----
+// ---- production traversal: persistent waves over QNode/LeafTri (wf_traverse.h) ----
 __shared__ int g_tstack[TSTACK * TBLOCK];
-__shared__ U4 g_top[QNODE_U4 * (TOP_NODES > 0 ? TOP_NODES : 1)];   // (WF_TOP_NODES=0: no LDS copy of the tree top — every node fetch is a plain global load)
 // the render-space ray of every lane (o.xyz, d.xyz), for the instance transitions and the alpha test of the two-level / general
 // variants: re-reading it from the queue (round 2) put an L2 round trip in front of every transition — eight per ray on the spec scene
 __shared__ float g_ray[6 * TBLOCK];
@@ -303,10 +288,6 @@ __device__ inline void StoreWorldRay(V3 o, V3 d) {
     g_ray[0 * TBLOCK + threadIdx.x] = o.x; g_ray[1 * TBLOCK + threadIdx.x] = o.y; g_ray[2 * TBLOCK + threadIdx.x] = o.z;
     g_ray[3 * TBLOCK + threadIdx.x] = d.x; g_ray[4 * TBLOCK + threadIdx.x] = d.y; g_ray[5 * TBLOCK + threadIdx.x] = d.z;
 }
-// WF_SAVE_WORLD == 2: nine of the lane's render-space walk constants (a, bk of WalkSetSlab and the shear's S: what costs a reciprocal or an
-// IEEE division to rebuild), kept in LDS from the ray's start for every exit from an instance — 9 KiB per workgroup: with them the
-// two-level kernels use 39 KiB, four workgroups still fit a CU's 160 KiB
-__shared__ float g_save[9 * TBLOCK];
 // the ray's time, for the kernels of scenes with animated primitives (written by their fetch functors, read at instance entries)
 __shared__ float g_time[TBLOCK];
 __device__ inline V3 WorldRayO() { return V3{g_ray[0 * TBLOCK + threadIdx.x], g_ray[1 * TBLOCK + threadIdx.x], g_ray[2 * TBLOCK + threadIdx.x]}; }
@@ -330,46 +311,6 @@ struct LdsStackT {
     int lo;       // entries [0, lo) are in the HBM column, [lo, n) in the LDS ring (n - lo <= TSTACK)
     int rows;     // capacity of the HBM column
     int *dbg;
-    // The render-space constants of the lane's ray (slab constants on the top-level grid, the triangle test's shear: 16 dwords), written
-    // once when the ray starts and RELOADED whenever the lane leaves an instance (round 6).  Until round 5 ExitInstance recomputed them —
-    // three IEEE divisions, three v_rcp, ~95 VALU instructions of a walk that is bound by VALU issue at a quarter of its lanes — eight
-    // times per ray on the spec scene.  Four 16-byte planes per lane, lane-major: a wave reads 1 KiB per instruction, mostly from L2.
-    F4 *save = nullptr;
-    __device__ void saveWorld(const RayWalk &w) const {
-        const size_t S = (size_t)spillStride;
-        save[0] = F4{w.a.x, w.a.y, w.a.z, w.bn.x};
-        save[S] = F4{w.bn.y, w.bn.z, w.af.x, w.af.y};
-        save[2 * S] = F4{w.af.z, w.bf.x, w.bf.y, w.bf.z};
-        save[3 * S] = F4{BitsToFloat((uint32_t)w.sh.kz), w.sh.Sx, w.sh.Sy, w.sh.Sz};
-    }
-    __device__ void saveWorldLds(const float a[3], const float bk[3], const RayShear &sh) const {
-        const int t = threadIdx.x;
-        g_save[0 * TBLOCK + t] = a[0]; g_save[1 * TBLOCK + t] = a[1]; g_save[2 * TBLOCK + t] = a[2];
-        g_save[3 * TBLOCK + t] = bk[0]; g_save[4 * TBLOCK + t] = bk[1]; g_save[5 * TBLOCK + t] = bk[2];
-        g_save[6 * TBLOCK + t] = sh.Sx; g_save[7 * TBLOCK + t] = sh.Sy; g_save[8 * TBLOCK + t] = sh.Sz;
-    }
-    __device__ void loadWorld(RayWalk &w, V3 oW, V3 dW) const {
-#if WF_SAVE_WORLD == 2
-        const int t = threadIdx.x;
-        const float a[3] = {g_save[0 * TBLOCK + t], g_save[1 * TBLOCK + t], g_save[2 * TBLOCK + t]};
-        const float bk[3] = {g_save[3 * TBLOCK + t], g_save[4 * TBLOCK + t], g_save[5 * TBLOCK + t]};
-        w.o = oW;
-        w.sh.kz = MaxComponentIndex(Abs(dW));   // (MakeRayShear's permutation; its three divisions are the saved S)
-        w.sh.Sx = g_save[6 * TBLOCK + t]; w.sh.Sy = g_save[7 * TBLOCK + t]; w.sh.Sz = g_save[8 * TBLOCK + t];
-        WalkSlabFromAB(w, a, bk);
-        return;
-#endif
-        const size_t S = (size_t)spillStride;
-        const F4 p0 = save[0], p1 = save[S], p2 = save[2 * S], p3 = save[3 * S];
-        w.o = oW;
-        w.a = V3{p0.x, p0.y, p0.z}; w.bn = V3{p0.w, p1.x, p1.y};
-        w.af = V3{p1.z, p1.w, p2.x}; w.bf = V3{p2.y, p2.z, p2.w};
-        w.sh.kz = (int)FloatToBits(p3.x); w.sh.Sx = p3.y; w.sh.Sy = p3.z; w.sh.Sz = p3.w;
-        // (the v_perm selectors follow the direction's sign, which is the sign of `a`: WalkSetSlab)
-        w.selx = (FloatToBits(p0.x) >> 31) ? 0x01000302u : 0x03020100u;
-        w.sely = (FloatToBits(p0.y) >> 31) ? 0x01000302u : 0x03020100u;
-        w.selz = (FloatToBits(p0.z) >> 31) ? 0x01000302u : 0x03020100u;
-    }
     static constexpr int MASK = TSTACK - 1;
     static_assert((TSTACK & (TSTACK - 1)) == 0, "WF_TSTACK must be a power of two (ring indexing)");
     __device__ void reset() { n = 0; lo = 0; }
@@ -383,23 +324,6 @@ struct LdsStackT {
         g_tstack[(n & MASK) * TBLOCK + threadIdx.x] = v;
         ++n;
     }
-    // room for k more entries at once (k <= 3: the interior step's pushes), so that the pushes themselves need no test (WF_PUSH_RESERVE)
-    __device__ void reserve(int k) {
-        while (__builtin_expect(n - lo + k > TSTACK, 0)) {
-            if (__builtin_expect(lo >= rows, 0)) { if (dbg) atomicOr(dbg + 1, 1); return; }
-            SpillWrite(&spill[(size_t)lo * spillStride], g_tstack[(lo & MASK) * TBLOCK + threadIdx.x]);
-            if (dbg) atomicAdd(dbg, 1);
-            ++lo;
-        }
-    }
-    __device__ void pushIf(int v, bool wanted) {
-        g_tstack[(n & MASK) * TBLOCK + threadIdx.x] = v;
-        n += wanted ? 1 : 0;
-    }
-    __device__ void pushReserved(int v) {
-        g_tstack[(n & MASK) * TBLOCK + threadIdx.x] = v;
-        ++n;
-    }
     __device__ int pop() {
         --n;
         int v = g_tstack[(n & MASK) * TBLOCK + threadIdx.x];  // always a ds_read
@@ -409,31 +333,11 @@ struct LdsStackT {
     __device__ bool empty() const { return n == 0; }
 };
 
-__device__ inline void LoadTreeTop(const FastBVH &bvh) {
-    const U4 *src = reinterpret_cast<const U4 *>(bvh.nodes);
-    if constexpr (TOP_NODES == 0) return;
-    const int n = QNODE_U4 * (bvh.nNodes < TOP_NODES ? bvh.nNodes : TOP_NODES);
-    for (int i = threadIdx.x; i < n; i += TBLOCK) g_top[i] = src[i];
-    __syncthreads();
-}
-// a node's 16-byte words: tree top from LDS, the rest from global memory.  (Measured: splitting the two fetch paths
-// into separate loops so that each is a pure ds_read / global_load costs more in extra wave serialisation than the
-// merged flat load does: 0.57 ms vs 0.45 ms per launch.)
-#ifndef WF_FETCH_ALL
-#define WF_FETCH_ALL 0
-#endif
+// a node's 16-byte words: a plain global load.  (Rounds 1-5 copied the top of the tree into LDS per workgroup, and a node was then fetched
+// through a pointer into either LDS or global memory, which the compiler can only issue as FLAT loads.  Measured and dropped in round 6:
+// closest-hit 31.3 -> 28.4 ms, any-hit 13.5 -> 12.5 ms per 16 spp on the spec scene, profiles/r06_tree_top_global_loads_and_knobs_ab_sm16.txt.)
 __device__ inline void FetchNode(const FastBVH &bvh, int node, U4 *n) {
-    if constexpr (TOP_NODES == 0) {
-        const U4 *p = reinterpret_cast<const U4 *>(bvh.nodes + node);
-        for (int k = 0; k < QNODE_U4; ++k) n[k] = p[k];
-#if WF_FETCH_ALL
-        // the child references (the node's last 16 bytes) are only read when a child is hit, and the compiler sinks their load behind the
-        // slab tests: a second dependent round trip per step.  Pinned here, the four loads of a node issue together.
-        asm volatile("" : "+v"(n[QNODE_U4 - 1].x), "+v"(n[QNODE_U4 - 1].y), "+v"(n[QNODE_U4 - 1].z), "+v"(n[QNODE_U4 - 1].w));
-#endif
-        return;
-    }
-    const U4 *p = node < TOP_NODES ? g_top + QNODE_U4 * node : reinterpret_cast<const U4 *>(bvh.nodes + node);
+    const U4 *p = reinterpret_cast<const U4 *>(bvh.nodes + node);
     for (int k = 0; k < QNODE_U4; ++k) n[k] = p[k];
 }
 
@@ -526,24 +430,12 @@ struct GeneralPrims {
         if constexpr (GEN == 1) return false;
         else return QuadricIntersect<GEN == 3>(sv, prim, w.o, dir(), tMax, qh);
     }
-    __device__ void exact(RayWalk &wm) const { WalkMakeExact(bvh, wm, WorldRayO(), WorldRayD()); }
 };
-// the two-level walk of a scene without alpha cut-outs or quadrics: only the lazy instance transition's hook (wf_traverse.h)
-template <bool DEFER = false>
-struct InstOnlyPrims {
-    static constexpr bool pairBands = false;
-    static constexpr bool deferGeneral = DEFER;
-    const FastBVH &bvh;
-    __device__ bool accept(int, float, float, float) const { return true; }
-    __device__ bool sphere(int, float, QuadricHit *) const { return false; }
-    __device__ void exact(RayWalk &wm) const { WalkMakeExact(bvh, wm, WorldRayO(), WorldRayD()); }
-};
-struct DeferOnlyPrims {   // the one-level triangle walk of a scene that also holds primitives of the other class
+struct DeferOnlyPrims {   // the triangle walk of a scene that also holds primitives of the other class
     static constexpr bool pairBands = false;
     static constexpr bool deferGeneral = true;
     __device__ bool accept(int, float, float, float) const { return true; }
     __device__ bool sphere(int, float, QuadricHit *) const { return false; }
-    __device__ void exact(RayWalk &) const {}
 };
 // The part of a "while-while" iteration that follows the interior descent: every lane sits at a leaf run, at an instance transition
 // (an instance entry popped from the stack, or the NODE_EXIT marker) or is done.  Leaves are processed first; the transitions —
@@ -568,40 +460,30 @@ __device__ inline int LeafPhase(const SceneView &sv, const FastBVH &bvh, RayWalk
     constexpr bool DF = GenDefer(GENX), ANIM = GenAnim(GENX);
     if constexpr (INST) {
         bool tr = AtTransition(w.node);
-        // (round 4, WF_LAZY_INST) a lane that sits at a leaf while its ray state is not exact for the space it walks (RayWalk::lazy)
-        // owes WalkMakeExact — the reference's interval-arithmetic ray transform, the shear, the slab constants again — before its
-        // leaf can be processed: PARKED like a transition, so that this code too runs with several lanes at once (inside the leaf
-        // loop, lane by lane, the lazy transition LOST: closest 49.4 vs 45.0 ms, any-hit 26.1 vs 23.0)
-        const bool owes = WF_LAZY_INST && w.node != NODE_NONE && !tr && WF_LAZY_GET(w) != 0;
-        if (w.node < 0 && w.node != NODE_NONE && !tr && !owes) {   // (w.node >= 0: a lane the descent left at an interior node, WF_SCHED_Q)
+        if (w.node < 0 && w.node != NODE_NONE && !tr) {   // (w.node >= 0: a lane the descent left at an interior node, WF_SCHED_Q)
             if constexpr (GEN > 0) LeafStep<ANY, true, true>(bvh, w, st, GeneralPrims<Fetch, GEN, DF, ANIM>{sv, bvh, w, fetch, idx});
-            else LeafStep<ANY, false, true>(bvh, w, st, InstOnlyPrims<DF>{bvh});
+            else if constexpr (DF) LeafStep<ANY, false, true>(bvh, w, st, DeferOnlyPrims{});
+            else LeafStep<ANY, false, true>(bvh, w, st);
         }
         if constexpr (WF_TRANS_BATCH > 0) {
             tr = AtTransition(w.node);
-            const int nT = __popcll(__ballot(tr || owes));
+            const int nT = __popcll(__ballot(tr));
             if (nT == 0) return 0;
 #if WF_TRANS_Q > 0
             {
                 // (round 6) ... and, like the descent (WalkDescend), until the lanes that wait for a transition are at least WF_TRANS_Q / 4 of
                 // the lanes that have nodes and leaves to visit: the transition is the walk's most expensive code (~400 instructions)
-                const int nO = __popcll(__ballot(w.node != NODE_NONE && !tr && !owes));
+                const int nO = __popcll(__ballot(w.node != NODE_NONE && !tr));
                 if (nO > 0 && (nT < WF_TRANS_BATCH || 4 * nT < WF_TRANS_Q * nO)) return 0;
             }
 #else
-            if (nT < WF_TRANS_BATCH && __any(w.node != NODE_NONE && !tr && !owes)) return 0;   // parked: the others still have nodes and leaves to visit
+            if (nT < WF_TRANS_BATCH && __any(w.node != NODE_NONE && !tr)) return 0;   // parked: the others still have nodes and leaves to visit
 #endif
         } else tr = AtTransition(w.node);
-        if (owes) WalkMakeExact(bvh, w, WorldRayO(), WorldRayD());   // (its leaf is processed in the next iteration)
-        else if (tr) {
+        if (tr) {
             const V3 o = WorldRayO(), d = WorldRayD();
-#if WF_FUSE_EXIT_ENTER
             if (w.node == NODE_EXIT) ExitInstance(bvh, w, st, o, d);
             if (IsInstanceEntry(w.node)) EnterInstance<ANIM>(bvh, w, st, o, d, (int)((~(unsigned)w.node) >> 4) - INST_FIRST, ANIM ? g_time[threadIdx.x] : 0.f);   // (also the entry an exit has just popped)
-#else
-            if (w.node == NODE_EXIT) ExitInstance(bvh, w, st, o, d);
-            else EnterInstance<ANIM>(bvh, w, st, o, d, (int)((~(unsigned)w.node) >> 4) - INST_FIRST, ANIM ? g_time[threadIdx.x] : 0.f);
-#endif
         }
         return WF_WALK_STATS ? __popcll(__ballot(tr)) : 0;
     } else if (w.node < 0 && w.node != NODE_NONE) {
@@ -747,7 +629,6 @@ __device__ inline bool WalkDescend(const RayWalk &w) {
 }
 template <bool ANY, int GEN, bool INST = false, typename Fetch, typename Finish>
 __device__ inline void BatchTrace(const SceneView &sv, const FastBVH &bvh, int n, LdsStackT &st, Fetch fetch, Finish finish, int *cursor = nullptr, int chunk = 4) {
-    LoadTreeTop(bvh);
     // cursor != nullptr (only when `finish` has no workgroup barrier): every wave takes its next `chunk` x 64 rays from a shared
     // cursor, so a wave with short walks serves more of the queue and the launch ends without a tail of waves that drew long ones
     // (one returning atomic per chunk x 64 rays: a counter sustains ~88 of them per microsecond)
@@ -783,11 +664,8 @@ __device__ inline void BatchTrace(const SceneView &sv, const FastBVH &bvh, int n
             V3 o, d;
             float tMax;
             fetch(idx, &o, &d, &tMax);
-            float sa[3], sb[3];
-            WalkInit(bvh, w, o, d, tMax, sa, sb);
+            WalkInit(bvh, w, o, d, tMax);
             if constexpr (INST || GEN > 0) StoreWorldRay(o, d);
-            if constexpr (INST && WF_SAVE_WORLD == 1) st.saveWorld(w);
-            if constexpr (INST && WF_SAVE_WORLD == 2) st.saveWorldLds(sa, sb, w.sh);
             st.reset();
         }
         // (Measured and dropped: parking a lane's first leaf and descending on speculatively — 11 % slower; continuous
@@ -827,7 +705,7 @@ __device__ inline void BatchTrace(const SceneView &sv, const FastBVH &bvh, int n
 // variant: no workgroup barrier) and deals them the next rays of the wave's private run of the queue (runs of chunk x 64 rays, taken
 // from the shared cursor with one returning atomic each, or dealt statically when the queue is short).  Between refills the loop is
 // the same "while-while" as before, so the lanes of one refill — neighbours in the queue — descend the top of the tree together
-// (LDS-cached nodes), which is what the continuous per-lane refill measured in round 2 lost (5x the L1 line accesses).
+// (the same cache lines), which is what the continuous per-lane refill measured in round 2 lost (5x the L1 line accesses).
 #ifndef WF_REFILL_AT
 #define WF_REFILL_AT 40
 #endif
@@ -840,7 +718,6 @@ __device__ inline void BatchTrace(const SceneView &sv, const FastBVH &bvh, int n
 template <bool ANY, int GEN, bool INST = false, bool DEFER = false, typename Fetch, typename Finish>
 __device__ inline void BatchTraceRefill(const SceneView &sv, const FastBVH &bvh, int n, LdsStackT &st, Fetch fetch, Finish finish, int *cursor = nullptr, int chunk = 4,
                                         int workBlocks = 0) {
-    LoadTreeTop(bvh);
     if (workBlocks <= 0) workBlocks = (int)gridDim.x;   // (the first workBlocks workgroups of the grid walk rays; the rest, if any, have another job)
     if (n < 2 * workBlocks * TBLOCK) cursor = nullptr;
     if (cursor && st.dbg && threadIdx.x == 0 && blockIdx.x == 0) atomicOr(st.dbg + 3, 1);
@@ -864,19 +741,9 @@ __device__ inline void BatchTraceRefill(const SceneView &sv, const FastBVH &bvh,
     w.inst = w.curInst = -1;
     WalkStats ws_;
     auto retire = [&]() {
-        // DEFER: `finish` queues a near-tie ray and the kernel resolves it after its walks (DrainRetrace) — the reference-order walk inlined HERE
-        // costs the closest-hit kernel 37 % (76.9 vs 56.0 ms per 16 spp on the spec scene), without it the refill gains 28 % (40.3 ms)
-        if constexpr (!ANY && RetraceInline(GenBase(GEN)) && !DEFER) {
-            if (WalkAmbiguous(w)) {
-                V3 o, d;
-                float t0;
-                fetch(idx, &o, &d, &t0);
-                const float tB = __builtin_fminf(2 * WalkBound(bvh, WalkT(w)) - WalkT(w), t0);
-                const RefHit rh = RetraceRefOrder<GenBase(GEN), GenAnim(GEN)>(bvh.sv, o.x, o.y, o.z, d.x, d.y, d.z, tB, st.spill, st.spillStride, st.rows, st.dbg, GenAnim(GEN) ? g_time[threadIdx.x] : 0.f);
-                w.prim = rh.prim; w.inst = rh.inst; w.route = rh.route;
-                w.tMax = rh.t; w.b0 = rh.b0; w.b1 = rh.b1; w.b2 = rh.b2;
-            }
-        }
+        // (a closest-hit walk here never re-walks a near tie itself: with DEFER `finish` queues the ray and the kernel resolves it after its
+        //  walks (DrainRetrace), otherwise the separate re-trace launch does.  The reference-order walk inlined HERE cost the closest-hit
+        //  kernel 37 %: 76.9 vs 56.0 ms per 16 spp on the spec scene; without it the refill gains 28 %, 40.3 ms)
         finish(idx, true, w);
         idx = -1;
     };
@@ -924,11 +791,8 @@ __device__ inline void BatchTraceRefill(const SceneView &sv, const FastBVH &bvh,
                 V3 o, d;
                 float tMax;
                 fetch(idx, &o, &d, &tMax);
-                float sa[3], sb[3];
-                WalkInit(bvh, w, o, d, tMax, sa, sb);
+                WalkInit(bvh, w, o, d, tMax);
                 if constexpr (INST || GEN > 0) StoreWorldRay(o, d);
-                if constexpr (INST && WF_SAVE_WORLD == 1) st.saveWorld(w);
-                if constexpr (INST && WF_SAVE_WORLD == 2) st.saveWorldLds(sa, sb, w.sh);
                 st.reset();
             }
             if (exhausted && !__any(w.node != NODE_NONE)) break;
@@ -948,29 +812,18 @@ __device__ inline void BatchTraceRefill(const SceneView &sv, const FastBVH &bvh,
     ws_.flush(st.dbg, ANY ? 1 : 0);
     if (idx >= 0) retire();   // the rays still held when the queue ran out
 }
-// Measured on the spec scene (16 spp, same box; gpurun_out/r3b_ab_sm16.txt): the any-hit walk gains (30.1 -> 25.2 ms at a threshold of
-// 40 lanes, 26.2 at 24, 27.5 at 12), the closest-hit walk loses (58.3 -> 65.7 / 74.9 / 72.2 ms: it carries the hit record and the
-// near-tie code through the refill, 400 B of scratch instead of 304) — so only the any-hit kernels use it by default.
-#ifndef WF_REFILL_SHADOW
-#define WF_REFILL_SHADOW 1
-#endif
-#ifndef WF_REFILL_INLINE
-#define WF_REFILL_INLINE 0    // diagnostic: the closest-hit walk refills its lanes but re-walks near ties inline (no queue, no service workgroups)
-#endif
-#ifndef WF_REFILL_GEN2
-#define WF_REFILL_GEN2 1   // spec scene + one sphere, 16 spp, same box: closest-hit 73.4 -> 64.6 ms (profiles/r04_one_sphere_refill_ab_sm16.txt)
-#endif
-#ifndef WF_REFILL_CLOSEST
-#define WF_REFILL_CLOSEST 1   // with the near-tie walk out of the loop (DrainRetrace): 56.0 -> see DESIGN 4.1
-#endif
-// PERLANE: `finish` has no workgroup barrier (every caller but the workgroup-routed closest-hit variant, SPLIT = false)
-// DEFER (closest-hit only): the caller queues near-tie rays in `finish` and drains the queue itself after this returns
+// Which walk a launch takes.  Every PERLANE launch (`finish` has no workgroup barrier: every caller but the workgroup-routed closest-hit
+// variant, SPLIT = false) walks with refill:
+//   any-hit: spec scene, 16 spp, same box (round 3): 30.1 -> 25.2 ms at a threshold of 40 lanes, 26.2 at 24, 27.5 at 12;
+//   closest-hit with the near-tie walk out of the loop (DEFER: the caller queues near-tie rays in `finish` and drains the queue itself
+//   after this returns, DrainRetrace): 56.0 -> see DESIGN 4.1;
+//   closest-hit of scenes with general primitives (GEN >= 2, whose near ties go to the separate re-trace launch): spec scene + one
+//   sphere, 73.4 -> 64.6 ms (profiles/r04_one_sphere_refill_ab_sm16.txt).
+// The other closest-hit launches walk with BatchTrace, which re-walks near ties inline.
 template <bool ANY, int GEN, bool INST, bool PERLANE, bool DEFER = false, typename Fetch, typename Finish>
 __device__ inline void TraceQueue(const SceneView &sv, const FastBVH &bvh, int n, LdsStackT &st, Fetch fetch, Finish finish, int *cursor = nullptr, int chunk = 4,
                                   int workBlocks = 0) {
-    // (the closest-hit walk of scenes with general primitives, GEN >= 2: its near-ties go to the separate re-trace launch anyway, so the
-    //  refill loop carries no reference-order walk — WF_REFILL_GEN2, round 4)
-    if constexpr (PERLANE && (ANY ? WF_REFILL_SHADOW != 0 : (DEFER || WF_REFILL_INLINE != 0 || (WF_REFILL_GEN2 != 0 && !RetraceInline(GenBase(GEN)))))) BatchTraceRefill<ANY, GEN, INST, DEFER>(sv, bvh, n, st, fetch, finish, cursor, chunk, workBlocks);
+    if constexpr (PERLANE && (ANY || DEFER || !RetraceInline(GenBase(GEN)))) BatchTraceRefill<ANY, GEN, INST, DEFER>(sv, bvh, n, st, fetch, finish, cursor, chunk, workBlocks);
     else BatchTrace<ANY, GEN, INST>(sv, bvh, n, st, fetch, finish, cursor, chunk);
 }
 // The near-tie rays of a closest-hit launch, resolved inside the launch (round 3, second step).  A walk that ends on a near-tie publishes
@@ -1075,17 +928,13 @@ __device__ inline void DrainRetrace(const SceneView &sv, const WorkState &ws, co
 constexpr uint32_t ROUTE_SKIP = 0x80000000u;   // near-tie: the re-trace routes this ray
 // The occupancy target of a walk kernel.  The general-primitive variants (GEN >= 2) cannot reach the triangle kernels' 4-5 waves, but the
 // target still matters: the allocator spills towards it before the callees' frames are added (asked for 3 / 2 waves, which they could
-// reach, GEN = 2 / 3 ended at 2 / 1; asked for the triangle kernels' 4-5 they end at 3 / 2).  WF_TWAVES_GEN2: see the Makefile's note on
-// zero-initialised locals, which cost GEN = 2 fifteen registers at the old target.
-#ifndef WF_TWAVES_GEN2
-#define WF_TWAVES_GEN2 0   // 0: the triangle kernels' target
-#endif
+// reach, GEN = 2 / 3 ended at 2 / 1; asked for the triangle kernels' 4-5 they end at 3 / 2).  GEN = 2 takes the triangle kernels' target.
 // (GEN = 3, the curve kernels: at the one-level kernels' 5-wave target they were the only kernels of the library that spilled an SGPR-spill
 //  carrier register — tools/check_spill_carriers.py; at the two-level kernels' 4 they do not)
 // (round 5: with alpha textures on curves the GEN = 3 kernels reach the curve intersector through the alpha recursion as well — a chain of
 //  out-of-line callees the compiler gives 200+ VGPRs; it reported "final occupancy is 2" for every target above, and at a target of 4 the
 //  kernels spilled carriers again: their target is what they get)
-constexpr int TWavesFor(int gen, int triangleWaves) { return gen == 2 && WF_TWAVES_GEN2 > 0 ? WF_TWAVES_GEN2 : gen == 3 ? 2 : triangleWaves; }
+constexpr int TWavesFor(int gen, int triangleWaves) { return gen == 3 ? 2 : triangleWaves; }
 // GENX: 0 - 3 as above; 4 / 5 = GEN 0 / 1 handing rays that meet a quadric / patch / curve to `deferQ` (TWO-CLASS TRAVERSAL).
 // list != nullptr: walk the rays list[0 .. counters[CNT_DEFER]) of the queue instead of all of it (the second launch of that scheme).
 template <int GENX, bool INST = false, bool SPLIT = false>
@@ -1095,10 +944,10 @@ __global__ void __launch_bounds__(TBLOCK, TWavesFor(GenBase(GENX), INST ? WF_TWA
     if constexpr (!SPLIT) list = nullptr;   // (only the launches of the routing-split path take a list)
     const int n = list ? ws.counters[(CNT_DEFER) * CNT_STRIDE] : ws.counters[(CNT_RAY0 + cur) * CNT_STRIDE];
     const int gtid = blockIdx.x * TBLOCK + threadIdx.x, stride = gridDim.x * TBLOCK;
-    LdsStackT st{sp.base + gtid, stride, 0, 0, sp.rows, sp.dbg, sp.save + gtid};
+    LdsStackT st{sp.base + gtid, stride, 0, 0, sp.rows, sp.dbg};
     const RayQueueV q = ws.rq[cur];
     // near-ties resolved by this launch itself: the kernels that would otherwise inline the reference-order walk (RetraceInline), walking with refill
-    constexpr bool DRAIN = SPLIT && RetraceInline(GEN) && WF_REFILL_CLOSEST != 0 && WF_REFILL_INLINE == 0;
+    constexpr bool DRAIN = SPLIT && RetraceInline(GEN);
     const int workBlocks = DRAIN ? (int)gridDim.x - ServiceBlocks() : (int)gridDim.x;
     if (DRAIN && (int)blockIdx.x >= workBlocks) { DrainRetrace<GEN, INST, GenAnim(GENX)>(sv, ws, bvh, cur, st, true); return; }   // a service workgroup
     TraceQueue<false, GENX, INST, SPLIT, DRAIN>(
@@ -1174,74 +1023,6 @@ __global__ void __launch_bounds__(RBLOCK) k_route_hits(const SceneView svArg, Wo
         KRouteHitBlock<GENERAL>(sv, ws, cur, i, valid, (int)FloatToBits(h.x), route, tHit, h.y, h.z, h.w, inst);
     }
 }
-// ---- ray-coherence pass -----------------------------------------------------------------------------------------
-// Rays past the first bounce arrive in the order the material kernels pushed them: neighbouring lanes start anywhere in the scene and
-// point anywhere, a wavefront's 64 walks share neither nodes nor length.  Before such a queue is traced it is SORTED by a key made of
-// the cell of the ray's origin (Morton order of a 2^b grid over the scene bounds) and its direction (Morton order of the octahedral
-// map), and the queue is permuted physically — one gather per ray, after which the traversal and every later stage of the depth
-// read coalesced again.  Results do not depend on the order of a queue (each item owns its pixel-sample slot), only the time does.
-extern "C" int wf_sort_pairs_u32(hipStream_t stream, void *temp, size_t *tempBytes, const uint32_t *keysIn, uint32_t *keysOut, const uint32_t *valsIn, uint32_t *valsOut,
-                                 unsigned n, unsigned endBit);
-__device__ inline uint32_t Part1By2(uint32_t x) {  // 10 bits -> every third bit
-    x &= 0x3ff;
-    x = (x ^ (x << 16)) & 0xff0000ff;
-    x = (x ^ (x << 8)) & 0x0300f00f;
-    x = (x ^ (x << 4)) & 0x030c30c3;
-    x = (x ^ (x << 2)) & 0x09249249;
-    return x;
-}
-__device__ inline uint32_t Part1By1(uint32_t x) {  // 16 bits -> every second bit
-    x &= 0xffff;
-    x = (x ^ (x << 8)) & 0x00ff00ff;
-    x = (x ^ (x << 4)) & 0x0f0f0f0f;
-    x = (x ^ (x << 2)) & 0x33333333;
-    x = (x ^ (x << 1)) & 0x55555555;
-    return x;
-}
-struct SortGrid { float base[3], scale[3]; int obits, dbits; };
-__device__ inline uint32_t RaySortKey(const SortGrid &g, F4 o, F4 d) {
-    const int oMax = (1 << g.obits) - 1;
-    int cx = min(max((int)((o.x - g.base[0]) * g.scale[0]), 0), oMax);
-    int cy = min(max((int)((o.y - g.base[1]) * g.scale[1]), 0), oMax);
-    int cz = min(max((int)((o.z - g.base[2]) * g.scale[2]), 0), oMax);
-    uint32_t key = Part1By2(cx) | (Part1By2(cy) << 1) | (Part1By2(cz) << 2);
-    if (g.dbits > 0) {
-        // octahedral map of the direction to [0, 1)^2
-        float inv = 1.f / (fabsf(d.x) + fabsf(d.y) + fabsf(d.z));
-        float u = d.x * inv, v = d.y * inv;
-        if (d.z < 0) {
-            float tu = (1 - fabsf(v)) * (u >= 0 ? 1.f : -1.f), tv = (1 - fabsf(u)) * (v >= 0 ? 1.f : -1.f);
-            u = tu; v = tv;
-        }
-        const int dMax = (1 << g.dbits) - 1;
-        int du = min(max((int)((u * .5f + .5f) * (dMax + 1)), 0), dMax), dv = min(max((int)((v * .5f + .5f) * (dMax + 1)), 0), dMax);
-        key = (key << (2 * g.dbits)) | Part1By1(du) | (Part1By1(dv) << 1);
-    }
-    return key;
-}
-__global__ void __launch_bounds__(BLOCK) k_ray_sort_keys(const F4 *o, const F4 *d, int n, SortGrid g, uint32_t *keys, uint32_t *vals) {
-    for (int i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) {
-        keys[i] = RaySortKey(g, o[i], d[i]);
-        vals[i] = (uint32_t)i;
-    }
-}
-__global__ void __launch_bounds__(BLOCK) k_permute_rays(RayQueueV src, RayQueueV dst, const uint32_t *perm, int n) {
-    for (int i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) {
-        const uint32_t j = perm[i];
-        F4 a = src.o[j], b = src.d[j], c = src.beta[j], e = src.r_u[j], f = src.r_l[j], g = src.ctx0[j], h = src.ctx1[j], k = src.ctx2[j];
-        I4 m = src.meta[j];
-        dst.o[i] = a; dst.d[i] = b; dst.beta[i] = c; dst.r_u[i] = e; dst.r_l[i] = f; dst.ctx0[i] = g; dst.ctx1[i] = h; dst.ctx2[i] = k; dst.meta[i] = m;
-    }
-}
-__global__ void __launch_bounds__(BLOCK) k_permute_shadow(ShadowQueueV src, ShadowQueueV dst, const uint32_t *perm, int n) {
-    for (int i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) {
-        const uint32_t j = perm[i];
-        F4 a = src.o[j], b = src.d[j], c = src.Ld[j], e = src.r_u[j], f = src.r_l[j];
-        dst.o[i] = a; dst.d[i] = b; dst.Ld[i] = c; dst.r_u[i] = e; dst.r_l[i] = f;
-        if (src.medium) dst.medium[i] = src.medium[j];
-    }
-}
-
 // the rays k_closest_fast marked as near-ties, in the reference's own traversal order (rare: coplanar overlapping geometry)
 __global__ void __launch_bounds__(BLOCK) k_closest_retrace(const SceneView sv, WorkState ws, int cur, int *stackSpill) {
     const int n = ws.counters[(CNT_RETRACE) * CNT_STRIDE];
@@ -1298,7 +1079,7 @@ __global__ void __launch_bounds__(TBLOCK, TWavesFor(GenBase(GEN), INST ? WF_TWAV
     const SceneView &sv = SvOf<false>(svArg);
     const int n = list ? ws.counters[(CNT_DEFER_SHADOW) * CNT_STRIDE] : ws.counters[(CNT_SHADOW) * CNT_STRIDE];
     const int gtid = blockIdx.x * TBLOCK + threadIdx.x, stride = gridDim.x * TBLOCK;
-    LdsStackT st{sp.base + gtid, stride, 0, 0, sp.rows, sp.dbg, sp.save + gtid};
+    LdsStackT st{sp.base + gtid, stride, 0, 0, sp.rows, sp.dbg};
     TraceQueue<true, GEN, INST, true>(
         sv, bvh, n, st,
         [&](int i0, V3 *o, V3 *d, float *tMax) {
@@ -1323,7 +1104,7 @@ __global__ void __launch_bounds__(TBLOCK, TWavesFor(GenBase(GEN), INST ? WF_TWAV
 template <int GEN, bool INST>
 __global__ void __launch_bounds__(TBLOCK) k_trace_closest_fast(const SceneView sv, FastBVH bvh, int n, const float *rays, wf_hit_record *out, SpillArea sp) {
     const int gtid = blockIdx.x * TBLOCK + threadIdx.x, stride = gridDim.x * TBLOCK;
-    LdsStackT st{sp.base + gtid, stride, 0, 0, sp.rows, sp.dbg, sp.save + gtid};
+    LdsStackT st{sp.base + gtid, stride, 0, 0, sp.rows, sp.dbg};
     TraceQueue<false, GEN, INST, true>(
         sv, bvh, n, st,
         [&](int i, V3 *o, V3 *d, float *tMax) {
@@ -1344,7 +1125,7 @@ __global__ void __launch_bounds__(TBLOCK) k_trace_closest_fast(const SceneView s
 template <int GEN, bool INST>
 __global__ void __launch_bounds__(TBLOCK) k_trace_any_fast(const SceneView sv, FastBVH bvh, int n, const float *rays, int32_t *occluded, SpillArea sp) {
     const int gtid = blockIdx.x * TBLOCK + threadIdx.x, stride = gridDim.x * TBLOCK;
-    LdsStackT st{sp.base + gtid, stride, 0, 0, sp.rows, sp.dbg, sp.save + gtid};
+    LdsStackT st{sp.base + gtid, stride, 0, 0, sp.rows, sp.dbg};
     TraceQueue<true, GEN, INST, true>(
         sv, bvh, n, st,
         [&](int i, V3 *o, V3 *d, float *tMax) {
@@ -1364,80 +1145,18 @@ __global__ void __launch_bounds__(BLOCK) k_resolve_mix(const SceneView sv, WorkS
 #ifndef WF_MEDIUM_WAVES
 #define WF_MEDIUM_WAVES 2
 #endif
-// (round 6) WAVE-LEVEL REFILL of the delta-tracking loop.  Until round 5 a wave kept its 64 items until the longest
-// of their walks ended: on the cloud scene 24 % of the VALU lanes were active over a wave's lifetime (walks of one to a hundred and more
-// steps: majorant cells crossed, null collisions taken), at two waves per SIMD that wait for their density gathers 79 % of the time.
-// Now the kernel is persistent (one resident grid, work dealt in runs of 64 items from a shared cursor): a wave whose active lanes drop
-// to WF_MEDIUM_REFILL_AT or fewer takes new items for its idle lanes (MediumTrackBegin) and goes on stepping; a lane whose walk ends
-// retires its item at once (MediumTrackEnd: per-lane stores, wave-aggregated queue pushes — nothing waits for the workgroup).  The same
-// operations per item in the same order as the one-loop form (the CPU checker's KSampleMediumInteraction): bit-identical images.
-#ifndef WF_MEDIUM_REFILL
-#define WF_MEDIUM_REFILL 0
-#endif
-#ifndef WF_MEDIUM_REFILL_AT
-#define WF_MEDIUM_REFILL_AT 40
-#endif
-#ifndef WF_MEDIUM_STEPS
-#define WF_MEDIUM_STEPS 4   // steps between two looks at the wave's occupancy
-#endif
+// (round 6, measured and dropped: a persistent form of this kernel with wave-level refill of the delta-tracking loop, VERDICT r5 item 8 —
+//  a wave whose active lanes dropped below a threshold took new items for its idle lanes from a shared work cursor)
 // LEAN: every medium of the scene is homogeneous or a non-emissive uniform grid (ctx->mediumLean, set at upload): the kernel is built without the
 // procedural cloud, NanoVDB, RGB-grid and blackbody code and compiled for WF_MEDIUM_WAVES_LEAN waves
 #ifndef WF_MEDIUM_WAVES_LEAN
 #define WF_MEDIUM_WAVES_LEAN 3
 #endif
 template <bool LEAN>
-__global__ void __launch_bounds__(BLOCK, LEAN ? WF_MEDIUM_WAVES_LEAN : WF_MEDIUM_WAVES) k_medium_sample(const SceneView sv, WorkState ws, int cur, int *cursor) {
+__global__ void __launch_bounds__(BLOCK, LEAN ? WF_MEDIUM_WAVES_LEAN : WF_MEDIUM_WAVES) k_medium_sample(const SceneView sv, WorkState ws, int cur) {
     const int n = ws.counters[(CNT_MEDIUM_SAMPLE) * CNT_STRIDE];
-#if WF_MEDIUM_REFILL
-    const int lane = threadIdx.x & 63;
-    const int waveId = (blockIdx.x * BLOCK + threadIdx.x) >> 6, nWaves = ((int)gridDim.x * BLOCK) >> 6;
-    if (n < 2 * nWaves * 64) cursor = nullptr;   // (a short queue is dealt statically: every wave starts at once, no atomics)
-    MediumTrack s;
-    s.i = -1;
-    int next = 0, end = 0, staticJ = 0;   // the wave's private run [next, end) of queue indices (uniform)
-    bool exhausted = false;
-    while (true) {
-        const unsigned long long act = __ballot(s.i >= 0);
-        const int nAct = __popcll(act);
-        if (nAct <= WF_MEDIUM_REFILL_AT && !exhausted) {
-            const bool idle = s.i < 0;
-            const int need = 64 - nAct;
-            const int rank = __popcll(~act & ((1ull << lane) - 1ull));
-            int served = 0, qi = -1;
-            while (served < need) {
-                if (next >= end) {
-                    int b;
-                    if (cursor) {
-                        b = 0;
-                        if (lane == 0) b = atomicAdd(cursor, 64);
-                        b = __builtin_amdgcn_readfirstlane(b);
-                    } else {
-                        b = (staticJ * nWaves + waveId) * 64;
-                        ++staticJ;
-                    }
-                    next = b;
-                    end = b + 64 < n ? b + 64 : n;
-                    if (next >= n) { exhausted = true; break; }
-                }
-                const int take = need - served < end - next ? need - served : end - next;
-                if (idle && rank >= served && rank < served + take) qi = next + (rank - served);
-                next += take;
-                served += take;
-            }
-            if (qi >= 0) MediumTrackBegin<LEAN>(sv, ws, cur, qi, s);
-            if (!__any(s.i >= 0)) break;   // (nothing was dealt and nothing is left)
-        } else if (nAct == 0) break;
-        for (int k = 0; k < WF_MEDIUM_STEPS; ++k) {
-            if (s.i >= 0 && !MediumTrackStep<LEAN>(sv, ws, cur, s)) {
-                MediumTrackEnd(sv, ws, cur, s);
-                s.i = -1;
-            }
-        }
-    }
-#else
     // (the nested-loop form of rounds 1-5 measured 43.2 ms against this form's 36.5 on the cloud scene, same box: profiles/r06_medium_nested_vs_state_machine_ab_cloud16.txt)
     for (int i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) KSampleMediumInteraction<LEAN>(sv, ws, cur, i);
-#endif
 }
 __global__ void __launch_bounds__(BLOCK) k_medium_route(const SceneView sv, WorkState ws, int cur) {
     const int n = ws.counters[(CNT_MEDIUM_ROUTE) * CNT_STRIDE];
@@ -1480,8 +1199,7 @@ template <bool ALPHA, bool MLEAN = false>
 __global__ void __launch_bounds__(TBLOCK) k_shadow_tr_fast(const SceneView sv, WorkState ws, FastBVH bvh, SpillArea sp) {
     const int n = ws.counters[(CNT_SHADOW) * CNT_STRIDE];
     const int gtid = blockIdx.x * TBLOCK + threadIdx.x, stride = gridDim.x * TBLOCK;
-    LdsStackT st{sp.base + gtid, stride, 0, 0, sp.rows, sp.dbg, sp.save + gtid};
-    LoadTreeTop(bvh);
+    LdsStackT st{sp.base + gtid, stride, 0, 0, sp.rows, sp.dbg};
     for (int i = gtid; i < n; i += stride)
         KTraceTransmittance<false, MLEAN>(sv, ws, i, [&](V3 o, V3 d, float tMax, int *prim, int *inst, float *b0, float *b1, float *b2) {
             RayWalk w;
@@ -1530,7 +1248,7 @@ template <int GEN, bool INST>
 __global__ void __launch_bounds__(TBLOCK, INST ? WF_TWAVES_INST : WF_TWAVES_CLOSEST) k_tr_trace(const SceneView sv, WorkState ws, FastBVH bvh, int cur, SpillArea sp) {
     const int n = ws.counters[(CNT_TR0 + cur) * CNT_STRIDE];
     const int gtid = blockIdx.x * TBLOCK + threadIdx.x, stride = gridDim.x * TBLOCK;
-    LdsStackT st{sp.base + gtid, stride, 0, 0, sp.rows, sp.dbg, sp.save + gtid};
+    LdsStackT st{sp.base + gtid, stride, 0, 0, sp.rows, sp.dbg};
     const int32_t *q = ws.trQ[cur];
     TraceQueue<false, GEN, INST, true>(
         sv, bvh, n, st,
@@ -1595,12 +1313,6 @@ __global__ void __launch_bounds__(BLOCK) k_handle_emissive(const SceneView svArg
 }
 // the material kernels live in wf_mat.hip (one translation unit per material type)
 extern "C" {
-#define WF_DECL_MAT(n) void wf_launch_eval_material_##n##_0(hipStream_t, int, const SceneView *, const WorkState *, int); \
-                       void wf_launch_eval_material_##n##_1(hipStream_t, int, const SceneView *, const WorkState *, int); \
-                       void wf_launch_eval_material_##n##_2(hipStream_t, int, const SceneView *, const WorkState *, int);
-#if defined(WF_HAVE_FUSED_MAT)   // (make MATFUSED=1: the one-kernel material stage of rounds 1-4 beside the split one, for same-box A/B runs)
-WF_DECL_MAT(1) WF_DECL_MAT(2) WF_DECL_MAT(3) WF_DECL_MAT(4) WF_DECL_MAT(5) WF_DECL_MAT(6) WF_DECL_MAT(7) WF_DECL_MAT(8) WF_DECL_MAT(9) WF_DECL_MAT(10)
-#endif
 // the two halves of the material stage (wf_mat.hip): shade variant 0 | 1 (lean) | 2 | 3, next-event estimation variant 0 | 1
 #define WF_DECL_SPLIT(n) void wf_launch_mat_shade_##n##_0(hipStream_t, int, const SceneView *, const WorkState *, int); \
                          void wf_launch_mat_shade_##n##_1(hipStream_t, int, const SceneView *, const WorkState *, int); \
@@ -1659,9 +1371,6 @@ __global__ void __launch_bounds__(BLOCK) k_update_film_pm(const SceneView sv, Wo
 
 // stand-alone traversal for parity tests / counters: rays as packed {o[3], d[3], tMax}
 // onlyMarked: the re-trace pass after k_trace_closest_fast — only the records it marked as near-ties (nodes_visited == -1)
-#ifndef WF_DBG_RETRACED
-#define WF_DBG_RETRACED 0
-#endif
 __global__ void __launch_bounds__(BLOCK) k_trace_closest(const SceneView sv, int n, const float *rays, wf_hit_record *out, int *stackSpill, int onlyMarked) {
     const int gtid = blockIdx.x * BLOCK + threadIdx.x, stride = gridDim.x * BLOCK;
     LdsStack st{stackSpill + gtid, stride, 0};
@@ -1674,7 +1383,7 @@ __global__ void __launch_bounds__(BLOCK) k_trace_closest(const SceneView sv, int
         wf_hit_record h;
         h.prim = found ? ch.prim : -1;
         h.t = found ? ch.h.t : 0; h.b0 = found ? ch.h.b0 : 0; h.b1 = found ? ch.h.b1 : 0; h.b2 = found ? ch.h.b2 : 0;
-        h.nodes_visited = onlyMarked ? WF_DBG_RETRACED : ch.nodesVisited; h.tris_tested = onlyMarked ? 0 : ch.trisTested; h.instance = found ? ch.inst : -1;
+        h.nodes_visited = onlyMarked ? 0 : ch.nodesVisited; h.tris_tested = onlyMarked ? 0 : ch.trisTested; h.instance = found ? ch.inst : -1;
         out[i] = h;
     }
 }
@@ -1814,7 +1523,7 @@ __global__ void k_pack_grid_corners(const float *v, int nx, int ny, int nz, floa
     for (size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x; c < cells; c += (size_t)gridDim.x * blockDim.x) {
         const int cx = (int)(c % (size_t)(nx + 1)), cy = (int)((c / (size_t)(nx + 1)) % (size_t)(ny + 1)), cz = (int)(c / ((size_t)(nx + 1) * (ny + 1)));
         const int ix = cx - 1, iy = cy - 1, iz = cz - 1;
-        float *o = out + 8 * wf::GridCornerIndex(nx, ny, cx, cy, cz);   // (bricked: wf_media.h)
+        float *o = out + 8 * wf::GridCornerIndex(nx, ny, cx, cy, cz);
         o[0] = wf::GridLookupI(v, nx, ny, nz, ix, iy, iz);         o[1] = wf::GridLookupI(v, nx, ny, nz, ix + 1, iy, iz);
         o[2] = wf::GridLookupI(v, nx, ny, nz, ix, iy + 1, iz);     o[3] = wf::GridLookupI(v, nx, ny, nz, ix + 1, iy + 1, iz);
         o[4] = wf::GridLookupI(v, nx, ny, nz, ix, iy, iz + 1);     o[5] = wf::GridLookupI(v, nx, ny, nz, ix + 1, iy, iz + 1);
@@ -2145,23 +1854,19 @@ static bool BuildFastBVH(const wf_scene_desc *d, std::vector<QNode> *nodes, std:
             return (uint32_t)q;
         };
         auto leafRef = [&](int i) { return (int)~(((unsigned)subFirst[i] << 4) | (unsigned)(subCount[i] - 1)); };
-        auto packBox = [&](const wf_bvh_node &b, uint32_t q[6], int slot) {
-            for (int a = 0; a < 3; ++a) q[slot * 3 + a] = qlo(b.bmin[a], a) | (qhi(b.bmax[a], a) << 16);
-        };
         const int qBase = (int)nodes->size();
-#if WF_BVH4
         auto emptyBox = [&](uint32_t q[12], int slot) { for (int a = 0; a < 3; ++a) q[slot * 3 + a] = 0x0000ffffu; };
         auto area = [&](int i) {
             const wf_bvh_node &bx = BoxOf(i);
             double dx = (double)bx.bmax[0] - bx.bmin[0], dy = (double)bx.bmax[1] - bx.bmin[1], dz = (double)bx.bmax[2] - bx.bmin[2];
             return dx * dy + dy * dz + dz * dx;
         };
-        auto packBox4 = [&](const wf_bvh_node &b, uint32_t q[12], int slot) {
+        auto packBox = [&](const wf_bvh_node &b, uint32_t q[12], int slot) {
             for (int a = 0; a < 3; ++a) q[slot * 3 + a] = qlo(b.bmin[a], a) | (qhi(b.bmax[a], a) << 16);
         };
         if (leafLike(root)) {
             QNode qn{};
-            packBox4(BoxOf(root), qn.q, 0);
+            packBox(BoxOf(root), qn.q, 0);
             qn.child[0] = leafRef(root);
             for (int c = 1; c < 4; ++c) { emptyBox(qn.q, c); qn.child[c] = NODE_NONE; }
             nodes->push_back(qn);
@@ -2200,49 +1905,15 @@ static bool BuildFastBVH(const wf_scene_desc *d, std::vector<QNode> *nodes, std:
             for (int c = 0; c < 4; ++c) {
                 int k = kidsOf[h][c];
                 if (k < 0) { emptyBox(qn.q, c); qn.child[c] = NODE_NONE; continue; }
-                packBox4(BoxOf(k), qn.q, c);
+                packBox(BoxOf(k), qn.q, c);
                 qn.child[c] = !leafLike(k) ? bfsIndex[k] : leafRef(k);
             }
             (*nodes)[(size_t)qBase + h] = qn;
         }
-#else
-        if (leafLike(root)) {
-            // the whole tree is one leaf: a root node whose two children are both that leaf (testing it twice
-            // changes neither the closest hit nor occlusion)
-            QNode qn{};
-            packBox(L[root], qn.q, 0);
-            packBox(L[root], qn.q, 1);
-            qn.left = leafRef(root);
-            qn.right = leafRef(root);
-            nodes->push_back(qn);
-            return qBase;
-        }
-        lastTreeDepth = 64;   // (two-wide legacy layout: the reference's own bound, nodesToVisit[64])
-        // breadth-first numbering of the interior nodes
-        std::vector<int> order;
-        order.push_back(root);
-        bfsIndex[root] = qBase;
-        for (size_t h = 0; h < order.size(); ++h) {
-            int i = order[h];
-            for (int c : {i + 1, (int)L[i].offset})
-                if (!leafLike(c)) { bfsIndex[c] = qBase + (int)order.size(); order.push_back(c); }
-        }
-        nodes->resize((size_t)qBase + order.size());
-        for (size_t h = 0; h < order.size(); ++h) {
-            int i = order[h];
-            int l = i + 1, r = L[i].offset;
-            QNode qn{};
-            packBox(L[l], qn.q, 0);
-            packBox(L[r], qn.q, 1);
-            qn.left = !leafLike(l) ? bfsIndex[l] : leafRef(l);
-            qn.right = !leafLike(r) ? bfsIndex[r] : leafRef(r);
-            (*nodes)[(size_t)qBase + h] = qn;
-        }
-#endif
         return qBase;
     };
     // the definitions' trees first (the entries of the re-braided top-level tree name their nodes), then the top-level tree; afterwards
-    // the top-level tree is moved to the FRONT of the array: the walk starts at node 0 and caches nodes [0, TOP_NODES) in LDS
+    // the top-level tree is moved to the FRONT of the array: the walk starts at node 0
     for (int i = 0; i < nRef; ++i)
         if (leafLike(i)) {
             int ni = 0;
@@ -2260,7 +1931,7 @@ static bool BuildFastBVH(const wf_scene_desc *d, std::vector<QNode> *nodes, std:
     subs->clear();
     std::vector<wf_bvh_node> Lx;
     int topRoot = 0;
-    if (braid && WF_BVH4) {
+    if (braid) {
         // ---- partial re-braiding: the entries of every instance
         const int nTop = d->n_top_bvh_nodes;
         std::vector<char> defGeneral((size_t)d->n_instance_defs, 0);
@@ -2422,11 +2093,7 @@ static bool BuildFastBVH(const wf_scene_desc *d, std::vector<QNode> *nodes, std:
         std::vector<QNode> moved((size_t)nAll);
         for (int i = 0; i < nAll; ++i) {
             QNode qn = (*nodes)[(size_t)i];
-#if WF_BVH4
             for (int c = 0; c < 4; ++c) qn.child[c] = remap(qn.child[c]);
-#else
-            qn.left = remap(qn.left); qn.right = remap(qn.right);
-#endif
             moved[(size_t)remap(i)] = qn;
         }
         nodes->swap(moved);
@@ -2494,13 +2161,8 @@ struct CheckWalk {
             if (r < 0) { Leaf(r, inst, o, dir); continue; }
             ++nodesVisited;
             const QNode &qn = nodes[(size_t)r];
-#if WF_BVH4
             for (int c = 0; c < 4; ++c)
                 if (qn.child[c] != NODE_NONE && Slab(base, cell, qn.q + 3 * c, o, dir)) st.push_back(qn.child[c]);
-#else
-            if (Slab(base, cell, qn.q, o, dir)) st.push_back(qn.left);
-            if (Slab(base, cell, qn.q + 3, o, dir)) st.push_back(qn.right);
-#endif
         }
     }
     void Enter(int entry, const double oW[3], const double dW[3]) {
@@ -2552,13 +2214,8 @@ int wf_debug_fastbvh_check(const wf_scene_desc *d, int n_rays, uint64_t seed, in
     out[0] = (int64_t)qn.size(); out[1] = (int64_t)lt.size(); out[2] = (int64_t)fsubs.size(); out[3] = fdep.top;
     // structure: every child reference names a node / a leaf run / an entry inside the arrays
     for (size_t i = 0; i < qn.size(); ++i)
-#if WF_BVH4
         for (int c = 0; c < 4; ++c) {
             const int r = qn[i].child[c];
-#else
-        for (int c = 0; c < 2; ++c) {
-            const int r = c ? qn[i].right : qn[i].left;
-#endif
             if (r == NODE_NONE) continue;
             if (r >= 0) { if ((size_t)r >= qn.size()) return fail(-1, "wf_debug_fastbvh_check: node %zu child %d out of range", i, c); continue; }
             const unsigned u = ~(unsigned)r;
@@ -2620,7 +2277,7 @@ int wf_debug_fastbvh_check(const wf_scene_desc *d, int n_rays, uint64_t seed, in
 // The stream's scratch (private segment) grows whenever a kernel needs more per lane than any kernel before it; on about a third of the
 // pool's boxes every such growth costs the launch that triggers it 20-30 ms (round 4: the first frame of a process took 200 ms instead of
 // 112: "Handle escaped rays" 1264 B, "Handle emitters" 1424 B, conductor 1468 B, coated diffuse 1500 B per lane — four steps in launch
-// order).  One launch of a kernel whose private segment is at least the largest of the library's (k_eval_material<7, 2>: 3372 B) pays for
+// order).  One launch of a kernel whose private segment is at least the largest of the library's (round 4: the one-kernel material stage of type 7, 3372 B) pays for
 // the growth once, when the context is created.  WF_SCRATCH_PRIME=0 skips it.
 constexpr int SCRATCH_PRIME_WORDS = 896;   // 3584 B per lane
 __global__ void k_scratch_prime(int *out, int n) {
@@ -2814,7 +2471,7 @@ int wf_scene_upload(wf_ctx *ctx, const wf_scene_desc *d) {
             for (int m = 0; m < d->n_media; ++m) {
                 const wf_medium &M = d->media[m];
                 if (M.type != WF_MEDIUM_GRID || M.density_offset < 0 || M.nx < 1 || M.ny < 1 || M.nz < 1) continue;
-                const size_t cells = wf::GridCornerCells(M.nx, M.ny, M.nz);   // (whole 8 x 8 x 8 bricks)
+                const size_t cells = wf::GridCornerCells(M.nx, M.ny, M.nz);
                 if ((double)(total + 8 * cells) * sizeof(float) > budget) continue;
                 base[m] = (long long)total;
                 total += 8 * cells;
@@ -3013,13 +2670,10 @@ int wf_scene_upload(wf_ctx *ctx, const wf_scene_desc *d) {
             const int rows = std::max(std::max(needRef - std::min(STACK_LDS, TSTACK), needFast - TSTACK), STACK_MAX - std::min(STACK_LDS, TSTACK));
             if (rows > 2048) return fail(-1, "BVH too deep for the traversal stacks (depth %d + %d)", depthTop, depthDef);
             if ((e = devAlloc(ctx, &ctx->stackSpill, (size_t)rows * MAX_GRID * BLOCK))) return e;
-            if ((e = devAlloc(ctx, &ctx->walkSave, (size_t)4 * MAX_GRID * BLOCK))) return e;
             ctx->spillRows = rows;
             if ((e = devAlloc(ctx, &ctx->dbgWords, (size_t)8 + 32))) return e;   // [8..39]: -DWF_WALK_STATS builds: sixteen 64-bit phase counters (WalkStats)   // [4..7]: near-tie queue diagnostics (pushes, re-walks without a hit, -, -)
             HIPCHK(hipMemset(ctx->dbgWords, 0, (8 + 32) * sizeof(int)));
         }
-        if (d->n_bvh_nodes > 0)
-            for (int a = 0; a < 3; ++a) { ctx->sceneMin[a] = d->bvh_nodes[0].bmin[a]; ctx->sceneMax[a] = d->bvh_nodes[0].bmax[a]; }
         if (ctx->fastOk) {
             if ((e = devUpload(ctx, &ctx->fast.nodes, qn.data(), qn.size()))) return e;
             if ((e = devUpload(ctx, &ctx->fast.tris, lt.data(), lt.size()))) return e;
@@ -3078,11 +2732,6 @@ int wf_scene_upload(wf_ctx *ctx, const wf_scene_desc *d) {
                 (e = residentGrid(g1 ? (const void *)k_shadow_fast<9, true> : (const void *)k_shadow_fast<8, true>, &ctx->persistentGridShadow))) return e;
         }
         if ((e = devAlloc(ctx, &ctx->probeCursor, (size_t)1))) return e;
-        {
-            int perCU = 0;
-            HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, (const void *)k_medium_sample<false>, BLOCK, 0));
-            ctx->mediumGrid = std::min(MAX_GRID, std::max(1, perCU) * prop.multiProcessorCount);
-        }
     }
     if ((e = devAlloc(ctx, &ctx->ws.film, (size_t)ctx->W * ctx->H * 4))) return e;
     ctx->ws.filmSpectral = nullptr;
@@ -3197,14 +2846,8 @@ int wf_queues_alloc(wf_ctx *ctx, int pixels_per_pass, int samples_per_pass) {
     if ((e = devAlloc(ctx, &ws.sq.o, n)) || (e = devAlloc(ctx, &ws.sq.d, n)) || (e = devAlloc(ctx, &ws.sq.Ld, n)) ||
         (e = devAlloc(ctx, &ws.sq.r_u, n)) || (e = devAlloc(ctx, &ws.sq.r_l, n)))
         return e;
-#if defined(WF_HAVE_FUSED_MAT)
-#if defined(WF_MAT_SPLIT_DEFAULT)
-    ctx->matSplit = WF_MAT_SPLIT_DEFAULT != 0;
-#endif
-    if (const char *sp = getenv("WF_MAT_SPLIT")) ctx->matSplit = atoi(sp) != 0;
-#endif
     if (ctx->svHost.haveAnimated && (e = devAlloc(ctx, &ws.pathTime, n))) return e;   // the paths' times, for the shadow rays (AnimatedPrimitive)
-    if (ctx->matSplit) {
+    {
         // the NeeItems between the material stage's two kernels: as many 16-byte planes as the widest record of the material types present
         int planes = 0;
         for (int m = 1; m < WF_MAT_NTYPES; ++m) if (ctx->matPresent[m]) planes = std::max(planes, NeePlanes(m));
@@ -3215,34 +2858,6 @@ int wf_queues_alloc(wf_ctx *ctx, int pixels_per_pass, int samples_per_pass) {
     ctx->splitRoute = getenv("WF_SPLIT_ROUTE") ? std::max(1, atoi(getenv("WF_SPLIT_ROUTE"))) : 2;
     if (getenv("WF_CURSOR_CHUNK")) ctx->cursorChunk = ctx->cursorChunkShadow = std::max(1, atoi(getenv("WF_CURSOR_CHUNK")));  // (default: chosen at scene upload)
     if (ctx->splitRoute && (e = devAlloc(ctx, &ws.routeCode, n))) return e;
-    ctx->raySort = getenv("WF_RAY_SORT") ? atoi(getenv("WF_RAY_SORT")) : 0;
-    if (!ctx->fastOk) ctx->raySort = 0;
-    if (ctx->raySort) {
-        if (getenv("WF_SORT_MIN")) ctx->sortMin = atoi(getenv("WF_SORT_MIN"));
-        if (getenv("WF_SORT_OBITS")) ctx->sortOriginBits = std::min(std::max(atoi(getenv("WF_SORT_OBITS")), 1), 10);
-        if (getenv("WF_SORT_DBITS")) ctx->sortDirBits = std::min(std::max(atoi(getenv("WF_SORT_DBITS")), 0), (32 - 3 * ctx->sortOriginBits) / 2);
-        for (int k = 0; k < 2; ++k)
-            if ((e = devAlloc(ctx, &ctx->sortKeys[k], n)) || (e = devAlloc(ctx, &ctx->sortVals[k], n))) return e;
-        size_t bytes = 0;
-        if (wf_sort_pairs_u32(ctx->stream, nullptr, &bytes, ctx->sortKeys[0], ctx->sortKeys[1], ctx->sortVals[0], ctx->sortVals[1], (unsigned)n, 32u) != 0)
-            return fail(-1, "ray sort: scratch size query failed");
-        unsigned char *tmp = nullptr;
-        if ((e = devAlloc(ctx, &tmp, bytes))) return e;
-        ctx->sortTemp = tmp; ctx->sortTempBytes = bytes;
-        if ((ctx->raySort & 1) && (e = allocRayQueue(ctx, &ctx->rqTmp, n))) return e;
-        if (ctx->raySort & 2) {
-            if ((e = devAlloc(ctx, &ctx->sqTmp.o, n)) || (e = devAlloc(ctx, &ctx->sqTmp.d, n)) || (e = devAlloc(ctx, &ctx->sqTmp.Ld, n)) ||
-                (e = devAlloc(ctx, &ctx->sqTmp.r_u, n)) || (e = devAlloc(ctx, &ctx->sqTmp.r_l, n)))
-                return e;
-            if (ctx->svHost.haveMedia && (e = devAlloc(ctx, &ctx->sqTmp.medium, n))) return e;
-        }
-        const float cells = (float)(1 << ctx->sortOriginBits);
-        for (int a = 0; a < 3; ++a) {
-            float ext = ctx->sceneMax[a] - ctx->sceneMin[a];
-            ctx->sortBase[a] = ctx->sceneMin[a];
-            ctx->sortScale[a] = ext > 0 ? cells / ext : 0.f;
-        }
-    }
     ctx->maxQueueSize = max_queue_size;
     ctx->queuesAllocated = true;
     return 0;
@@ -3297,7 +2912,6 @@ int wf_reset_stage_queues(wf_ctx *ctx, int depth) {
     // stats->indirectRays[depth] += queue size (integrator.cpp:411-414)
     LAUNCH("Reset queues before tracing rays", k_reset, 1, ctx->ws, mask, 1 + statDepth(depth), CNT_RAY0 + cur);
     ctx->cursorDirty[0] = false;
-    ctx->cursorDirty[2] = false;
     return 0;
 }
 int wf_gen_camera_rays(wf_ctx *ctx, int y0, int sample_index) {
@@ -3323,34 +2937,6 @@ int wf_gen_ray_samples(wf_ctx *ctx, int depth, int sample_index) {
            tops ? depth : -1);
     return 0;
 }
-// ray-coherence pass: sort + physically permute the ray queue `cur` (shadow = false) or the shadow queue (see k_ray_sort_keys)
-static int SortQueue(wf_ctx *ctx, bool shadow, int cur) {
-    WorkState &ws = ctx->ws;
-    int n = 0;
-    HIPCHK(hipMemcpyAsync(&n, &ws.counters[(shadow ? CNT_SHADOW : CNT_RAY0 + cur) * CNT_STRIDE], sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (n < ctx->sortMin) return 0;  // (a launch this small is latency, not throughput)
-    SortGrid g;
-    for (int a = 0; a < 3; ++a) { g.base[a] = ctx->sortBase[a]; g.scale[a] = ctx->sortScale[a]; }
-    g.obits = ctx->sortOriginBits; g.dbits = ctx->sortDirBits;
-    const F4 *o = shadow ? ws.sq.o : ws.rq[cur].o, *d = shadow ? ws.sq.d : ws.rq[cur].d;
-    {
-        Prof prof_(ctx, shadow ? "Sort shadow rays" : "Sort rays");
-        hipLaunchKernelGGL(k_ray_sort_keys, dim3(gridFor(n)), dim3(BLOCK), 0, ctx->stream, o, d, n, g, ctx->sortKeys[0], ctx->sortVals[0]);
-        size_t bytes = ctx->sortTempBytes;
-        if (wf_sort_pairs_u32(ctx->stream, ctx->sortTemp, &bytes, ctx->sortKeys[0], ctx->sortKeys[1], ctx->sortVals[0], ctx->sortVals[1], (unsigned)n,
-                              (unsigned)(3 * g.obits + 2 * g.dbits)) != 0)
-            return fail(-1, "ray sort failed");
-        if (shadow) {
-            hipLaunchKernelGGL(k_permute_shadow, dim3(gridFor(n)), dim3(BLOCK), 0, ctx->stream, ws.sq, ctx->sqTmp, ctx->sortVals[1], n);
-            std::swap(ws.sq, ctx->sqTmp);
-        } else {
-            hipLaunchKernelGGL(k_permute_rays, dim3(gridFor(n)), dim3(BLOCK), 0, ctx->stream, ws.rq[cur], ctx->rqTmp, ctx->sortVals[1], n);
-            std::swap(ws.rq[cur], ctx->rqTmp);
-        }
-    }
-    return 0;
-}
 static int JoinRetrace(wf_ctx *ctx) {
     if (!ctx->retracePending) return 0;
     HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->evJoin, 0));
@@ -3365,8 +2951,6 @@ int wf_intersect_closest(wf_ctx *ctx, int depth) {
         { if (ctx->svHost.haveAnimated) LAUNCH("Intersect closest", (k_intersect_closest<true, true>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1, ctx->stackSpill);
           else LAUNCH("Intersect closest", k_intersect_closest<true>, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1, ctx->stackSpill); }
     else if (ctx->fastOk) {
-        if ((ctx->raySort & 1) && depth >= 1)
-            if (int e = SortQueue(ctx, false, depth & 1)) return e;
         if (ctx->splitRoute) {
             int *cursor = nullptr;
             if (ctx->splitRoute > 1) {
@@ -3423,15 +3007,8 @@ int wf_intersect_closest(wf_ctx *ctx, int depth) {
 int wf_medium_sample(wf_ctx *ctx, int depth) {
     if (int e = checkReady(ctx)) return e;
     if (!ctx->svHost.haveMedia) return 0;
-    {
-        // persistent launch with wave-level refill: one resident grid, the items dealt from a work cursor (zeroed by the stage's reset launch)
-        int *cursor = ctx->ws.counters + CNT_CURSOR_MEDIUM * CNT_STRIDE;
-        if (ctx->cursorDirty[2]) HIPCHK(hipMemsetAsync(cursor, 0, sizeof(int), ctx->stream));
-        ctx->cursorDirty[2] = true;
-        const int grid = WF_MEDIUM_REFILL ? std::min(ctx->mediumGrid, gridFor(ctx->maxQueueSize)) : gridFor(ctx->maxQueueSize);
-        if (ctx->mediumLean) LAUNCH("Sample medium interaction", k_medium_sample<true>, grid, ctx->svHost, ctx->ws, depth & 1, cursor);
-        else LAUNCH("Sample medium interaction", k_medium_sample<false>, grid, ctx->svHost, ctx->ws, depth & 1, cursor);
-    }
+    if (ctx->mediumLean) LAUNCH("Sample medium interaction", k_medium_sample<true>, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
+    else LAUNCH("Sample medium interaction", k_medium_sample<false>, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
     LAUNCH("Sample medium interaction: route surface hits", k_medium_route, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
     if (depth == ctx->maxDepth) return 0;
     if (ctx->rareLights) LAUNCH("Sample direct/indirect - Henyey-Greenstein", k_medium_scatter<true>, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
@@ -3500,7 +3077,7 @@ int wf_eval_material(wf_ctx *ctx, int material_type, int depth) {
 static int EvalMaterials(wf_ctx *ctx, int depth) {
     int present = 0;
     for (int m = 1; m < WF_MAT_NTYPES; ++m) present += ctx->matPresent[m] ? 1 : 0;
-    const bool parallel = ctx->matStreams && present > 1 && ctx->profile != 1 && !ctx->traceLaunch && ctx->matSplit;
+    const bool parallel = ctx->matStreams && present > 1 && ctx->profile != 1 && !ctx->traceLaunch;
     if (!parallel) {
         for (int m = 1; m < WF_MAT_NTYPES; ++m)
             if (ctx->matPresent[m])
@@ -3534,25 +3111,6 @@ static int EvalMaterialOn(wf_ctx *ctx, int material_type, int depth, hipStream_t
     const bool tex = ctx->svHost.texNeedsFootprint != 0;
     const bool vs = ctx->svHost.film.type == WF_FILM_GBUFFER || ctx->svHost.camera.anim.actually_animated || ctx->svHost.haveAnimated ||
                     (ctx->svHost.haveCurves && ctx->svHost.haveQuadricAlpha);   // the variant that fills the visible surface / differentiates a moving camera / meets animated instances or alpha-textured curves
-#if defined(WF_HAVE_FUSED_MAT)
-    if (!ctx->matSplit) {
-        Prof prof_(ctx, timed ? names[material_type] : "(untimed)", stream);
-        const bool rare = ctx->rareLights || vs;   // a portal infinite light, or a GBufferFilm: the variant that can reach the portal samplers / fills the visible surface
-        switch (material_type) {
-        case 1: (rare ? wf_launch_eval_material_1_2 : tex ? wf_launch_eval_material_1_1 : wf_launch_eval_material_1_0)(stream, g, &ctx->svHost, &ctx->ws, cur); break;
-        case 2: (rare ? wf_launch_eval_material_2_2 : tex ? wf_launch_eval_material_2_1 : wf_launch_eval_material_2_0)(stream, g, &ctx->svHost, &ctx->ws, cur); break;
-        case 3: (rare ? wf_launch_eval_material_3_2 : tex ? wf_launch_eval_material_3_1 : wf_launch_eval_material_3_0)(stream, g, &ctx->svHost, &ctx->ws, cur); break;
-        case 4: (rare ? wf_launch_eval_material_4_2 : tex ? wf_launch_eval_material_4_1 : wf_launch_eval_material_4_0)(stream, g, &ctx->svHost, &ctx->ws, cur); break;
-        case 5: (rare ? wf_launch_eval_material_5_2 : tex ? wf_launch_eval_material_5_1 : wf_launch_eval_material_5_0)(stream, g, &ctx->svHost, &ctx->ws, cur); break;
-        case 6: (rare ? wf_launch_eval_material_6_2 : tex ? wf_launch_eval_material_6_1 : wf_launch_eval_material_6_0)(stream, g, &ctx->svHost, &ctx->ws, cur); break;
-        case 7: (rare ? wf_launch_eval_material_7_2 : tex ? wf_launch_eval_material_7_1 : wf_launch_eval_material_7_0)(stream, g, &ctx->svHost, &ctx->ws, cur); break;
-        case 8: (rare ? wf_launch_eval_material_8_2 : tex ? wf_launch_eval_material_8_1 : wf_launch_eval_material_8_0)(stream, g, &ctx->svHost, &ctx->ws, cur); break;
-        case 9: (rare ? wf_launch_eval_material_9_2 : tex ? wf_launch_eval_material_9_1 : wf_launch_eval_material_9_0)(stream, g, &ctx->svHost, &ctx->ws, cur); break;
-        case 10: (rare ? wf_launch_eval_material_10_2 : tex ? wf_launch_eval_material_10_1 : wf_launch_eval_material_10_0)(stream, g, &ctx->svHost, &ctx->ws, cur); break;
-        }
-        return 0;
-    }
-#endif
     // the two halves (wf_kernels.h MatShade / MatNee; the items' NeeItems stay in ws.neeRec between them)
     {
         Prof prof_(ctx, timed ? names[material_type] : "(untimed)", stream);
@@ -3599,8 +3157,6 @@ int wf_intersect_shadow(wf_ctx *ctx, int depth) {
         { if (ctx->svHost.haveAnimated) LAUNCH("Intersect shadow", (k_intersect_shadow<true, true>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, ctx->stackSpill);
           else LAUNCH("Intersect shadow", k_intersect_shadow<true>, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, ctx->stackSpill); }
     else if (ctx->fastOk) {
-        if ((ctx->raySort & 2) && (depth >= 1 || (ctx->raySort & 4)))
-            if (int e = SortQueue(ctx, true, 0)) return e;
         int *cursor = nullptr;
         if (ctx->splitRoute > 1) {
             cursor = ctx->ws.counters + CNT_CURSOR_SHADOW * CNT_STRIDE;   // (zeroed by the "Reset shadowRayQueue" launch that follows every any-hit launch)

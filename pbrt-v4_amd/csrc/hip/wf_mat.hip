@@ -1,16 +1,15 @@
 // wf_mat.hip — one translation unit per material type, stage half and variant (compiled with
-// -DWF_MAT_INSTANCE=<wf_material_type> -DWF_MAT_PART=<0|1|2> -DWF_MAT_TEXCTX=<variant>):
+// -DWF_MAT_INSTANCE=<wf_material_type> -DWF_MAT_PART=<1|2> -DWF_MAT_TEXCTX=<variant>):
 // the K9 kernels "<Material> + BxDF eval" (EvaluateMaterialAndBSDF<M, BasicTextureEvaluator>, wavefront/surfscatter.cpp:57-328) and
 // their launchers.  Split from wf_backend.hip so that the material kernels compile in parallel (the layered ones take minutes).
 //   WF_MAT_PART 1  k_mat_shade<M, V>   interaction + textures + BxDF + BSDF sample + indirect-ray push; leaves the item's NeeItem
 //                                      (wf_kernels.h) in HBM                                  V = 0 | 1 | 2 (texture context / GBuffer)
 //   WF_MAT_PART 2  k_mat_nee<M, R>     next-event estimation from the NeeItem                 R = 0 | 1 (rare light types reachable)
-//   WF_MAT_PART 0  k_eval_material<M, V>  both halves in one kernel (round 1-4; WF_MAT_SPLIT=0 selects it at run time for A/B runs;
-//                                      built only with `make MATFUSED=1`)
+// (Rounds 1-4 ran both halves in one kernel per type; measured and dropped, profiles/r05_material_split_ab_sm16.txt.)
 #include <hip/hip_runtime.h>
 
 #if !defined(WF_MAT_INSTANCE) || !defined(WF_MAT_TEXCTX) || !defined(WF_MAT_PART)
-#error "compile with -DWF_MAT_INSTANCE=<wf_material_type> -DWF_MAT_PART=<0|1|2> -DWF_MAT_TEXCTX=<variant>"
+#error "compile with -DWF_MAT_INSTANCE=<wf_material_type> -DWF_MAT_PART=<1|2> -DWF_MAT_TEXCTX=<variant>"
 #endif
 // the LEAN shade variants (0, 1): device code without the quadric / patch / curve interaction callees and without the texture-graph
 // evaluator (wf_scene.h "LEAN DEVICE VARIANTS") — must be defined before the common headers are read
@@ -24,14 +23,11 @@ using namespace wf;
 
 constexpr int MBLOCK = 256;
 
-// minimum waves per SIMD (the register budget: 2 -> 256 VGPRs, 3 -> 168, 4 -> 128).  The fused kernel, measured per material on the spec
+// minimum waves per SIMD (the register budget: 2 -> 256 VGPRs, 3 -> 168, 4 -> 128).  The one-kernel stage of rounds 1-4, measured per material on the spec
 // scene, 2 vs 3 waves: diffuse 24.1 -> 22.7 ms per 16 spp, conductor 6.27 -> 6.40, coated diffuse 17.4 -> 20.2 (its stochastic walks spill).
 // Rounds 3-4 ran the diffuse kernel at 3 waves for those 6 %; round 4 took it back: at 168 VGPRs the unit spills ~170 VGPRs beside ~300 SGPRs
 // that the compiler spills THROUGH VGPR lanes, and that build was the common factor of three wrong-code incidents that no source change
 // explains; tools/check_spill_carriers.py (CPU suite) fails any build in which a kernel spills such a carrier register.
-#ifndef WF_MAT_WAVES
-#define WF_MAT_WAVES 2
-#endif
 #ifndef WF_SHADE_WAVES
 #define WF_SHADE_WAVES 2
 #endif
@@ -151,23 +147,7 @@ struct NeeIO {
 #define WF_CAT4_(a, b, c, d) a##b##c##d
 #define WF_CAT4(a, b, c, d) WF_CAT4_(a, b, c, d)
 
-#if WF_MAT_PART == 0
-template <int MAT, int TEXCTX>
-__global__ void __launch_bounds__(MBLOCK, WF_MAT_WAVES) k_eval_material(const SceneView *__restrict__ svp, WorkState ws, int cur) {
-    const SceneView &sv = *svp;
-    const int n = ws.counters[(CNT_MAT0 + MAT) * CNT_STRIDE];
-    // block-uniform trip count: BlockAlloc inside the body synchronises the workgroup
-    for (int base = blockIdx.x * MBLOCK; base < n; base += gridDim.x * MBLOCK) {
-        const int i = base + threadIdx.x;
-        KEvalMaterial<MAT, TEXCTX>(sv, ws, cur, i, i < n);
-    }
-}
-// WF_MAT_TEXCTX = 1: some texture depends on the footprint, or some material has a displacement texture / normal map;
-// 2: the same plus the rarely used light types (KEvalMaterial)
-extern "C" void WF_CAT4(wf_launch_eval_material_, WF_MAT_INSTANCE, _, WF_MAT_TEXCTX)(hipStream_t stream, int grid, const SceneView *sv, const WorkState *ws, int cur) {
-    hipLaunchKernelGGL((k_eval_material<WF_MAT_INSTANCE, WF_MAT_TEXCTX>), dim3(grid), dim3(MBLOCK), 0, stream, sv->self, *ws, cur);
-}
-#elif WF_MAT_PART == 1
+#if WF_MAT_PART == 1
 // VARIANT (WF_MAT_TEXCTX): 0 lean, no texture needs the footprint and nothing is displaced; 1 lean, with the footprint / bump block;
 // 2 general (quadrics, patches, curves, texture graphs); 3 = 2 + the GBufferFilm's visible surface and the moving camera's differentials
 template <int MAT, int VARIANT>

@@ -1,17 +1,12 @@
-// wf_sort.hip — the key/value radix sort behind the ray-coherence pass (wf_backend.hip: SortRayQueue).  rocPRIM's device-wide
-// radix sort is the library primitive; the keys, the permutation of the queues and everything on the tracing path are ours.
-// Its own translation unit: the rocPRIM headers cost ~20 s of compile time.
+// wf_sort.hip — the HLBVH build's Morton-code sort on the device.  rocPRIM's device-wide radix sort is the library primitive; the
+// keys are ours.  Its own translation unit: the rocPRIM headers cost ~20 s of compile time.
+// (The ray-coherence sort that also used it — rays sorted by origin cell and direction before tracing — was measured and dropped:
+// docs/DESIGN_HISTORY.md.)
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include <cstdint>
-
-// temp == nullptr: *tempBytes receives the scratch size needed for n pairs.  Sorts by the low `endBit` bits of the keys.
-extern "C" int wf_sort_pairs_u32(hipStream_t stream, void *temp, size_t *tempBytes, const uint32_t *keysIn, uint32_t *keysOut, const uint32_t *valsIn, uint32_t *valsOut,
-                                 unsigned n, unsigned endBit) {
-    return (int)rocprim::radix_sort_pairs(temp, *tempBytes, keysIn, keysOut, valsIn, valsOut, n, 0u, endBit, stream);
-}
 
 // ---- HLBVH build, device part (cpu/aggregates.cpp:394-411): Morton codes of the primitive centroids + stable radix sort ------
 // codes[i] / order[i]: code and input position of the i-th primitive in Morton order — what the host builder's treelet emission
