@@ -718,8 +718,9 @@ int wf_trace_any_host(wf_ctx *ctx, int n, const float *o, const float *d, const 
                       int32_t *occluded, int32_t *nodes_visited, int32_t *tris_tested);
 /* ... with the rays' TIMES (round 6): the reference's WavefrontAggregate reads ray.time (integrator.h:32-54) and an AnimatedPrimitive
    (cpu/primitive.cpp:132-158) is intersected with its transformation interpolated at that time.  On a scene with animated primitives
-   the untimed calls above and below (and wf_trace_shadow_tr_host / wf_trace_one_random_host) return an error instead of answering
-   for the start-time geometry; these two walk in the reference's order (cpu/aggregates.cpp:529-579) at time[i].  Any scene. */
+   the untimed calls above and below (and wf_trace_shadow_tr_host / wf_trace_one_random_host, whose timed forms are
+   wf_trace_shadow_tr_host_t / wf_trace_one_random_host_t below) return an error instead of answering for the start-time geometry;
+   these two walk in the reference's order (cpu/aggregates.cpp:529-579) at time[i].  Any scene. */
 int wf_trace_closest_host_t(wf_ctx *ctx, int n, const float *o, const float *d, const float *tmax, const float *time, wf_hit_record *out);
 int wf_trace_any_host_t(wf_ctx *ctx, int n, const float *o, const float *d, const float *tmax, const float *time, int32_t *occluded);
 /* The same two calls on caller-owned DEVICE buffers (what a GPU-resident host integrator binds: its RayQueue / ShadowRayQueue stay on
@@ -739,10 +740,21 @@ int wf_device_download(wf_ctx *ctx, void *dst_host, const void *src_device, uint
    RecordShadowRayResult's caller adds to the pixel (zero when the ray is blocked or the transmittance roulette ends it). */
 int wf_trace_shadow_tr_host(wf_ctx *ctx, int n, const float *o, const float *d, const float *tmax, const int32_t *medium, const float *lambda,
                             const float *Ld, const float *r_u, const float *r_l, float *out_L);
+/* ... with the rays' TIMES (time[i], one per ray): on a scene with animated primitives the transmittance walk interpolates their
+   transformations at that time, as the render does for a shadow ray spawned on a path of that time (the reference-order walk).  Any
+   scene with media; the untimed call refuses a scene with animated primitives. */
+int wf_trace_shadow_tr_host_t(wf_ctx *ctx, int n, const float *o, const float *d, const float *tmax, const int32_t *medium, const float *lambda,
+                              const float *Ld, const float *r_u, const float *r_l, const float *time, float *out_L);
 /* WavefrontAggregate::IntersectOneRandom (integrator.h:51-52) on caller-supplied probe segments p0 -> p1 (3 floats each): out[i] =
    the hit of a surface whose material id is material[i], chosen by the reference's weighted reservoir sampling (seed Hash(p0, p1))
    among all such hits along the segment, reservoir_pdf[i] its sample probability (0 and prim = -1: none) */
 int wf_trace_one_random_host(wf_ctx *ctx, int n, const float *p0, const float *p1, const int32_t *material, wf_hit_record *out, float *reservoir_pdf);
+/* ... with a TIME per segment (time[i]): the segment is walked with the animated primitives' transformations interpolated at that time.
+   The render's own probe segments are walked at time 0 (the reference spawns them from an Interaction of time 0,
+   wavefront/aggregate.cpp:96): a caller that restates the render passes 0.  Any scene; the untimed call refuses a scene with animated
+   primitives. */
+int wf_trace_one_random_host_t(wf_ctx *ctx, int n, const float *p0, const float *p1, const int32_t *material, const float *time, wf_hit_record *out,
+                               float *reservoir_pdf);
 /* Device part of the HLBVH build (cpu/aggregates.cpp:394-411): Morton codes (10 bits per axis of each centroid's
    offset inside `bounds` = min.xyz max.xyz) and their stable radix sort.  codes[i] / order[i] = code and input position of the i-th
    primitive in Morton order; the host builder emits the treelets and the SAH upper tree from them.  Needs no context; non-zero

@@ -390,15 +390,26 @@ WF_HD int SurfaceMedium(const wf_mesh &mesh, N3 n, V3 w, int rayMedium) {
     if (mesh.medium_inside != mesh.medium_outside) return Dot(w, n) > 0 ? mesh.medium_outside : mesh.medium_inside;
     return rayMedium;
 }
+// ANIM (the consumers of a hit before the material stage: interface skip, MixMaterial resolve): the scene has animated primitives — the
+// hit's interaction is rebuilt at the ray's time (o.w), as the reference's SurfaceInteraction comes from the intersection at that time.
+// The HIP kernels ask for it in their ANIM variants only (launched for scenes with animated primitives: the interpolation is an
+// out-of-line callee whose registers the static scenes' kernels must not pay for); the CPU build takes it always — InstanceAt<true>
+// returns a static instance as it is, so a static scene's result is the same.
+#if defined(__HIPCC__)
+#define WF_ANIM_BY_DEFAULT false
+#else
+#define WF_ANIM_BY_DEFAULT true
+#endif
 // The MixMaterial resolve loop of EnqueueWorkAfterIntersection (intersect.h:92-97) + MixMaterial::ChooseMaterial
 // (materials.h:284-294).  The reference hashes (p, wo, the two Material tagged POINTERS): its choice depends on heap
 // addresses and differs from run to run, so this is the one place where parity with it is statistical by construction;
 // here the two material ids take the pointers' place.
 WF_HD int HitInst(const SceneView &sv, const WorkState &ws, int i) { return sv.nInstances > 0 ? ws.hitInst[i] : -1; }
-WF_HD int ResolveMix(const SceneView &sv, int matId, int prim, int inst, float b0, float b1, float b2, V3 wo, V3 ro) {
+template <bool ANIM = WF_ANIM_BY_DEFAULT>
+WF_HD int ResolveMix(const SceneView &sv, int matId, int prim, int inst, float b0, float b1, float b2, V3 wo, V3 ro, float time) {
     if (sv.materials[matId].type != WF_MAT_MIX) return matId;
     SurfIntr si;
-    HitInteraction(sv, prim, inst, b0, b1, b2, &si, ro, -wo);
+    HitInteraction<!WF_DEV_LEAN, false, ANIM>(sv, prim, inst, b0, b1, b2, &si, ro, -wo, time);
     TexCtx tc;
     tc.p = si.pi.mid(); tc.n = si.n; tc.uv = si.uv;
     while (sv.materials[matId].type == WF_MAT_MIX) {
@@ -422,7 +433,9 @@ WF_HD int ResolveMix(const SceneView &sv, int matId, int prim, int inst, float b
 // fromMedium: the caller is the medium stage (SampleMediumInteraction's copy of this routing, media.cpp:176-201).  There the reference
 // continues a ray through an interface surface from `Interaction intr(w.pi, w.n)` — an interaction whose time is the member's default, 0 —
 // while EnqueueWorkAfterIntersection (intersect.h:99-106) spawns it from the full SurfaceInteraction, which carries the ray's time.  The
-// time of a ray only matters to AnimatedPrimitives (and to the shadow rays' path time): fuzz finding s1800074, round 5.
+// time of a ray only matters to AnimatedPrimitives (and to the shadow rays' path time): fuzz finding s1800074, round 5.  The interface
+// surface's own interaction is the intersection's, at the ray's time, in both cases.
+template <bool ANIM = WF_ANIM_BY_DEFAULT>
 WF_HD void RouteSurfaceHit(const SceneView &sv, const WorkState &ws, int cur, int i, int prim, int inst, float b0, float b1, float b2, bool fromMedium = false) {
     const wf_mesh mesh = sv.meshes[sv.triMesh[prim]];
     if (mesh.material < 0) {
@@ -432,7 +445,7 @@ WF_HD void RouteSurfaceHit(const SceneView &sv, const WorkState &ws, int cur, in
         SurfIntr si;
         F4 o = q.o[i], d = q.d[i];
         V3 rd{d.x, d.y, d.z};
-        HitInteraction(sv, prim, inst, b0, b1, b2, &si, V3{o.x, o.y, o.z}, rd);
+        HitInteraction<!WF_DEV_LEAN, false, ANIM>(sv, prim, inst, b0, b1, b2, &si, V3{o.x, o.y, o.z}, rd, o.w);
         V3 no = OffsetRayOrigin(si.pi, si.n, rd);
         int slot = QueueAlloc(&ws.counters[(CNT_RAY0 + (cur ^ 1)) * CNT_STRIDE]);
         nq.o[slot] = F4{no.x, no.y, no.z, fromMedium ? 0.f : o.w};
@@ -455,7 +468,7 @@ WF_HD void RouteSurfaceHit(const SceneView &sv, const WorkState &ws, int cur, in
     int matId = mesh.material;
     if (sv.haveMix && sv.materials[matId].type == WF_MAT_MIX) {
         F4 d = ws.rq[cur].d[i], o = ws.rq[cur].o[i];
-        matId = ResolveMix(sv, matId, prim, inst, b0, b1, b2, V3{-d.x, -d.y, -d.z}, V3{o.x, o.y, o.z});
+        matId = ResolveMix<ANIM>(sv, matId, prim, inst, b0, b1, b2, V3{-d.x, -d.y, -d.z}, V3{o.x, o.y, o.z}, o.w);
         ws.mixMat[i] = matId;
     }
     int mtype = sv.materials[matId].type;
@@ -470,6 +483,7 @@ WF_HD void RouteSurfaceHit(const SceneView &sv, const WorkState &ws, int cur, in
 // In sequential order the effect can be reproduced, which is how the diagnosis was checked: one stale depth per medium-sample slot.
 inline int32_t *g_msStaleDepth = nullptr;
 #endif
+template <bool ANIM = WF_ANIM_BY_DEFAULT>
 WF_HD void KAfterClosestHit(const SceneView &sv, const WorkState &ws, int cur, int i, bool found, int prim, int inst, float tHit, float b0, float b1, float b2) {
     if (sv.nInstances > 0) ws.hitInst[i] = found ? inst : -1;
     if (sv.haveMedia && ws.rq[cur].meta[i].w >= 0) {
@@ -494,16 +508,17 @@ WF_HD void KAfterClosestHit(const SceneView &sv, const WorkState &ws, int cur, i
         return;
     }
     ws.hit[i] = F4{BitsToFloat((uint32_t)prim), b0, b1, b2};
-    RouteSurfaceHit(sv, ws, cur, i, prim, inst, b0, b1, b2);
+    RouteSurfaceHit<ANIM>(sv, ws, cur, i, prim, inst, b0, b1, b2);
 }
 
 // the follow-up of the HIP traversal kernel for hits on a MixMaterial (ws.mixQ): resolve, then the material queue
+template <bool ANIM = WF_ANIM_BY_DEFAULT>
 WF_HD void KResolveMix(const SceneView &sv, const WorkState &ws, int cur, int qi) {
     const int i = ws.mixQ[qi];
     F4 h = ws.hit[i], d = ws.rq[cur].d[i], o = ws.rq[cur].o[i];
     int prim = (int)FloatToBits(h.x);
     const int inst = HitInst(sv, ws, i);
-    int matId = ResolveMix(sv, sv.meshes[sv.triMesh[prim]].material, prim, inst, h.y, h.z, h.w, V3{-d.x, -d.y, -d.z}, V3{o.x, o.y, o.z});
+    int matId = ResolveMix<ANIM>(sv, sv.meshes[sv.triMesh[prim]].material, prim, inst, h.y, h.z, h.w, V3{-d.x, -d.y, -d.z}, V3{o.x, o.y, o.z}, o.w);
     ws.mixMat[i] = matId;
     int slot = QueueAlloc(&ws.counters[(CNT_MAT0 + sv.materials[matId].type) * CNT_STRIDE]);
     ws.matQ[sv.materials[matId].type][slot] = i;
@@ -516,9 +531,11 @@ WF_HD void KResolveMix(const SceneView &sv, const WorkState &ws, int cur, int qi
 // 2 re-pushed ray (interface material), 2 + t material type t, MS medium sample (rays travelling in a medium).
 // GENERAL: the scene has non-triangle primitives (the plain traversal variant must not even link the quadric code:
 // an out-of-line callee's register count becomes the kernel's and costs it a wave of occupancy).
-template <bool GENERAL>
+// ANIM: the scene has animated primitives — an interface surface's interaction is rebuilt at the ray's time (always two-level: GENERAL).
+template <bool GENERAL, bool ANIM = false>
 __device__ inline void KRouteHitBlock(const SceneView &sv, const WorkState &ws, int cur, int i, bool valid, int prim, uint32_t route,
                                       float tHit, float b0, float b1, float b2, int inst = -1) {
+    static_assert(GENERAL || !ANIM, "an animated primitive is an instance: its hits take the general interaction");
     constexpr int MS = 2 + WF_MAT_NTYPES;
     constexpr int MIXQ = MS + 1;
     constexpr int NID = MIXQ + 1;
@@ -580,7 +597,7 @@ __device__ inline void KRouteHitBlock(const SceneView &sv, const WorkState &ws, 
             const RayQueueV &nq = ws.rq[cur ^ 1];
             SurfIntr si;
             F4 o = q.o[i], d = q.d[i];
-            if constexpr (GENERAL) HitInteraction(sv, prim, inst, b0, b1, b2, &si, V3{o.x, o.y, o.z}, V3{d.x, d.y, d.z});
+            if constexpr (GENERAL) HitInteraction<!WF_DEV_LEAN, false, ANIM>(sv, prim, inst, b0, b1, b2, &si, V3{o.x, o.y, o.z}, V3{d.x, d.y, d.z}, o.w);
             else TriangleInteraction(sv, prim, b0, b1, b2, &si);
             V3 no = OffsetRayOrigin(si.pi, si.n, V3{d.x, d.y, d.z});
             nq.o[slot] = F4{no.x, no.y, no.z, o.w};
@@ -789,10 +806,11 @@ WF_HD void KSampleMediumInteraction(const SceneView &sv, const WorkState &ws, in
     MediumTrackEnd(sv, ws, cur, s);
 }
 // the second half of K5 on the HIP back end: EnqueueWorkAfterIntersection for the medium-sample items that reached their surface
+template <bool ANIM = WF_ANIM_BY_DEFAULT>
 WF_HD void KMediumRoute(const SceneView &sv, const WorkState &ws, int cur, int qi) {
     const int i = ws.mediumRouteQ[qi];
     const F4 h = ws.hit[i];
-    RouteSurfaceHit(sv, ws, cur, i, (int)FloatToBits(h.x), HitInst(sv, ws, i), h.y, h.z, h.w, /* fromMedium */ true);
+    RouteSurfaceHit<ANIM>(sv, ws, cur, i, (int)FloatToBits(h.x), HitInst(sv, ws, i), h.y, h.z, h.w, /* fromMedium */ true);
 }
 
 // K6: SampleMediumScattering<HGPhaseFunction>, wavefront/media.cpp:259-352
@@ -1579,9 +1597,10 @@ WF_HD void KSubsurfaceProbe(const SceneView &sv, const WorkState &ws, int i) {
 }
 // WavefrontAggregate::IntersectOneRandom (CPUAggregate: wavefront/aggregate.cpp:90-115; OptiX: gpu/optix/optix.cu:474-573)
 // returns the reservoir's sample probability (0: the segment meets no surface of `material`) and the kept hit
-// ANIM: the scene has animated primitives; the probe rays are spawned from an Interaction of time 0 ("FIXME time", aggregate.cpp:96)
+// ANIM: the scene has animated primitives; the render's probe rays are spawned from an Interaction of time 0 ("FIXME time",
+// aggregate.cpp:96) — `time` is the boundary's (wf_trace_one_random_host_t: a caller's segment at a time of its own)
 template <bool ANIM = false, typename Stack>
-WF_HD float IntersectOneRandom(const SceneView &sv, V3 p0, V3 p1, int material, Stack &st, ClosestHit *kept, SurfIntr *keptSi) {
+WF_HD float IntersectOneRandom(const SceneView &sv, V3 p0, V3 p1, int material, Stack &st, ClosestHit *kept, SurfIntr *keptSi, float time = 0.f) {
     RNG rng;
     rng.SetSequence(Hash6f(p0, p1));   // WeightedReservoirSampler(seed) -> RNG(seed)
     float weightSum = 0, reservoirWeight = 0;
@@ -1592,11 +1611,11 @@ WF_HD float IntersectOneRandom(const SceneView &sv, V3 p0, V3 p1, int material, 
         if (r.d.x == 0 && r.d.y == 0 && r.d.z == 0) break;
         ClosestHit ch;
         st.n = 0;
-        if (!BVHIntersectClosest<ANIM>(sv, r.o, r.d, 1.f, st, &ch, 0.f)) break;
+        if (!BVHIntersectClosest<ANIM>(sv, r.o, r.d, 1.f, st, &ch, time)) break;
         SurfIntr si;
         // (CURVE_ALPHA: a probe segment that crosses an alpha-textured curve is respawned from the interaction the reference's recursion ends
         //  with — GeometricPrimitive::Intersect's replay, wf_shapes.h — not from the first candidate's: ADVICE r5)
-        HitInteraction<!WF_DEV_LEAN, true, ANIM>(sv, ch.prim, ch.inst, ch.h.b0, ch.h.b1, ch.h.b2, &si, r.o, r.d, 0.f);
+        HitInteraction<!WF_DEV_LEAN, true, ANIM>(sv, ch.prim, ch.inst, ch.h.b0, ch.h.b1, ch.h.b2, &si, r.o, r.d, time);
         basePi = si.pi; baseN = si.n;
         if (sv.meshes[si.mesh].material == material) {
             // wrs.Add(SubsurfaceInteraction(si->intr), 1.f)  (util/sampling.h:535-546)

@@ -800,8 +800,8 @@ WF_HD void InstanceRay(const wf_instance &in, V3 o, V3 d, float *tMax, V3 *oOut,
 // AnimatedPrimitive::Intersect (cpu/primitive.cpp:140-153): the instance record with renderFromPrimitive.Interpolate(ray.time) in place of
 // the static transformation — what InstanceRay / InstanceInteraction / InstanceWoP are then applied to.  A static instance is returned as it is.
 // ANIM = false (the default): the caller cannot meet an animated instance — the interpolation (a quaternion slerp, a 4 x 4 inverse: an
-// out-of-line callee) is then not reachable from it and does not set its register allocation (wf_scene.h "LEAN DEVICE VARIANTS").  The
-// scene builder admits animated shapes / instances only where the consumers that ask for ANIM can meet them: ordinary materials, no media.
+// out-of-line callee) is then not reachable from it and does not set its register allocation (wf_scene.h "LEAN DEVICE VARIANTS").  Every
+// consumer of a hit that can meet an animated instance asks for ANIM in the kernel variants the back end launches for such scenes.
 template <bool ANIM>
 WF_HD const wf_instance &InstanceAt(const SceneView &sv, const wf_instance &in, float time, wf_instance *tmp) {
     if constexpr (!ANIM) return in;

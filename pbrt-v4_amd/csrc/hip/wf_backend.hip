@@ -245,7 +245,7 @@ __global__ void __launch_bounds__(BLOCK) k_intersect_closest(const SceneView sv,
         ClosestHit ch;
         st.n = 0;
         bool found = BVHIntersectClosest<ANIM>(sv, V3{o.x, o.y, o.z}, V3{d.x, d.y, d.z}, WF_INFINITY, st, &ch, o.w);
-        KAfterClosestHit(sv, ws, cur, i, found, ch.prim, ch.inst, ch.h.t, ch.h.b0, ch.h.b1, ch.h.b2);
+        KAfterClosestHit<ANIM>(sv, ws, cur, i, found, ch.prim, ch.inst, ch.h.t, ch.h.b0, ch.h.b1, ch.h.b2);
         if (COUNT) { nv += ch.nodesVisited; nt += ch.trisTested; nh += found; nr += 1; }
     }
     if (COUNT) {
@@ -992,7 +992,7 @@ __global__ void __launch_bounds__(TBLOCK, TWavesFor(GenBase(GENX), INST ? WF_TWA
                 if (INST) ws.hitInst[i] = w.prim >= 0 ? w.inst : -1;
                 if (sv.haveMedia) ws.hitT[i] = w.prim >= 0 ? WalkT(w) : WF_INFINITY;
             } else
-            KRouteHitBlock<(GEN > 1) || INST>(sv, ws, cur, i, valid && !amb, w.prim, w.route, WalkT(w), w.b0, w.b1, w.b2, INST ? w.inst : -1);
+            KRouteHitBlock<(GEN > 1) || INST, GenAnim(GENX)>(sv, ws, cur, i, valid && !amb, w.prim, w.route, WalkT(w), w.b0, w.b1, w.b2, INST ? w.inst : -1);
         }, SPLIT ? cursor : nullptr, chunk, workBlocks);
     if constexpr (DRAIN) DrainRetrace<GEN, INST, GenAnim(GENX)>(sv, ws, bvh, cur, st, false);
 }
@@ -1000,11 +1000,16 @@ __global__ void __launch_bounds__(TBLOCK, TWavesFor(GenBase(GENX), INST ? WF_TWA
 // (1024 threads per workgroup: one returning atomic per destination queue per 1024 rays — a queue counter sustains ~88 of them per
 // microsecond, which at 256 rays per workgroup was the whole cost of this pass)
 constexpr int RBLOCK = 1024;
-template <bool GENERAL>
-__global__ void __launch_bounds__(RBLOCK) k_route_hits(const SceneView svArg, WorkState ws, int cur) {
+// ANIM: the scene has animated primitives (the interface skip rebuilds the hit's interaction at the ray's time).  That variant takes
+// workgroups of BLOCK threads: the interpolation is an out-of-line callee shared with the ANIM walk kernels, and a 1024-thread caller
+// would cap its registers at 128 for all of them (measured: k_closest_fast<8, true, true> 162 -> 128 VGPRs, its spills 104 -> 183).
+constexpr int RouteBlock(bool anim) { return anim ? BLOCK : RBLOCK; }
+template <bool GENERAL, bool ANIM = false>
+__global__ void __launch_bounds__(RouteBlock(ANIM)) k_route_hits(const SceneView svArg, WorkState ws, int cur) {
+    constexpr int RB = RouteBlock(ANIM);
     const SceneView &sv = SvOf<true>(svArg);
     const int n = ws.counters[(CNT_RAY0 + cur) * CNT_STRIDE];
-    for (int base = blockIdx.x * RBLOCK; base < n; base += gridDim.x * RBLOCK) {
+    for (int base = blockIdx.x * RB; base < n; base += gridDim.x * RB) {
         const int i = base + threadIdx.x;
         bool valid = i < n;
         uint32_t route = 0;
@@ -1020,7 +1025,7 @@ __global__ void __launch_bounds__(RBLOCK) k_route_hits(const SceneView svArg, Wo
                 if (sv.haveMedia) tHit = ws.hitT[i];
             }
         }
-        KRouteHitBlock<GENERAL>(sv, ws, cur, i, valid, (int)FloatToBits(h.x), route, tHit, h.y, h.z, h.w, inst);
+        KRouteHitBlock<GENERAL, ANIM>(sv, ws, cur, i, valid, (int)FloatToBits(h.x), route, tHit, h.y, h.z, h.w, inst);
     }
 }
 // the rays k_closest_fast marked as near-ties, in the reference's own traversal order (rare: coplanar overlapping geometry)
@@ -1054,15 +1059,17 @@ __global__ void __launch_bounds__(BLOCK) k_intersect_one_random(const SceneView 
     for (int i = gtid; i < n; i += stride) KIntersectOneRandom<ANIM>(sv, ws, i, st);
 }
 // IntersectOneRandom on caller-supplied probe segments (the boundary adapter's path): segs = p0.xyz p1.xyz per item
-__global__ void __launch_bounds__(BLOCK) k_trace_one_random(const SceneView sv, int n, const float *segs, const int32_t *material, wf_hit_record *out, float *pdf,
-                                                            int *stackSpill) {
+// ANIM: walked at times[i] (wf_trace_one_random_host_t); otherwise at time 0 on a static scene
+template <bool ANIM>
+__global__ void __launch_bounds__(BLOCK) k_trace_one_random(const SceneView sv, int n, const float *segs, const int32_t *material, const float *times, wf_hit_record *out,
+                                                            float *pdf, int *stackSpill) {
     const int gtid = blockIdx.x * BLOCK + threadIdx.x, stride = gridDim.x * BLOCK;
     LdsStack st{stackSpill + gtid, stride, 0};
     for (int i = gtid; i < n; i += stride) {
         const float *s = segs + (size_t)6 * i;
         ClosestHit ch;
         SurfIntr si;
-        float p = IntersectOneRandom(sv, V3{s[0], s[1], s[2]}, V3{s[3], s[4], s[5]}, material[i], st, &ch, &si);
+        float p = IntersectOneRandom<ANIM>(sv, V3{s[0], s[1], s[2]}, V3{s[3], s[4], s[5]}, material[i], st, &ch, &si, ANIM ? times[i] : 0.f);
         wf_hit_record h{};
         h.prim = p != 0 ? ch.prim : -1;
         if (p != 0) { h.t = ch.h.t; h.b0 = ch.h.b0; h.b1 = ch.h.b1; h.b2 = ch.h.b2; h.instance = ch.inst; } else h.instance = -1;
@@ -1135,9 +1142,11 @@ __global__ void __launch_bounds__(TBLOCK) k_trace_any_fast(const SceneView sv, F
         [&](int i, bool valid, const RayWalk &w) { if (valid) occluded[i] = w.prim >= 0; });
 }
 
+// ANIM: the scene has animated primitives (the amount textures are evaluated on the interaction at the ray's time)
+template <bool ANIM>
 __global__ void __launch_bounds__(BLOCK) k_resolve_mix(const SceneView sv, WorkState ws, int cur) {
     const int n = ws.counters[(CNT_MIX) * CNT_STRIDE];
-    for (int i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) KResolveMix(sv, ws, cur, i);
+    for (int i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) KResolveMix<ANIM>(sv, ws, cur, i);
 }
 // K5 / K6 / K11: participating media (wf_media.h, wf_kernels.h)
 // (round 5) the delta-tracking loop alone: the routing of the items that reach their surface — interaction rebuild of interface hits,
@@ -1158,9 +1167,11 @@ __global__ void __launch_bounds__(BLOCK, LEAN ? WF_MEDIUM_WAVES_LEAN : WF_MEDIUM
     // (the nested-loop form of rounds 1-5 measured 43.2 ms against this form's 36.5 on the cloud scene, same box: profiles/r06_medium_nested_vs_state_machine_ab_cloud16.txt)
     for (int i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) KSampleMediumInteraction<LEAN>(sv, ws, cur, i);
 }
+// ANIM: the scene has animated primitives (interface / MixMaterial hits are rebuilt at the ray's time)
+template <bool ANIM>
 __global__ void __launch_bounds__(BLOCK) k_medium_route(const SceneView sv, WorkState ws, int cur) {
     const int n = ws.counters[(CNT_MEDIUM_ROUTE) * CNT_STRIDE];
-    for (int i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) KMediumRoute(sv, ws, cur, i);
+    for (int i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) KMediumRoute<ANIM>(sv, ws, cur, i);
 }
 template <bool RARE>
 __global__ void __launch_bounds__(BLOCK) k_medium_scatter(const SceneView sv, WorkState ws, int cur) {
@@ -2988,7 +2999,9 @@ int wf_intersect_closest(wf_ctx *ctx, int depth) {
             {
                 Prof prof_(ctx, "Route hits");
                 const int g = std::min(MAX_GRID, std::max(1, (ctx->maxQueueSize + RBLOCK - 1) / RBLOCK));
-                if (ctx->genMode > 1 || ctx->svHost.nInstances > 0) hipLaunchKernelGGL(k_route_hits<true>, dim3(g), dim3(RBLOCK), 0, ctx->stream, ctx->svHost, ctx->ws, depth & 1);
+                if (ctx->svHost.haveAnimated)   // (two-level)
+                    hipLaunchKernelGGL((k_route_hits<true, true>), dim3(std::min(MAX_GRID, std::max(1, (ctx->maxQueueSize + BLOCK - 1) / BLOCK))), dim3(BLOCK), 0, ctx->stream, ctx->svHost, ctx->ws, depth & 1);
+                else if (ctx->genMode > 1 || ctx->svHost.nInstances > 0) hipLaunchKernelGGL(k_route_hits<true>, dim3(g), dim3(RBLOCK), 0, ctx->stream, ctx->svHost, ctx->ws, depth & 1);
                 else hipLaunchKernelGGL(k_route_hits<false>, dim3(g), dim3(RBLOCK), 0, ctx->stream, ctx->svHost, ctx->ws, depth & 1);
             }
         }
@@ -2997,7 +3010,10 @@ int wf_intersect_closest(wf_ctx *ctx, int depth) {
             if (int e = JoinRetrace(ctx)) return e;
         } else if (!RetraceInline(ctx->genMode))
         LAUNCH("Intersect closest: near-tie re-trace", k_closest_retrace, 128, ctx->svHost, ctx->ws, depth & 1, ctx->stackSpill);
-        if (ctx->svHost.haveMix) LAUNCH("Resolve MixMaterial hits", k_resolve_mix, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
+        if (ctx->svHost.haveMix) {
+            if (ctx->svHost.haveAnimated) LAUNCH("Resolve MixMaterial hits", k_resolve_mix<true>, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
+            else LAUNCH("Resolve MixMaterial hits", k_resolve_mix<false>, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
+        }
     } else
         { if (ctx->svHost.haveAnimated) LAUNCH("Intersect closest", (k_intersect_closest<false, true>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1, ctx->stackSpill);
           else LAUNCH("Intersect closest", k_intersect_closest<false>, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1, ctx->stackSpill); }
@@ -3009,7 +3025,8 @@ int wf_medium_sample(wf_ctx *ctx, int depth) {
     if (!ctx->svHost.haveMedia) return 0;
     if (ctx->mediumLean) LAUNCH("Sample medium interaction", k_medium_sample<true>, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
     else LAUNCH("Sample medium interaction", k_medium_sample<false>, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
-    LAUNCH("Sample medium interaction: route surface hits", k_medium_route, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
+    if (ctx->svHost.haveAnimated) LAUNCH("Sample medium interaction: route surface hits", k_medium_route<true>, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
+    else LAUNCH("Sample medium interaction: route surface hits", k_medium_route<false>, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
     if (depth == ctx->maxDepth) return 0;
     if (ctx->rareLights) LAUNCH("Sample direct/indirect - Henyey-Greenstein", k_medium_scatter<true>, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
     else LAUNCH("Sample direct/indirect - Henyey-Greenstein", k_medium_scatter<false>, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
@@ -3498,13 +3515,14 @@ int wf_trace_closest_host(wf_ctx *ctx, int n, const float *o, const float *d, co
     return 0;
 }
 // IntersectShadowTr on caller-supplied shadow rays: a scratch WorkState over temporary device arrays (one "pixel" per ray) run through
-// the same transmittance kernels as the render
-int wf_trace_shadow_tr_host(wf_ctx *ctx, int n, const float *o, const float *d, const float *tmax, const int32_t *medium, const float *lambda,
-                            const float *Ld, const float *r_u, const float *r_l, float *out_L) {
+// the same transmittance kernels as the render.  time != nullptr (wf_trace_shadow_tr_host_t): the rays' times are the pixels' path
+// times (ws.pathTime) of the reference-order walk's ANIM variant, the render's kernel for scenes with animated primitives.
+static int TraceShadowTrHost(wf_ctx *ctx, const char *fn, int n, const float *o, const float *d, const float *tmax, const int32_t *medium, const float *lambda,
+                             const float *Ld, const float *r_u, const float *r_l, const float *time, float *out_L) {
     if (!ctx || !ctx->sceneLoaded) return fail(-1, "no scene uploaded");
     useDevice(ctx);
-    if (!ctx->svHost.haveMedia) return fail(-1, "wf_trace_shadow_tr_host: the scene has no media");
-    if (ctx->svHost.haveAnimated) return fail(-1, "wf_trace_shadow_tr_host: the scene has animated primitives and this entry point carries no ray times (not supported)");
+    if (!ctx->svHost.haveMedia) return fail(-1, "%s: the scene has no media", fn);
+    if (ctx->svHost.haveAnimated && !time) return fail(-1, "%s: the scene has animated primitives and this entry point carries no ray times (wf_trace_shadow_tr_host_t)", fn);
     if (n <= 0) return 0;
     std::vector<F4> ho(n), hd(n), hl(n), hp(n, F4{1, 1, 1, 1});
     for (int i = 0; i < n; ++i) {
@@ -3532,7 +3550,10 @@ int wf_trace_shadow_tr_host(wf_ctx *ctx, int n, const float *o, const float *d, 
         return e;
     HIPCHK(hipMemcpyAsync(cnt + CNT_SHADOW * CNT_STRIDE, &n, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     ws.counters = cnt;
-    if (ctx->fastOk && ctx->svHost.nInstances == 0) {
+    if (time) {
+        if ((e = up(&ws.pathTime, time, n * sizeof(float)))) return e;
+        LAUNCH("shadow Tr (host rays, timed)", k_shadow_tr<true>, gridFor(n), ctx->svHost, ws, ctx->stackSpill);
+    } else if (ctx->fastOk && ctx->svHost.nInstances == 0) {
         if (ctx->svHost.haveAlpha || ctx->svHost.nQuadrics > 0) LAUNCHT("shadow Tr (host rays)", k_shadow_tr_fast<true>, ctx->persistentGrid, ctx->svHost, ws, ctx->fast, ctx->spillArea());
         else LAUNCHT("shadow Tr (host rays)", k_shadow_tr_fast<false>, ctx->persistentGrid, ctx->svHost, ws, ctx->fast, ctx->spillArea());
     } else LAUNCH("shadow Tr (host rays)", k_shadow_tr<false>, gridFor(n), ctx->svHost, ws, ctx->stackSpill);
@@ -3541,17 +3562,27 @@ int wf_trace_shadow_tr_host(wf_ctx *ctx, int n, const float *o, const float *d, 
     for (void *p : tmp) HIPCHK(hipFree(p));
     return 0;
 }
-int wf_trace_one_random_host(wf_ctx *ctx, int n, const float *p0, const float *p1, const int32_t *material, wf_hit_record *out, float *reservoir_pdf) {
+int wf_trace_shadow_tr_host(wf_ctx *ctx, int n, const float *o, const float *d, const float *tmax, const int32_t *medium, const float *lambda,
+                            const float *Ld, const float *r_u, const float *r_l, float *out_L) {
+    return TraceShadowTrHost(ctx, "wf_trace_shadow_tr_host", n, o, d, tmax, medium, lambda, Ld, r_u, r_l, nullptr, out_L);
+}
+int wf_trace_shadow_tr_host_t(wf_ctx *ctx, int n, const float *o, const float *d, const float *tmax, const int32_t *medium, const float *lambda,
+                              const float *Ld, const float *r_u, const float *r_l, const float *time, float *out_L) {
+    if (!time) return fail(-1, "wf_trace_shadow_tr_host_t: no ray times");
+    return TraceShadowTrHost(ctx, "wf_trace_shadow_tr_host_t", n, o, d, tmax, medium, lambda, Ld, r_u, r_l, time, out_L);
+}
+// time != nullptr (wf_trace_one_random_host_t): every segment walked at its own time (the render's probes walk at time 0,
+// wavefront/subsurface.cpp:70)
+static int TraceOneRandomHost(wf_ctx *ctx, int n, const float *p0, const float *p1, const int32_t *material, const float *time, wf_hit_record *out, float *reservoir_pdf) {
     if (!ctx || !ctx->sceneLoaded) return fail(-1, "no scene uploaded");
     useDevice(ctx);
-    // (the reference walks its subsurface probe segments at time 0, wavefront/subsurface.cpp:70: an animated scene would need that walk's
-    //  ANIM variant here — refused instead of answered for the start-time geometry)
-    if (ctx->svHost.haveAnimated) return fail(-1, "wf_trace_one_random_host: the scene has animated primitives (not supported by this entry point)");
+    // (without times an animated scene is refused instead of answered for the start-time geometry)
+    if (ctx->svHost.haveAnimated && !time) return fail(-1, "wf_trace_one_random_host: the scene has animated primitives and this entry point carries no segment times (wf_trace_one_random_host_t)");
     if (n <= 0) return 0;
     std::vector<float> segs((size_t)n * 6);
     for (int i = 0; i < n; ++i)
         for (int k = 0; k < 3; ++k) { segs[(size_t)i * 6 + k] = p0[3 * i + k]; segs[(size_t)i * 6 + 3 + k] = p1[3 * i + k]; }
-    float *ds = nullptr, *dp = nullptr;
+    float *ds = nullptr, *dp = nullptr, *dt = nullptr;
     int32_t *dm = nullptr;
     wf_hit_record *dh = nullptr;
     HIPCHK(hipMalloc((void **)&ds, segs.size() * sizeof(float)));
@@ -3560,12 +3591,24 @@ int wf_trace_one_random_host(wf_ctx *ctx, int n, const float *p0, const float *p
     HIPCHK(hipMalloc((void **)&dp, (size_t)n * sizeof(float)));
     HIPCHK(hipMemcpyAsync(ds, segs.data(), segs.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(dm, material, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    LAUNCH("intersect one random (host segments)", k_trace_one_random, gridFor(n), ctx->svHost, n, ds, dm, dh, dp, ctx->stackSpill);
+    if (time) {
+        HIPCHK(hipMalloc((void **)&dt, (size_t)n * sizeof(float)));
+        HIPCHK(hipMemcpyAsync(dt, time, (size_t)n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+        LAUNCH("intersect one random (host segments, timed)", k_trace_one_random<true>, gridFor(n), ctx->svHost, n, ds, dm, (const float *)dt, dh, dp, ctx->stackSpill);
+    } else LAUNCH("intersect one random (host segments)", k_trace_one_random<false>, gridFor(n), ctx->svHost, n, ds, dm, (const float *)nullptr, dh, dp, ctx->stackSpill);
     HIPCHK(hipMemcpyAsync(out, dh, (size_t)n * sizeof(wf_hit_record), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(reservoir_pdf, dp, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     HIPCHK(hipFree(ds)); HIPCHK(hipFree(dm)); HIPCHK(hipFree(dh)); HIPCHK(hipFree(dp));
+    if (dt) HIPCHK(hipFree(dt));
     return 0;
+}
+int wf_trace_one_random_host(wf_ctx *ctx, int n, const float *p0, const float *p1, const int32_t *material, wf_hit_record *out, float *reservoir_pdf) {
+    return TraceOneRandomHost(ctx, n, p0, p1, material, nullptr, out, reservoir_pdf);
+}
+int wf_trace_one_random_host_t(wf_ctx *ctx, int n, const float *p0, const float *p1, const int32_t *material, const float *time, wf_hit_record *out, float *reservoir_pdf) {
+    if (!time) return fail(-1, "wf_trace_one_random_host_t: no segment times");
+    return TraceOneRandomHost(ctx, n, p0, p1, material, time, out, reservoir_pdf);
 }
 int wf_trace_any_host(wf_ctx *ctx, int n, const float *o, const float *d, const float *tmax, int32_t *occluded, int32_t *nodes_visited, int32_t *tris_tested) {
     if (!ctx || !ctx->sceneLoaded) return fail(-1, "no scene uploaded");

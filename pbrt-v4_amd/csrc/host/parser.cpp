@@ -2,7 +2,8 @@
 // src/pbrt/parser.cpp (tokenizer :140-330, parameter lists :434-600, directives :600-1000) and the
 // graphics-state bookkeeping of BasicSceneBuilder (src/pbrt/scene.cpp:80-620).  ActiveTransform is tracked (start- and end-time
 // CTM) and TransformTimes kept: a CAMERA created under two different CTMs moves over that interval (camera motion blur — what the
-// reference's own GPU path supports too); creating a shape, light or medium where the two differ (AnimatedPrimitive) is refused.
+// reference's own GPU path supports too); a shape or object instance created where the two differ is an AnimatedPrimitive, a light
+// takes the start transformation with the reference's warning.
 #include "scene.h"
 #include "hanimated.h"
 #include <algorithm>
@@ -281,7 +282,7 @@ static int ParseIntTok(const std::string &t, const std::string &loc) {
 // ---- graphics state & interpreter --------------------------------------------------------------------
 struct GraphicsState {
     Transform ctm;       // the start-time CTM: what a static render uses
-    Transform ctmEnd;    // the end-time CTM (ActiveTransform EndTime); they must agree wherever something is created
+    Transform ctmEnd;    // the end-time CTM (ActiveTransform EndTime); a shape / instance created where the two differ is animated
     int activeBits = 3;  // ActiveTransform: 1 StartTime, 2 EndTime, 3 All
     bool reverseOrientation = false;
     int currentMaterialIndex = 0;
@@ -316,13 +317,6 @@ struct Interpreter {
         std::reverse(ps.params.begin(), ps.params.end());
         ps.params.insert(ps.params.end(), attrs.rbegin(), attrs.rend());
         return ps;
-    }
-    // a static render uses the start-time transformation; something created under two different CTMs is animated (AnimatedTransform /
-    // AnimatedPrimitive in the reference): refused, not rendered in the wrong place
-    void RequireStaticCTM(const std::string &loc) const {
-        for (int i = 0; i < 4; ++i)
-            for (int j = 0; j < 4; ++j)
-                if (gs.ctm.m.m[i][j] != gs.ctmEnd.m.m[i][j]) Fatal(loc, "animated transformations (ActiveTransform StartTime / EndTime with different CTMs) are not supported by this build");
     }
     Transform RenderFromObject() const { return Transform((renderFromWorld * gs.ctm).m); }
     bool CTMIsAnimated() const {   // TransformSet::IsAnimated (scene.h): ctm[0] != ctm[1]
@@ -481,7 +475,8 @@ struct Interpreter {
             else if (tok == "LightSource") {
                 LightEntity e;
                 basicParamDirective(&e, gs.lightAttributes);
-                RequireStaticCTM(loc);
+                // BasicScene::AddLight (scene.cpp:1007-1009): a light under an animated CTM is created with the start transformation
+                if (CTMIsAnimated()) fprintf(stderr, "Warning: %s: Animated lights aren't supported. Using the start transform.\n", loc.c_str());
                 e.renderFromLight = RenderFromObject();
                 e.medium = gs.currentOutsideMedium;
                 scene->lights.push_back(std::move(e));

@@ -3624,14 +3624,9 @@ void BuildSceneTables(const ParsedScene &scene, const RenderOptions &optIn, Scen
                 // the ORDER of candidates at exactly coincident geometry only (stated in DESIGN.md 2).
                 for (int j = 0; j < 3; ++j)
                     if (u.renderFromInstanceEnd.m.m[3][j] != 0 || u.renderFromInstanceEnd.m.m[3][3] != 1) Die(u.loc, "only affine animated transformations are supported");
-                // what this build admits (the consumers of a hit that interpolate the transformation are the walks, the transmittance trace and
-                // the material stage: wf_shapes.h InstanceAt<ANIM>): ordinary materials on the animated primitives
-                for (const auto &pr : defPrims[d]) {
-                    const int meshId = pr.first < nTrisAll ? T->triMesh[pr.first] : T->quadrics[pr.first - nTrisAll].mesh;
-                    const int mt = T->meshes[meshId].material < 0 ? (int)WF_MAT_INTERFACE : T->materials[T->meshes[meshId].material].type;
-                    if (mt == WF_MAT_INTERFACE || mt == WF_MAT_MIX || mt == WF_MAT_SUBSURFACE)
-                        Die(u.loc, "an animated shape / instance with an interface, mix or subsurface material is not supported by this build");
-                }
+                // (every material: the consumers of a hit interpolate the transformation at the ray's time — the walks, the transmittance trace,
+                // the interface skip and MixMaterial resolve of the routing, the material stage: wf_shapes.h InstanceAt<ANIM>; the subsurface
+                // probes at time 0, as the reference's)
                 const wf_animated_transform A = MakeAnimatedTransform(u.renderFromInstance, u.startTime, u.renderFromInstanceEnd, u.endTime);
                 in.anim_plus1 = (int)T->animated.size() + 1;
                 T->animated.push_back(A);

@@ -60,6 +60,7 @@ ABI_SYMBOLS = [
     "wf_trace_closest_host", "wf_trace_any_host", "wf_sampler_probe", "wf_libm_probe", "wf_kat_probe", "wf_queue_size", "wf_queue_download",
     "wf_counters_enable", "wf_counters_download", "wf_kernel_time_ms", "wf_debug_counters", "wf_debug_fastbvh_check", "wf_trace_closest_host_t", "wf_trace_any_host_t", "wf_ctx_query",
     "wf_trace_closest_device", "wf_trace_any_device", "wf_device_alloc", "wf_device_free", "wf_device_upload", "wf_device_download", "wf_trace_shadow_tr_host",
+    "wf_trace_shadow_tr_host_t", "wf_trace_one_random_host_t",
 ]
 HOST_SYMBOLS = [
     "wfh_init", "wfh_last_error", "wfh_scene_load", "wfh_scene_load_string", "wfh_scene_free", "wfh_scene_desc", "wfh_scene_info",
@@ -285,6 +286,46 @@ class Scene:
         _check(hip.wf_trace_closest_host_t(self.ctx, n, o.ctypes.data, d.ctypes.data, tmax.ctypes.data, time.ctypes.data, C.addressof(out)), "wf_trace_closest_host_t")
         return np.frombuffer(out, dtype=np.dtype([("prim", "<i4"), ("t", "<f4"), ("b0", "<f4"), ("b1", "<f4"), ("b2", "<f4"),
                                                   ("nodes_visited", "<i4"), ("tris_tested", "<i4"), ("instance", "<i4")])).copy()
+
+    def trace_shadow_tr(self, o, d, tmax, medium, lambda_, Ld, r_u, r_l, time=None):
+        """wf_trace_shadow_tr_host (time=None) / wf_trace_shadow_tr_host_t: IntersectShadowTr on the given shadow rays of a scene with media —
+        per ray the medium id, four wavelengths and the item's Ld / r_u / r_l; returns the [n, 4] radiance each ray adds to its pixel"""
+        _, hip = libs()
+        o, d, tmax = (np.ascontiguousarray(a, dtype=np.float32) for a in (o, d, tmax))
+        medium = np.ascontiguousarray(medium, dtype=np.int32)
+        lambda_, Ld, r_u, r_l = (np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 4) for a in (lambda_, Ld, r_u, r_l))
+        n = o.shape[0]
+        out = np.zeros((n, 4), dtype=np.float32)
+        args = [self.ctx, n] + [a.ctypes.data for a in (o, d, tmax, medium, lambda_, Ld, r_u, r_l)]
+        if time is None:
+            hip.wf_trace_shadow_tr_host.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 9
+            _check(hip.wf_trace_shadow_tr_host(*args, out.ctypes.data), "wf_trace_shadow_tr_host")
+        else:
+            time = np.ascontiguousarray(time, dtype=np.float32)
+            hip.wf_trace_shadow_tr_host_t.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 10
+            _check(hip.wf_trace_shadow_tr_host_t(*args, time.ctypes.data, out.ctypes.data), "wf_trace_shadow_tr_host_t")
+        return out
+
+    def trace_one_random(self, p0, p1, material, time=None):
+        """wf_trace_one_random_host (time=None) / wf_trace_one_random_host_t: IntersectOneRandom on probe segments p0 -> p1 —
+        (hit records, reservoir pdfs) of one surface of material[i] along each segment"""
+        _, hip = libs()
+        p0, p1 = (np.ascontiguousarray(a, dtype=np.float32) for a in (p0, p1))
+        material = np.ascontiguousarray(material, dtype=np.int32)
+        n = p0.shape[0]
+        out = (HitRecord * n)()
+        pdf = np.zeros(n, dtype=np.float32)
+        if time is None:
+            hip.wf_trace_one_random_host.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
+            _check(hip.wf_trace_one_random_host(self.ctx, n, p0.ctypes.data, p1.ctypes.data, material.ctypes.data, C.addressof(out), pdf.ctypes.data),
+                   "wf_trace_one_random_host")
+        else:
+            time = np.ascontiguousarray(time, dtype=np.float32)
+            hip.wf_trace_one_random_host_t.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6
+            _check(hip.wf_trace_one_random_host_t(self.ctx, n, p0.ctypes.data, p1.ctypes.data, material.ctypes.data, time.ctypes.data, C.addressof(out),
+                                                  pdf.ctypes.data), "wf_trace_one_random_host_t")
+        return np.frombuffer(out, dtype=np.dtype([("prim", "<i4"), ("t", "<f4"), ("b0", "<f4"), ("b1", "<f4"), ("b2", "<f4"),
+                                                  ("nodes_visited", "<i4"), ("tris_tested", "<i4"), ("instance", "<i4")])).copy(), pdf
 
     def bounds(self):
         """WavefrontAggregate::Bounds() in rendering space: (pMin[3], pMax[3])"""

@@ -231,7 +231,10 @@ class Gen:
         return out
 
     def material(self, name):
-        t = self.pick(["diffuse"] * 3 + ["conductor", "dielectric", "thindielectric", "diffusetransmission", "coateddiffuse", "coatedconductor", "hair", "subsurface", "measured", "interface"])   # ("mix" hashes heap pointers in the reference: statistical, tests/test_oracle_golden.py)
+        # ("mix" hashes heap pointers in the reference where its amount lies strictly between 0 and 1: statistical, tests/test_oracle_golden.py;
+        #  its amounts here are 0 / 1 only — a constant, or a point-filtered lookup of an image of zeros and ones through a planar mapping of the
+        #  hit's position, which on an animated primitive is the position at the ray's time)
+        t = self.pick(["diffuse"] * 3 + ["conductor", "dielectric", "thindielectric", "diffusetransmission", "coateddiffuse", "coatedconductor", "hair", "subsurface", "measured", "interface", "mix"])
         rough = lambda pre="": ('%s "bool remaproughness" %s' % (self.float_param(pre + "roughness", 0, 0.6), self.pick(["true", "false"]))
                                 if self.r.random() < 0.6 else '"float %suroughness" [ %s ] "float %svroughness" [ %s ]' % (pre, f(self.u(0, 0.5)), pre, f(self.u(0, 0.5))))
         extra = ""
@@ -273,8 +276,14 @@ class Gen:
             if len(prev) < 2:
                 return self.material(name)
             a, b = self.r.sample(prev, 2)
-            body = '"string materials" [ "%s" "%s" ] %s' % (a[0], b[0], self.float_param("amount", 0, 1))
             extra = ""
+            if self.r.random() < 0.3:
+                body = '"string materials" [ "%s" "%s" ] "float amount" [ %d ]' % (a[0], b[0], self.pick([0, 1]))
+            else:
+                tex = 'Texture "%s_amount" "float" "imagemap" "string filename" "%s" "string filter" "point" "string mapping" "planar" "vector3 v1" [ %s ] "vector3 v2" [ %s ]\n' % (
+                    name, os.path.join(GOLDEN, "checker01.pfm"), f(self.u(-1, 1), self.u(-1, 1), self.u(-1, 1)), f(self.u(-1, 1), self.u(-1, 1), self.u(-1, 1)))
+                self.materials.append((name, t))
+                return tex + 'MakeNamedMaterial "%s" "string type" "mix" "string materials" [ "%s" "%s" ] "texture amount" "%s_amount"' % (name, a[0], b[0], name)
         self.materials.append((name, t))
         return 'MakeNamedMaterial "%s" "string type" "%s" %s%s' % (name, t, body, extra)
 
@@ -370,7 +379,7 @@ class Gen:
         if self.r.random() < 0.12:   # (round 4, end) ConcatTransform with a sheared matrix on top of the usual chain
             body = "  ConcatTransform [ 1 %s 0 0  0 1 0 0  %s 0 1 0  0 0 0 1 ]\n" % (f(self.u(-0.4, 0.4)), f(self.u(-0.3, 0.3))) + body
         # (round 5) AnimatedPrimitive: the shape / instance under an animated CTM — where this build admits it: no
-        # emitter, an ordinary material (the caller says so).  A translation, half of the time a scale too; NO rotation: the reference
+        # emitter (the caller says so; the reference refuses animated area lights).  A translation, half of the time a scale too; NO rotation: the reference
         # bounds a rotating primitive through the zeros of its motion derivative (util/transform.cpp:434-960, not restated), this build
         # through samples of the path — the boxes, and with them the scene bounds the lights are preprocessed with, differ in the last
         # bits, and the comparison here is bit for bit (tests/golden/animated.pbrt has rotations under a ground plane that fixes the bounds)
@@ -431,7 +440,6 @@ class Gen:
         if have_def:
             solid = [m for m in self.materials if m[1] != "interface"]
             def_mat = self.pick(solid) if solid else ("m0", self.materials[0][1] if self.materials else "diffuse")
-            def_mat_type = def_mat[1]
             out.append('ObjectBegin "thing"\n  NamedMaterial "%s"\n  %s\n  Translate 0 0 1.2\n  %s\nObjectEnd' % (def_mat[0], self.shape(), self.shape()))
         for i in range(self.r.randrange(2, 7)):
             name, t = self.pick(self.materials)
@@ -450,10 +458,10 @@ class Gen:
             if self.r.random() < 0.15:
                 body += "  ReverseOrientation\n"
             body += "  " + self.shape()
-            out.append(self.placed(body, may_animate=not emitter and t not in ("interface", "mix", "subsurface")))
+            out.append(self.placed(body, may_animate=not emitter))
         if have_def:
             for _ in range(self.r.randrange(1, 4)):
-                out.append(self.placed('  ObjectInstance "thing"', may_animate=def_mat_type not in ("interface", "mix", "subsurface")))
+                out.append(self.placed('  ObjectInstance "thing"', may_animate=True))
         if "fog" in self.media:
             # A ray that travels in a medium and MISSES every surface is pushed by MediumSampleQueue::Push(RayWorkItem, tMax), which leaves the
             # item's `depth` unwritten (wavefront/workitems.h:468-492): the reference then reads a stale depth and its image depends on
