@@ -27,6 +27,7 @@
 #include <string>
 #include <thread>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 // This unit is compiled with -ftrivial-auto-var-init=zero (Makefile, BACKENDFLAGS; DESIGN 4.1 "Locals that start as undef"): the walk
@@ -65,6 +66,30 @@ constexpr int MAX_GRID = 256 * 8;  // 256 CUs x up to 8 resident 256-thread work
 
 struct SpillArea { int *base; int rows; int *dbg; };   // the context's stackSpill rows + the debug words (kernel argument of the production traversal)
 
+// The production walk kernels of the uploaded scene and their resident grids: filled once, by PickWalkKernels at the end of the traversal
+// set-up of wf_scene_upload, the only place that turns (genMode, genTri, deferGeneral, animFast, nInstances) into template instantiations.
+// Every launch below goes through these pointers, so the kernel whose occupancy sized a grid is the kernel launched on it.
+// (every instantiation of a walk kernel template has the signature of its pointer type)
+using ClosestWalkFn = void (*)(const SceneView, WorkState, FastBVH, int, SpillArea, int *, int, const int *);   // k_closest_fast
+using ShadowWalkFn = void (*)(const SceneView, WorkState, FastBVH, SpillArea, int *, int, const int *);         // k_shadow_fast
+using TrTraceFn = void (*)(const SceneView, WorkState, FastBVH, int, SpillArea);                                // k_tr_trace
+using TraceClosestFn = void (*)(const SceneView, FastBVH, int, const float *, wf_hit_record *, SpillArea);      // k_trace_closest_fast
+using TraceAnyFn = void (*)(const SceneView, FastBVH, int, const float *, int32_t *, SpillArea);                // k_trace_any_fast
+struct WalkKernels {
+    ClosestWalkFn closest = nullptr;   // the launch every ray goes through
+    ShadowWalkFn shadow = nullptr;
+    // TWO-CLASS TRAVERSAL (round 6): `closest` / `shadow` are then the triangle kernels (genTri = 0 | 1) in their handing-over variants, and
+    // these the general kernels (genMode >= 2) that walk only the rays handed to deferQ; null otherwise
+    ClosestWalkFn closestGen = nullptr;
+    ShadowWalkFn shadowGen = nullptr;
+    int grid = 1024, gridShadow = 1024, gridGen = 1024, gridShadowGen = 1024;   // resident workgroups of the four, each from its own kernel's occupancy
+    // The kernels below are launched on `grid`, the closest-hit walk's, and k_shadow_tr_fast with them, not on grids of their own: an
+    // occupancy query per kernel would change their launches and so their times — a measurement of its own, left as it is here.
+    TrTraceFn trTrace = nullptr;       // the transmittance wavefront's walk (genMode <= 1 only: null otherwise)
+    TraceClosestFn traceClosest = nullptr;   // wf_trace_closest_device / wf_trace_any_device
+    TraceAnyFn traceAny = nullptr;
+};
+
 struct wf_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -82,7 +107,6 @@ struct wf_ctx {
     hipStream_t stream2 = nullptr;   // the near-tie re-trace runs here, beside the routing pass and the next stage's sample generation
     hipEvent_t evFork = nullptr, evJoin = nullptr;
     bool retracePending = false, deferJoin = false;
-    int overlapRetrace = 1;      // WF_OVERLAP_RETRACE=0: everything on one stream
     // the transmittance wavefront: -1 = for two-level scenes only (default), 1 = always, 0 = never (WF_TR_WAVEFRONT).  Measured on the
     // cloud-like spec scene (14 triangles, 512^3 grid; gpurun_out/r3j_bench_cloud_tr*.json): per-lane loop 27.9 ms per 16 spp, wavefront
     // 31.4 ms (begin 3.3 + trace 3.7 + segment 24.1 + rest 0.3) — the time is the ratio tracking through the grid, not the walk, and the
@@ -90,9 +114,6 @@ struct wf_ctx {
     int trWavefront = -1;
     bool cursorDirty[2] = {false, false};   // the closest-hit / any-hit work cursor has been used since a k_reset last zeroed it
     bool mediumLean = false;     // every medium is homogeneous or a non-emissive uniform grid: k_medium_sample<true>
-    int matStreams = 0;          // WF_MAT_STREAMS=0: the material kernels of one depth one after the other on the render stream
-    hipStream_t matStream[WF_MAT_NTYPES] = {};
-    hipEvent_t evMatFork = nullptr, evMatJoin[WF_MAT_NTYPES] = {};
     bool portalLights = false;   // the scene has a portal infinite light (k_handle_escaped<RARE>)
     bool leanShade = false;      // the scene qualifies for the lean shade kernels (SceneLean: set at upload)
     // ... per MATERIAL TYPE since round 6: a type none of whose materials sits on a quadric / patch / curve keeps its lean shade kernel
@@ -100,21 +121,14 @@ struct wf_ctx {
     bool leanType[WF_MAT_NTYPES] = {};
     bool rareLights = false;     // the scene has a light type only the VARIANT 2 material kernels sample (portal infinite lights)
     int genMode = 0;             // general-primitive strength of the traversal kernels: 0 triangles only, 1 simple alpha, 2 anything but curves and alpha on quadrics, 3 anything (see GeneralPrims)
-    int persistentGrid = 1024;   // resident workgroups for the persistent traversal kernels (closest-hit variant of the scene)
-    int persistentGridShadow = 1024;
-    // TWO-CLASS TRAVERSAL (round 6): the triangle kernels (genTri = 0 | 1, in their handing-over variants) walk every ray, the general
-    // kernels (genMode >= 2) only the rays handed to deferQ; persistentGrid / persistentGridShadow are then the triangle kernels' grids
-    bool deferGeneral = false;
+    bool deferGeneral = false;   // TWO-CLASS TRAVERSAL (see WalkKernels)
     int genTri = 0;
     bool animFast = false;       // the scene's AnimatedPrimitives are walked by the production kernels' ANIM variants (round 6; genMode <= 1 only)
-    int persistentGridGen = 1024, persistentGridShadowGen = 1024;
-    static bool splitRouteWanted() { return true; }
-    int cursorChunk = 2;         // 64-ray batches a closest-hit wave takes per cursor fetch (WF_CURSOR_CHUNK sets both)
+    WalkKernels walk;
+    int cursorChunk = 2;         // 64-ray batches a closest-hit wave takes per cursor fetch (chosen from the tree size at upload)
     int cursorChunkShadow = 2;   // ... an any-hit wave (round 6, with the descent scheduling, 10 M-triangle scene: closest-hit 27.7 ms at 1, 26.7 at 3, 27.0 at 4, 27.4 at 8, 29.9 at 16;
                                  // any-hit 12.15 at 1, 12.16 at 3, 12.4 at 4, 13.0 at 8: profiles/r06_cursor_chunk_ab_sm16.txt)
                                  // (-3 %), but on a 30 k-triangle scene one fetch per 64 rays is 83 atomics/us on one counter: the kernel's bound
-    int splitRoute = 2;          // WF_SPLIT_ROUTE: 0 = the closest-hit walk routes its hits per workgroup (KRouteHitBlock inside the walk);
-                                 // 1 = walk without the workgroup barrier + k_route_hits; 2 (default) = 1 + waves draw their rays from a shared cursor
     int32_t *probeCursor = nullptr;
     bool matPresent[WF_MAT_NTYPES] = {};
     int W = 0, H = 0;
@@ -404,6 +418,7 @@ __device__ __attribute__((noinline)) bool AlphaTestSimpleP(const SceneView *svp,
 constexpr int GenBase(int g) { return g & 3; }
 constexpr bool GenDefer(int g) { return (g & 4) != 0; }
 constexpr bool GenAnim(int g) { return (g & 8) != 0; }
+constexpr int GenX(int gen, bool defer, bool anim) { return gen | (defer ? 4 : 0) | (anim ? 8 : 0); }   // (the host packs a template value here only: PickWalkKernels)
 template <typename Fetch, int GEN, bool DEFER = false, bool ANIM = false>
 struct GeneralPrims {
     static constexpr bool pairBands = GEN >= 2;   // quadrics / patches / curves in the scene: the near-tie band depends on the pair (wf_traverse.h)
@@ -684,6 +699,7 @@ __device__ inline void BatchTrace(const SceneView &sv, const FastBVH &bvh, int n
             LeafPhase<ANY, GEN, INST>(sv, bvh, w, st, fetch, idx);
         }
         if constexpr (!ANY && RetraceInline(GenBase(GEN))) {
+            static_assert(ANY || !GenDefer(GEN), "the inline re-walk's `w.route = rh.route` would drop WALK_DEFER: the handing-over variants must walk with BatchTraceRefill");
             if (valid && WalkAmbiguous(w)) {
                 V3 o, d;
                 float t0;
@@ -715,7 +731,7 @@ __device__ inline void BatchTrace(const SceneView &sv, const FastBVH &bvh, int n
 #ifndef WF_GUIDED_DIV
 #define WF_GUIDED_DIV 4
 #endif
-template <bool ANY, int GEN, bool INST = false, bool DEFER = false, typename Fetch, typename Finish>
+template <bool ANY, int GEN, bool INST = false, bool DRAIN = false, typename Fetch, typename Finish>
 __device__ inline void BatchTraceRefill(const SceneView &sv, const FastBVH &bvh, int n, LdsStackT &st, Fetch fetch, Finish finish, int *cursor = nullptr, int chunk = 4,
                                         int workBlocks = 0) {
     if (workBlocks <= 0) workBlocks = (int)gridDim.x;   // (the first workBlocks workgroups of the grid walk rays; the rest, if any, have another job)
@@ -741,7 +757,7 @@ __device__ inline void BatchTraceRefill(const SceneView &sv, const FastBVH &bvh,
     w.inst = w.curInst = -1;
     WalkStats ws_;
     auto retire = [&]() {
-        // (a closest-hit walk here never re-walks a near tie itself: with DEFER `finish` queues the ray and the kernel resolves it after its
+        // (a closest-hit walk here never re-walks a near tie itself: with DRAIN `finish` queues the ray and the kernel resolves it after its
         //  walks (DrainRetrace), otherwise the separate re-trace launch does.  The reference-order walk inlined HERE cost the closest-hit
         //  kernel 37 %: 76.9 vs 56.0 ms per 16 spp on the spec scene; without it the refill gains 28 %, 40.3 ms)
         finish(idx, true, w);
@@ -812,18 +828,19 @@ __device__ inline void BatchTraceRefill(const SceneView &sv, const FastBVH &bvh,
     ws_.flush(st.dbg, ANY ? 1 : 0);
     if (idx >= 0) retire();   // the rays still held when the queue ran out
 }
-// Which walk a launch takes.  Every PERLANE launch (`finish` has no workgroup barrier: every caller but the workgroup-routed closest-hit
-// variant, SPLIT = false) walks with refill:
-//   any-hit: spec scene, 16 spp, same box (round 3): 30.1 -> 25.2 ms at a threshold of 40 lanes, 26.2 at 24, 27.5 at 12;
-//   closest-hit with the near-tie walk out of the loop (DEFER: the caller queues near-tie rays in `finish` and drains the queue itself
-//   after this returns, DrainRetrace): 56.0 -> see DESIGN 4.1;
+// Which walk a launch takes (`finish` is a per-lane store in every caller: no workgroup barrier).  A walk whose near ties are resolved
+// outside its loop walks with refill:
+//   any-hit (no near ties): spec scene, 16 spp, same box (round 3): 30.1 -> 25.2 ms at a threshold of 40 lanes, 26.2 at 24, 27.5 at 12;
+//   closest-hit with DRAIN (the caller queues near-tie rays in `finish` and drains the queue itself after this returns, DrainRetrace):
+//   56.0 -> see DESIGN 4.1;
 //   closest-hit of scenes with general primitives (GEN >= 2, whose near ties go to the separate re-trace launch): spec scene + one
 //   sphere, 73.4 -> 64.6 ms (profiles/r04_one_sphere_refill_ab_sm16.txt).
-// The other closest-hit launches walk with BatchTrace, which re-walks near ties inline.
-template <bool ANY, int GEN, bool INST, bool PERLANE, bool DEFER = false, typename Fetch, typename Finish>
+// What remains — a closest-hit walk of triangles (GEN <= 1) whose caller does not drain: k_tr_trace, k_trace_closest_fast — walks with
+// BatchTrace, which re-walks near ties inline.
+template <bool ANY, int GEN, bool INST, bool DRAIN = false, typename Fetch, typename Finish>
 __device__ inline void TraceQueue(const SceneView &sv, const FastBVH &bvh, int n, LdsStackT &st, Fetch fetch, Finish finish, int *cursor = nullptr, int chunk = 4,
                                   int workBlocks = 0) {
-    if constexpr (PERLANE && (ANY || DEFER || !RetraceInline(GenBase(GEN)))) BatchTraceRefill<ANY, GEN, INST, DEFER>(sv, bvh, n, st, fetch, finish, cursor, chunk, workBlocks);
+    if constexpr (ANY || DRAIN || !RetraceInline(GenBase(GEN))) BatchTraceRefill<ANY, GEN, INST, DRAIN>(sv, bvh, n, st, fetch, finish, cursor, chunk, workBlocks);
     else BatchTrace<ANY, GEN, INST>(sv, bvh, n, st, fetch, finish, cursor, chunk);
 }
 // The near-tie rays of a closest-hit launch, resolved inside the launch (round 3, second step).  A walk that ends on a near-tie publishes
@@ -921,10 +938,8 @@ __device__ inline void DrainRetrace(const SceneView &sv, const WorkState &ws, co
     }
 }
 
-// SPLIT = false: a workgroup routes its 256 hits together at the end of every batch (KRouteHitBlock: one atomic per destination queue
-// per workgroup) — its four waves wait for the slowest walk of the 256.  SPLIT = true: the walk only records the hit (ws.hit, hitInst,
-// hitT, routeCode) and k_route_hits pushes the queue entries afterwards in one streaming pass; waves never meet, so a wave whose 64
-// walks are done moves on to its next 64 rays while the others still walk.
+// The walk only records the hit (ws.hit, hitInst, hitT, routeCode) and k_route_hits pushes the queue entries afterwards in one streaming
+// pass; waves never meet, so a wave whose 64 walks are done moves on to its next 64 rays while the others still walk.
 constexpr uint32_t ROUTE_SKIP = 0x80000000u;   // near-tie: the re-trace routes this ray
 // The occupancy target of a walk kernel.  The general-primitive variants (GEN >= 2) cannot reach the triangle kernels' 4-5 waves, but the
 // target still matters: the allocator spills towards it before the callees' frames are added (asked for 3 / 2 waves, which they could
@@ -937,20 +952,19 @@ constexpr uint32_t ROUTE_SKIP = 0x80000000u;   // near-tie: the re-trace routes 
 constexpr int TWavesFor(int gen, int triangleWaves) { return gen == 3 ? 2 : triangleWaves; }
 // GENX: 0 - 3 as above; 4 / 5 = GEN 0 / 1 handing rays that meet a quadric / patch / curve to `deferQ` (TWO-CLASS TRAVERSAL).
 // list != nullptr: walk the rays list[0 .. counters[CNT_DEFER]) of the queue instead of all of it (the second launch of that scheme).
-template <int GENX, bool INST = false, bool SPLIT = false>
+template <int GENX, bool INST = false>
 __global__ void __launch_bounds__(TBLOCK, TWavesFor(GenBase(GENX), INST ? WF_TWAVES_INST : WF_TWAVES_CLOSEST)) k_closest_fast(const SceneView svArg, WorkState ws, FastBVH bvh, int cur, SpillArea sp, int *cursor = nullptr, int chunk = 4, const int *list = nullptr) {
     constexpr int GEN = GenBase(GENX);
     const SceneView &sv = SvOf<false>(svArg);
-    if constexpr (!SPLIT) list = nullptr;   // (only the launches of the routing-split path take a list)
     const int n = list ? ws.counters[(CNT_DEFER) * CNT_STRIDE] : ws.counters[(CNT_RAY0 + cur) * CNT_STRIDE];
     const int gtid = blockIdx.x * TBLOCK + threadIdx.x, stride = gridDim.x * TBLOCK;
     LdsStackT st{sp.base + gtid, stride, 0, 0, sp.rows, sp.dbg};
     const RayQueueV q = ws.rq[cur];
     // near-ties resolved by this launch itself: the kernels that would otherwise inline the reference-order walk (RetraceInline), walking with refill
-    constexpr bool DRAIN = SPLIT && RetraceInline(GEN);
+    constexpr bool DRAIN = RetraceInline(GEN);
     const int workBlocks = DRAIN ? (int)gridDim.x - ServiceBlocks() : (int)gridDim.x;
     if (DRAIN && (int)blockIdx.x >= workBlocks) { DrainRetrace<GEN, INST, GenAnim(GENX)>(sv, ws, bvh, cur, st, true); return; }   // a service workgroup
-    TraceQueue<false, GENX, INST, SPLIT, DRAIN>(
+    TraceQueue<false, GENX, INST, DRAIN>(
         sv, bvh, n, st,
         [&](int i0, V3 *o, V3 *d, float *tMax) {
             const int i = list ? list[i0] : i0;
@@ -963,7 +977,7 @@ __global__ void __launch_bounds__(TBLOCK, TWavesFor(GenBase(GENX), INST ? WF_TWA
         },
         [&](int i0, bool valid, const RayWalk &w) {
             const int i = (list && valid) ? list[i0] : i0;
-            if constexpr (GenDefer(GENX) && SPLIT)
+            if constexpr (GenDefer(GENX))
                 if (valid && (w.route & WALK_DEFER)) {   // the general-primitive launch walks this ray (and writes its record)
                     ws.deferQ[QueueAlloc(&ws.counters[(CNT_DEFER) * CNT_STRIDE])] = i;
                     ws.routeCode[i] = ROUTE_SKIP;
@@ -984,25 +998,22 @@ __global__ void __launch_bounds__(TBLOCK, TWavesFor(GenBase(GENX), INST ? WF_TWA
                     ws.hit[i] = F4{0, bound, 0, 0};
                 }
             }
-            if constexpr (SPLIT) {
-                if (!valid) return;
-                ws.routeCode[i] = amb ? ROUTE_SKIP : (uint32_t)w.route;
-                if (amb) return;
-                ws.hit[i] = F4{BitsToFloat((uint32_t)w.prim), w.b0, w.b1, w.b2};
-                if (INST) ws.hitInst[i] = w.prim >= 0 ? w.inst : -1;
-                if (sv.haveMedia) ws.hitT[i] = w.prim >= 0 ? WalkT(w) : WF_INFINITY;
-            } else
-            KRouteHitBlock<(GEN > 1) || INST, GenAnim(GENX)>(sv, ws, cur, i, valid && !amb, w.prim, w.route, WalkT(w), w.b0, w.b1, w.b2, INST ? w.inst : -1);
-        }, SPLIT ? cursor : nullptr, chunk, workBlocks);
+            if (!valid) return;
+            ws.routeCode[i] = amb ? ROUTE_SKIP : (uint32_t)w.route;
+            if (amb) return;
+            ws.hit[i] = F4{BitsToFloat((uint32_t)w.prim), w.b0, w.b1, w.b2};
+            if (INST) ws.hitInst[i] = w.prim >= 0 ? w.inst : -1;
+            if (sv.haveMedia) ws.hitT[i] = w.prim >= 0 ? WalkT(w) : WF_INFINITY;
+        }, cursor, chunk, workBlocks);
     if constexpr (DRAIN) DrainRetrace<GEN, INST, GenAnim(GENX)>(sv, ws, bvh, cur, st, false);
 }
-// the routing pass of the SPLIT traversal: EnqueueWorkAfterIntersection / Miss for every ray of the queue (block-aggregated pushes)
+// the routing pass of the closest-hit traversal: EnqueueWorkAfterIntersection / Miss for every ray of the queue (block-aggregated pushes)
 // (1024 threads per workgroup: one returning atomic per destination queue per 1024 rays — a queue counter sustains ~88 of them per
 // microsecond, which at 256 rays per workgroup was the whole cost of this pass)
 constexpr int RBLOCK = 1024;
 // ANIM: the scene has animated primitives (the interface skip rebuilds the hit's interaction at the ray's time).  That variant takes
 // workgroups of BLOCK threads: the interpolation is an out-of-line callee shared with the ANIM walk kernels, and a 1024-thread caller
-// would cap its registers at 128 for all of them (measured: k_closest_fast<8, true, true> 162 -> 128 VGPRs, its spills 104 -> 183).
+// would cap its registers at 128 for all of them (measured: k_closest_fast<8, true> 162 -> 128 VGPRs, its spills 104 -> 183).
 constexpr int RouteBlock(bool anim) { return anim ? BLOCK : RBLOCK; }
 template <bool GENERAL, bool ANIM = false>
 __global__ void __launch_bounds__(RouteBlock(ANIM)) k_route_hits(const SceneView svArg, WorkState ws, int cur) {
@@ -1087,7 +1098,7 @@ __global__ void __launch_bounds__(TBLOCK, TWavesFor(GenBase(GEN), INST ? WF_TWAV
     const int n = list ? ws.counters[(CNT_DEFER_SHADOW) * CNT_STRIDE] : ws.counters[(CNT_SHADOW) * CNT_STRIDE];
     const int gtid = blockIdx.x * TBLOCK + threadIdx.x, stride = gridDim.x * TBLOCK;
     LdsStackT st{sp.base + gtid, stride, 0, 0, sp.rows, sp.dbg};
-    TraceQueue<true, GEN, INST, true>(
+    TraceQueue<true, GEN, INST>(
         sv, bvh, n, st,
         [&](int i0, V3 *o, V3 *d, float *tMax) {
             const int i = list ? list[i0] : i0;
@@ -1112,7 +1123,7 @@ template <int GEN, bool INST>
 __global__ void __launch_bounds__(TBLOCK) k_trace_closest_fast(const SceneView sv, FastBVH bvh, int n, const float *rays, wf_hit_record *out, SpillArea sp) {
     const int gtid = blockIdx.x * TBLOCK + threadIdx.x, stride = gridDim.x * TBLOCK;
     LdsStackT st{sp.base + gtid, stride, 0, 0, sp.rows, sp.dbg};
-    TraceQueue<false, GEN, INST, true>(
+    TraceQueue<false, GEN, INST>(
         sv, bvh, n, st,
         [&](int i, V3 *o, V3 *d, float *tMax) {
             const float *r = rays + (size_t)7 * i;
@@ -1133,7 +1144,7 @@ template <int GEN, bool INST>
 __global__ void __launch_bounds__(TBLOCK) k_trace_any_fast(const SceneView sv, FastBVH bvh, int n, const float *rays, int32_t *occluded, SpillArea sp) {
     const int gtid = blockIdx.x * TBLOCK + threadIdx.x, stride = gridDim.x * TBLOCK;
     LdsStackT st{sp.base + gtid, stride, 0, 0, sp.rows, sp.dbg};
-    TraceQueue<true, GEN, INST, true>(
+    TraceQueue<true, GEN, INST>(
         sv, bvh, n, st,
         [&](int i, V3 *o, V3 *d, float *tMax) {
             const float *r = rays + (size_t)7 * i;
@@ -1261,7 +1272,7 @@ __global__ void __launch_bounds__(TBLOCK, INST ? WF_TWAVES_INST : WF_TWAVES_CLOS
     const int gtid = blockIdx.x * TBLOCK + threadIdx.x, stride = gridDim.x * TBLOCK;
     LdsStackT st{sp.base + gtid, stride, 0, 0, sp.rows, sp.dbg};
     const int32_t *q = ws.trQ[cur];
-    TraceQueue<false, GEN, INST, true>(
+    TraceQueue<false, GEN, INST>(
         sv, bvh, n, st,
         [&](int j, V3 *o, V3 *d, float *tMax) {
             const int i = q[j];
@@ -1323,22 +1334,30 @@ __global__ void __launch_bounds__(BLOCK) k_handle_emissive(const SceneView svArg
     for (int i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) KHandleEmissive(sv, ws, cur, i);
 }
 // the material kernels live in wf_mat.hip (one translation unit per material type)
-extern "C" {
+// the material types that have kernels (wf_material_type 1 .. WF_MAT_NTYPES - 1): the one list the declarations and tables below are made from
+#define WF_MAT_TYPES(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10)
 // the two halves of the material stage (wf_mat.hip): shade variant 0 | 1 (lean) | 2 | 3, next-event estimation variant 0 | 1
-#define WF_DECL_SPLIT(n) void wf_launch_mat_shade_##n##_0(hipStream_t, int, const SceneView *, const WorkState *, int); \
-                         void wf_launch_mat_shade_##n##_1(hipStream_t, int, const SceneView *, const WorkState *, int); \
-                         void wf_launch_mat_shade_##n##_2(hipStream_t, int, const SceneView *, const WorkState *, int); \
-                         void wf_launch_mat_shade_##n##_3(hipStream_t, int, const SceneView *, const WorkState *, int); \
-                         void wf_launch_mat_nee_##n##_0(hipStream_t, int, const SceneView *, const WorkState *); \
-                         void wf_launch_mat_nee_##n##_1(hipStream_t, int, const SceneView *, const WorkState *);
-WF_DECL_SPLIT(1) WF_DECL_SPLIT(2) WF_DECL_SPLIT(3) WF_DECL_SPLIT(4) WF_DECL_SPLIT(5) WF_DECL_SPLIT(6) WF_DECL_SPLIT(7) WF_DECL_SPLIT(8) WF_DECL_SPLIT(9) WF_DECL_SPLIT(10)
+using MatShadeFn = void (*)(hipStream_t, int, const SceneView *, const WorkState *, int);
+using MatNeeFn = void (*)(hipStream_t, int, const SceneView *, const WorkState *);
+extern "C" {
+#define WF_MAT_DECL(n) void wf_launch_mat_shade_##n##_0(hipStream_t, int, const SceneView *, const WorkState *, int); \
+                       void wf_launch_mat_shade_##n##_1(hipStream_t, int, const SceneView *, const WorkState *, int); \
+                       void wf_launch_mat_shade_##n##_2(hipStream_t, int, const SceneView *, const WorkState *, int); \
+                       void wf_launch_mat_shade_##n##_3(hipStream_t, int, const SceneView *, const WorkState *, int); \
+                       void wf_launch_mat_nee_##n##_0(hipStream_t, int, const SceneView *, const WorkState *); \
+                       void wf_launch_mat_nee_##n##_1(hipStream_t, int, const SceneView *, const WorkState *);
+WF_MAT_TYPES(WF_MAT_DECL)
 }
+#define WF_MAT_SHADE_ROW(n) {wf_launch_mat_shade_##n##_0, wf_launch_mat_shade_##n##_1, wf_launch_mat_shade_##n##_2, wf_launch_mat_shade_##n##_3},
+#define WF_MAT_NEE_ROW(n) {wf_launch_mat_nee_##n##_0, wf_launch_mat_nee_##n##_1},
+static const MatShadeFn kMatShade[WF_MAT_NTYPES][4] = {{}, WF_MAT_TYPES(WF_MAT_SHADE_ROW)};   // [type][shade variant]; row 0: WF_MAT_INTERFACE has no kernel
+static const MatNeeFn kMatNee[WF_MAT_NTYPES][2] = {{}, WF_MAT_TYPES(WF_MAT_NEE_ROW)};         // [type][rare lights]
 // bytes of one NeeItem's BxDF (wf_kernels.h) -> 16-byte planes of the record between the two kernels (wf_mat.hip: NeeIO)
 template <int MAT> constexpr int NeePlanesOf() { return 10 + (int)((sizeof(typename MatBxDF<MAT>::T) + 15) / 16); }
 static int NeePlanes(int m) {
     switch (m) {
-    case 1: return NeePlanesOf<1>(); case 2: return NeePlanesOf<2>(); case 3: return NeePlanesOf<3>(); case 4: return NeePlanesOf<4>(); case 5: return NeePlanesOf<5>();
-    case 6: return NeePlanesOf<6>(); case 7: return NeePlanesOf<7>(); case 8: return NeePlanesOf<8>(); case 9: return NeePlanesOf<9>(); case 10: return NeePlanesOf<10>();
+#define WF_MAT_PLANES(n) case n: return NeePlanesOf<n>();
+    WF_MAT_TYPES(WF_MAT_PLANES)
     }
     return 0;
 }
@@ -1490,33 +1509,7 @@ struct Prof {
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(BLOCK), 0, ctx->stream, __VA_ARGS__);  \
     } while (0)
 
-// launch KERNEL<GEN, INST> (or <INST, GEN> for the host-ray probes: ORDER = 1) for the context's scene
-#define LAUNCHT_VARIANT(name, KERNEL, ORDER, ...)                                                              \
-    do {                                                                                                       \
-        const int gen_ = ctx->genMode;                                                                         \
-        const bool inst_ = ctx->svHost.nInstances > 0;                                                         \
-        if (ORDER == 0) {                                                                                      \
-            if (inst_) { if (gen_ == 0) LAUNCHT(name, (KERNEL<0, true>), __VA_ARGS__); else if (gen_ == 1) LAUNCHT(name, (KERNEL<1, true>), __VA_ARGS__); else if (gen_ == 2) LAUNCHT(name, (KERNEL<2, true>), __VA_ARGS__); else LAUNCHT(name, (KERNEL<3, true>), __VA_ARGS__); } \
-            else { if (gen_ == 0) LAUNCHT(name, (KERNEL<0, false>), __VA_ARGS__); else if (gen_ == 1) LAUNCHT(name, (KERNEL<1, false>), __VA_ARGS__); else if (gen_ == 2) LAUNCHT(name, (KERNEL<2, false>), __VA_ARGS__); else LAUNCHT(name, (KERNEL<3, false>), __VA_ARGS__); } \
-        }                                                                                                      \
-    } while (0)
-// ... and with the variant given (GENV = 0 .. 3, or 4 / 5: the handing-over triangle kernels of the two-class traversal)
-#define LAUNCHT_VARIANT_GEN(name, KERNEL, GENV, ...)                                                           \
-    do {                                                                                                       \
-        const int gen_ = (GENV);                                                                               \
-        const bool inst_ = ctx->svHost.nInstances > 0;                                                         \
-        if (inst_) { if (gen_ == 0) LAUNCHT(name, (KERNEL<0, true>), __VA_ARGS__); else if (gen_ == 1) LAUNCHT(name, (KERNEL<1, true>), __VA_ARGS__); else if (gen_ == 2) LAUNCHT(name, (KERNEL<2, true>), __VA_ARGS__); else if (gen_ == 3) LAUNCHT(name, (KERNEL<3, true>), __VA_ARGS__); else if (gen_ == 4) LAUNCHT(name, (KERNEL<4, true>), __VA_ARGS__); else if (gen_ == 5) LAUNCHT(name, (KERNEL<5, true>), __VA_ARGS__); else if (gen_ == 8) LAUNCHT(name, (KERNEL<8, true>), __VA_ARGS__); else LAUNCHT(name, (KERNEL<9, true>), __VA_ARGS__); } \
-        else { if (gen_ == 0) LAUNCHT(name, (KERNEL<0, false>), __VA_ARGS__); else if (gen_ == 1) LAUNCHT(name, (KERNEL<1, false>), __VA_ARGS__); else if (gen_ == 2) LAUNCHT(name, (KERNEL<2, false>), __VA_ARGS__); else if (gen_ == 3) LAUNCHT(name, (KERNEL<3, false>), __VA_ARGS__); else if (gen_ == 4) LAUNCHT(name, (KERNEL<4, false>), __VA_ARGS__); else LAUNCHT(name, (KERNEL<5, false>), __VA_ARGS__); } \
-    } while (0)
-// the closest-hit walk with the routing split off (ctx->splitRoute)
-#define LAUNCHT_CLOSEST_SPLIT(name, ...) LAUNCHT_CLOSEST_SPLIT_GEN(name, ctx->genMode, __VA_ARGS__)
-#define LAUNCHT_CLOSEST_SPLIT_GEN(name, GENV, ...)                                                             \
-    do {                                                                                                       \
-        const int gen_ = (GENV);                                                                               \
-        const bool inst_ = ctx->svHost.nInstances > 0;                                                         \
-        if (inst_) { if (gen_ == 0) LAUNCHT(name, (k_closest_fast<0, true, true>), __VA_ARGS__); else if (gen_ == 1) LAUNCHT(name, (k_closest_fast<1, true, true>), __VA_ARGS__); else if (gen_ == 2) LAUNCHT(name, (k_closest_fast<2, true, true>), __VA_ARGS__); else if (gen_ == 3) LAUNCHT(name, (k_closest_fast<3, true, true>), __VA_ARGS__); else if (gen_ == 4) LAUNCHT(name, (k_closest_fast<4, true, true>), __VA_ARGS__); else if (gen_ == 5) LAUNCHT(name, (k_closest_fast<5, true, true>), __VA_ARGS__); else if (gen_ == 8) LAUNCHT(name, (k_closest_fast<8, true, true>), __VA_ARGS__); else LAUNCHT(name, (k_closest_fast<9, true, true>), __VA_ARGS__); } \
-        else { if (gen_ == 0) LAUNCHT(name, (k_closest_fast<0, false, true>), __VA_ARGS__); else if (gen_ == 1) LAUNCHT(name, (k_closest_fast<1, false, true>), __VA_ARGS__); else if (gen_ == 2) LAUNCHT(name, (k_closest_fast<2, false, true>), __VA_ARGS__); else if (gen_ == 3) LAUNCHT(name, (k_closest_fast<3, false, true>), __VA_ARGS__); else if (gen_ == 4) LAUNCHT(name, (k_closest_fast<4, false, true>), __VA_ARGS__); else LAUNCHT(name, (k_closest_fast<5, false, true>), __VA_ARGS__); } \
-    } while (0)
+// a walk kernel (workgroups of TBLOCK threads), usually one of ctx->walk on its resident grid
 #define LAUNCHT(name, kernel, grid, ...)                                                   \
     do {                                                                                   \
         Prof prof_(ctx, name);                                                             \
@@ -2207,6 +2200,61 @@ bool HitsClearly(const double o[3], const double dir[3], const float *p0, const 
 }
 }  // namespace
 
+// ---- the scene's walk kernels (WalkKernels) --------------------------------------------------------------------------------------
+// the walk kernel templates as types, so that one function maps run-time values onto their instantiations
+struct ClosestWalk { using Fn = ClosestWalkFn; template <int G, bool I> static Fn of() { return k_closest_fast<G, I>; } };
+struct ShadowWalk { using Fn = ShadowWalkFn; template <int G, bool I> static Fn of() { return k_shadow_fast<G, I>; } };
+struct TrTraceWalk { using Fn = TrTraceFn; template <int G, bool I> static Fn of() { return k_tr_trace<G, I>; } };
+struct TraceClosestWalk { using Fn = TraceClosestFn; template <int G, bool I> static Fn of() { return k_trace_closest_fast<G, I>; } };
+struct TraceAnyWalk { using Fn = TraceAnyFn; template <int G, bool I> static Fn of() { return k_trace_any_fast<G, I>; } };
+// K<G, inst> for the G of the pack that equals genx; null if there is none.  The packs handed in are the variants the library holds —
+// a pair that appears nowhere here is not compiled.  The ANIM variants (GenAnim) exist two-level only: an animated shape is an instance.
+template <typename K, bool INST, int G>
+static typename K::Fn WalkVariant() {
+    if constexpr (GenAnim(G) && !INST) return nullptr;
+    else return K::template of<G, INST>();
+}
+template <typename K, int... G>
+static typename K::Fn PickWalk(int genx, bool inst, std::integer_sequence<int, G...>) {
+    typename K::Fn f = nullptr;
+    ((genx == G ? (void)(f = inst ? WalkVariant<K, true, G>() : WalkVariant<K, false, G>()) : (void)0), ...);
+    return f;
+}
+static int PickWalkKernels(wf_ctx *ctx) {
+    using QueueWalks = std::integer_sequence<int, 0, 1, 2, 3, GenX(0, true, false), GenX(1, true, false), GenX(0, false, true), GenX(1, false, true)>;
+    const bool inst = ctx->svHost.nInstances > 0;
+    const int gen = ctx->genMode;
+    // what every ray of a queue walks through: the triangle kernel that hands general primitives over, or the scene's one kernel
+    const int first = ctx->deferGeneral ? GenX(ctx->genTri, true, false) : GenX(gen, false, ctx->animFast);
+    WalkKernels k;
+    k.closest = PickWalk<ClosestWalk>(first, inst, QueueWalks{});
+    k.shadow = PickWalk<ShadowWalk>(first, inst, QueueWalks{});
+    if (ctx->deferGeneral) {
+        k.closestGen = PickWalk<ClosestWalk>(gen, inst, QueueWalks{});
+        k.shadowGen = PickWalk<ShadowWalk>(gen, inst, QueueWalks{});
+    }
+    k.traceClosest = PickWalk<TraceClosestWalk>(gen, inst, std::integer_sequence<int, 0, 1, 2, 3>{});
+    k.traceAny = PickWalk<TraceAnyWalk>(gen, inst, std::integer_sequence<int, 0, 1, 2, 3>{});
+    if (RetraceInline(gen)) k.trTrace = PickWalk<TrTraceWalk>(gen, inst, std::integer_sequence<int, 0, 1>{});   // (resolves its near ties inside the walk)
+    if (!k.closest || !k.shadow || !k.traceClosest || !k.traceAny || (ctx->deferGeneral && (!k.closestGen || !k.shadowGen)) || (RetraceInline(gen) && !k.trTrace))
+        return fail(-1, "no walk kernel for this scene (genMode %d, genTri %d, two-class %d, animated %d, instances %d)", gen, ctx->genTri, (int)ctx->deferGeneral, (int)ctx->animFast, (int)inst);
+    // resident workgroups of the queue walks (closest-hit and shadow differ in registers)
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, ctx->device));
+    const int maxG = MAX_GRID * BLOCK / TBLOCK;  // stackSpill is sized for MAX_GRID * BLOCK threads
+    auto residentGrid = [&](auto kernel, int *out) {
+        int perCU = 0;
+        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, (const void *)kernel, TBLOCK, 0));
+        *out = std::min(maxG, std::max(1, perCU) * prop.multiProcessorCount);
+        return 0;
+    };
+    int e;
+    if ((e = residentGrid(k.closest, &k.grid)) || (e = residentGrid(k.shadow, &k.gridShadow))) return e;
+    if (ctx->deferGeneral && ((e = residentGrid(k.closestGen, &k.gridGen)) || (e = residentGrid(k.shadowGen, &k.gridShadowGen)))) return e;
+    ctx->walk = k;
+    return 0;
+}
+
 extern "C" {
 
 const char *wf_last_error(void) { return g_err; }
@@ -2309,9 +2357,6 @@ int wf_ctx_create(int device, wf_ctx **out) {
     HIPCHK(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
     HIPCHK(hipEventCreateWithFlags(&c->evFork, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&c->evJoin, hipEventDisableTiming));
-    if (const char *e = getenv("WF_OVERLAP_RETRACE")) c->overlapRetrace = atoi(e);
-    if (const char *e = getenv("WF_MAT_STREAMS")) c->matStreams = atoi(e);
-    HIPCHK(hipEventCreateWithFlags(&c->evMatFork, hipEventDisableTiming));
     c->traceLaunch = getenv("WF_TRACE_LAUNCH") != nullptr;
     if (const char *e = getenv("WF_SCRATCH_PRIME"); !e || atoi(e) != 0) {
         int *tmp = nullptr;
@@ -2337,11 +2382,6 @@ int wf_ctx_destroy(wf_ctx *ctx) {
     if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
     if (ctx->evFork) (void)hipEventDestroy(ctx->evFork);
     if (ctx->evJoin) (void)hipEventDestroy(ctx->evJoin);
-    if (ctx->evMatFork) (void)hipEventDestroy(ctx->evMatFork);
-    for (int m = 0; m < WF_MAT_NTYPES; ++m) {
-        if (ctx->matStream[m]) (void)hipStreamDestroy(ctx->matStream[m]);
-        if (ctx->evMatJoin[m]) (void)hipEventDestroy(ctx->evMatJoin[m]);
-    }
     delete ctx;
     return 0;
 }
@@ -2641,13 +2681,12 @@ int wf_scene_upload(wf_ctx *ctx, const wf_scene_desc *d) {
                     alphaGen = std::max(alphaGen, ((tt == WF_TEX_FLOAT_CONSTANT || tt == WF_TEX_FLOAT_IMAGE || tt == WF_TEX_FLOAT_BILERP) && lean) ? 1 : 2);
                 }
             ctx->genMode = std::max(ctx->genMode, alphaGen);
-            if (getenv("WF_GEN_MODE")) ctx->genMode = std::max(ctx->genMode, atoi(getenv("WF_GEN_MODE")));  // timing experiments: force the general variant
             // TWO-CLASS TRAVERSAL: the scene's quadrics / patches / curves are few beside its triangles, and the triangles themselves need no
             // more than the simple alpha test — the triangle kernels walk first, the general kernels only the rays handed over
             // (WF_DEFER_GENERAL=1 | 0 forces / forbids it for any scene with such shapes)
             ctx->genTri = std::min(alphaGen, 1);
             ctx->deferGeneral = false;
-            if (d->n_quadrics > 0 && alphaGen <= 1 && ctx->genMode >= 2 && wf_ctx::splitRouteWanted()) {
+            if (d->n_quadrics > 0 && alphaGen <= 1 && ctx->genMode >= 2) {
                 const bool few = (int64_t)d->n_quadrics * 16 <= (int64_t)d->n_triangles;
                 ctx->deferGeneral = getenv("WF_DEFER_GENERAL") ? atoi(getenv("WF_DEFER_GENERAL")) != 0 : few;
             }
@@ -2692,44 +2731,11 @@ int wf_scene_upload(wf_ctx *ctx, const wf_scene_desc *d) {
             if ((e = devUpload(ctx, &ctx->fast.subs, fsubs.data(), fsubs.size()))) return e;
             // rays of a scene whose trees do not fit the caches walk long enough for one cursor fetch per 64 rays (measured: -3 % on
             // the 10 M-triangle scene); a cache-resident scene traces so fast that the cursor's atomics would bound it (see cursorChunk)
-            if (!getenv("WF_CURSOR_CHUNK")) {
-                const bool big = qn.size() * sizeof(QNode) + lt.size() * sizeof(LeafTri) > ((size_t)256 << 20);
-                ctx->cursorChunk = big ? 3 : 2;
-                ctx->cursorChunkShadow = big ? 1 : 2;
-            }
+            const bool big = qn.size() * sizeof(QNode) + lt.size() * sizeof(LeafTri) > ((size_t)256 << 20);
+            ctx->cursorChunk = big ? 3 : 2;
+            ctx->cursorChunkShadow = big ? 1 : 2;
             ctx->fast.instances = ctx->svHost.instances;
             HIPCHK(hipStreamSynchronize(ctx->stream));
-        }
-        // resident workgroups of the traversal kernel variants this scene launches (closest-hit and shadow differ in registers)
-        hipDeviceProp_t prop;
-        HIPCHK(hipGetDeviceProperties(&prop, ctx->device));
-        const int maxG = MAX_GRID * BLOCK / TBLOCK;  // stackSpill is sized for MAX_GRID * BLOCK threads
-        auto residentGrid = [&](const void *kernel, int *out) {
-            int perCU = 0;
-            HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, TBLOCK, 0));
-            int g = std::max(1, perCU) * prop.multiProcessorCount;
-            if (const char *m = getenv("WF_PGRID_MULT")) g = (int)(g * atof(m));
-            *out = g > maxG ? maxG : (g < 1 ? 1 : g);
-            return 0;
-        };
-        {
-            const int gen = ctx->genMode;
-            const bool inst = ctx->svHost.nInstances > 0, split = ctx->splitRouteWanted();
-            const void *kc, *ks;
-#define WF_PICK(K, ...) (inst ? (gen == 0 ? (const void *)K<0, true __VA_ARGS__> : gen == 1 ? (const void *)K<1, true __VA_ARGS__> : gen == 2 ? (const void *)K<2, true __VA_ARGS__> : (const void *)K<3, true __VA_ARGS__>) \
-                              : (gen == 0 ? (const void *)K<0, false __VA_ARGS__> : gen == 1 ? (const void *)K<1, false __VA_ARGS__> : gen == 2 ? (const void *)K<2, false __VA_ARGS__> : (const void *)K<3, false __VA_ARGS__>))
-            (void)split;
-            kc = WF_PICK(k_closest_fast, , true);
-            ks = WF_PICK(k_shadow_fast);
-#undef WF_PICK
-            if ((e = residentGrid(kc, &ctx->persistentGrid)) || (e = residentGrid(ks, &ctx->persistentGridShadow))) return e;
-            if (ctx->deferGeneral) {
-                ctx->persistentGridGen = ctx->persistentGrid; ctx->persistentGridShadowGen = ctx->persistentGridShadow;
-                const bool t1 = ctx->genTri == 1;
-                kc = inst ? (t1 ? (const void *)k_closest_fast<5, true, true> : (const void *)k_closest_fast<4, true, true>) : (t1 ? (const void *)k_closest_fast<5, false, true> : (const void *)k_closest_fast<4, false, true>);
-                ks = inst ? (t1 ? (const void *)k_shadow_fast<5, true> : (const void *)k_shadow_fast<4, true>) : (t1 ? (const void *)k_shadow_fast<5, false> : (const void *)k_shadow_fast<4, false>);
-                if ((e = residentGrid(kc, &ctx->persistentGrid)) || (e = residentGrid(ks, &ctx->persistentGridShadow))) return e;
-            }
         }
         if (getenv("WF_NO_FAST")) ctx->fastOk = false;
         // AnimatedPrimitive: the production walks' ANIM variants (triangles + simple alpha cut-outs, two-level: an animated shape entity is an
@@ -2737,11 +2743,7 @@ int wf_scene_upload(wf_ctx *ctx, const wf_scene_desc *d) {
         // reference-order walks (WF_ANIM_FAST=0: every animated scene does)
         ctx->animFast = d->n_animated > 0 && ctx->fastOk && ctx->genMode <= 1 && ctx->svHost.nInstances > 0 && !(getenv("WF_ANIM_FAST") && atoi(getenv("WF_ANIM_FAST")) == 0);
         if (d->n_animated > 0 && !ctx->animFast) ctx->fastOk = false;
-        if (ctx->animFast) {
-            const bool g1 = ctx->genMode == 1;
-            if ((e = residentGrid(g1 ? (const void *)k_closest_fast<9, true, true> : (const void *)k_closest_fast<8, true, true>, &ctx->persistentGrid)) ||
-                (e = residentGrid(g1 ? (const void *)k_shadow_fast<9, true> : (const void *)k_shadow_fast<8, true>, &ctx->persistentGridShadow))) return e;
-        }
+        if ((e = PickWalkKernels(ctx))) return e;
         if ((e = devAlloc(ctx, &ctx->probeCursor, (size_t)1))) return e;
     }
     if ((e = devAlloc(ctx, &ctx->ws.film, (size_t)ctx->W * ctx->H * 4))) return e;
@@ -2864,11 +2866,7 @@ int wf_queues_alloc(wf_ctx *ctx, int pixels_per_pass, int samples_per_pass) {
         for (int m = 1; m < WF_MAT_NTYPES; ++m) if (ctx->matPresent[m]) planes = std::max(planes, NeePlanes(m));
         if (planes > 0 && (e = devAlloc(ctx, &ws.neeRec, n * (size_t)planes))) return e;
     }
-    // (round 6: WF_SPLIT_ROUTE=0 — the walk routing its hits per workgroup, the round-2 path — is gone: its kernel variants were the ones that
-    //  kept tripping the spill-carrier lint whenever anything near them changed; 1 = no work cursor, 2 = the default)
-    ctx->splitRoute = getenv("WF_SPLIT_ROUTE") ? std::max(1, atoi(getenv("WF_SPLIT_ROUTE"))) : 2;
-    if (getenv("WF_CURSOR_CHUNK")) ctx->cursorChunk = ctx->cursorChunkShadow = std::max(1, atoi(getenv("WF_CURSOR_CHUNK")));  // (default: chosen at scene upload)
-    if (ctx->splitRoute && (e = devAlloc(ctx, &ws.routeCode, n))) return e;
+    if ((e = devAlloc(ctx, &ws.routeCode, n))) return e;
     ctx->maxQueueSize = max_queue_size;
     ctx->queuesAllocated = true;
     return 0;
@@ -2931,10 +2929,8 @@ int wf_gen_camera_rays(wf_ctx *ctx, int y0, int sample_index) {
     if (ctx->ws.sampleTops) LAUNCH("Sampler index prefixes", k_sample_tops, gridFor(5 * ctx->ws.pixelsPerPass), ctx->svHost, ctx->ws, y0, 0);
     if (ctx->svHost.camera.type == WF_CAMERA_REALISTIC)  // rays blocked by the lenses leave no queue entry: the kernel appends
         LAUNCH("Reset ray queue", k_reset, 1, ctx->ws, 1u << CNT_RAY0, -1, 0);
-    if (ctx->svHost.camera.anim.actually_animated)
-        LAUNCH("Generate camera rays", k_gen_camera_rays<true>, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, y0, sample_index, ctx->passStep, ctx->passSamples);
-    else
-        LAUNCH("Generate camera rays", k_gen_camera_rays<false>, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, y0, sample_index, ctx->passStep, ctx->passSamples);
+    LAUNCH("Generate camera rays", (ctx->svHost.camera.anim.actually_animated ? k_gen_camera_rays<true> : k_gen_camera_rays<false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, y0, sample_index,
+           ctx->passStep, ctx->passSamples);
     LAUNCH("Update camera ray stats", k_reset, 1, ctx->ws, 0u, 0, CNT_RAY0);
     return 0;
 }
@@ -2958,78 +2954,67 @@ int wf_intersect_closest(wf_ctx *ctx, int depth) {
     if (int e = checkReady(ctx)) return e;
     // counting on: the reference-order walk (its visit counts define the algorithmic bytes);
     // otherwise the production traversal (wf_traverse.h)
+    const bool anim = ctx->svHost.haveAnimated;
     if (ctx->countTraversal)
-        { if (ctx->svHost.haveAnimated) LAUNCH("Intersect closest", (k_intersect_closest<true, true>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1, ctx->stackSpill);
-          else LAUNCH("Intersect closest", k_intersect_closest<true>, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1, ctx->stackSpill); }
+        LAUNCH("Intersect closest", (anim ? k_intersect_closest<true, true> : k_intersect_closest<true, false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1, ctx->stackSpill);
     else if (ctx->fastOk) {
-        if (ctx->splitRoute) {
-            int *cursor = nullptr;
-            if (ctx->splitRoute > 1) {
-                // the work cursor starts at 0: zeroed by the stage's "Reset queues" launch (wf_reset_stage_queues) — a memset node of its own
-                // cost a launch's latency per traversal launch (139 fillBuffer launches, 6 ms, in three renders of the spec scene, round 4);
-                // only a caller that launches twice without that reset in between pays for one here
-                cursor = ctx->ws.counters + CNT_CURSOR * CNT_STRIDE;
-                if (ctx->cursorDirty[0]) HIPCHK(hipMemsetAsync(cursor, 0, sizeof(int), ctx->stream));
-                ctx->cursorDirty[0] = true;
-            }
-            ctx->ws.drainEpoch = (ctx->ws.drainEpoch + 1) & 0x7fffffff;   // tag of this launch's near-tie queue entries (DrainRetrace)
-            if (ctx->ws.drainEpoch == 0) ctx->ws.drainEpoch = 1;
-            if (ctx->deferGeneral) {
-                // TWO-CLASS TRAVERSAL: every ray through the triangle kernel; the rays it hands over (deferQ) through the general kernel
-                // (the triangle kernels know one near-tie band: the triangles' own, 2^-20 — the scene-wide band of FastBVH is the wide one of
-                //  the pairs that involve a quadric, which only the general kernel's rays can meet)
-                FastBVH triFast = ctx->fast;
-                triFast.absBand = triFast.absBandTri; triFast.tieRel = triFast.tieRelTri;
-                LAUNCHT_CLOSEST_SPLIT_GEN("Intersect closest", 4 + ctx->genTri, ctx->persistentGrid, ctx->svHost, ctx->ws, triFast, depth & 1, ctx->spillArea(), cursor, ctx->cursorChunk, (const int *)nullptr);
-                LAUNCHT_CLOSEST_SPLIT_GEN("Intersect closest: rays that met a general primitive", ctx->genMode, ctx->persistentGridGen, ctx->svHost, ctx->ws, ctx->fast, depth & 1, ctx->spillArea(), (int *)nullptr, ctx->cursorChunk, (const int *)ctx->ws.deferQ);
-            } else
-            LAUNCHT_CLOSEST_SPLIT_GEN("Intersect closest", ctx->animFast ? 8 + ctx->genMode : ctx->genMode, ctx->persistentGrid, ctx->svHost, ctx->ws, ctx->fast, depth & 1, ctx->spillArea(), cursor, ctx->cursorChunk, (const int *)nullptr);
-            // The near-tie re-trace of the scenes whose walk does not resolve its ties itself (genMode >= 2: quadrics, curves, texture-graph
-            // alpha; RetraceInline) is a handful of long single walks: it runs on a second stream beside the routing pass (and, in the
-            // fused pass, the next sample-generation launch) — they touch disjoint rays and share only the queue counters, through
-            // atomics — and the main stream waits for it before anything consumes the queues.
-            const bool overlap = !RetraceInline(ctx->genMode) && ctx->overlapRetrace && ctx->profile != 1 && !ctx->traceLaunch;   // (the full per-stage profile times every launch on the main stream)
-            if (overlap) {
-                HIPCHK(hipEventRecord(ctx->evFork, ctx->stream));
-                HIPCHK(hipStreamWaitEvent(ctx->stream2, ctx->evFork, 0));
-                hipLaunchKernelGGL(k_closest_retrace, dim3(128), dim3(BLOCK), 0, ctx->stream2, ctx->svHost, ctx->ws, depth & 1, ctx->stackSpill);   // (nothing that runs beside it walks a tree: the spill rows are its own)
-                HIPCHK(hipEventRecord(ctx->evJoin, ctx->stream2));
-                ctx->retracePending = true;
-            }
-            {
-                Prof prof_(ctx, "Route hits");
-                const int g = std::min(MAX_GRID, std::max(1, (ctx->maxQueueSize + RBLOCK - 1) / RBLOCK));
-                if (ctx->svHost.haveAnimated)   // (two-level)
-                    hipLaunchKernelGGL((k_route_hits<true, true>), dim3(std::min(MAX_GRID, std::max(1, (ctx->maxQueueSize + BLOCK - 1) / BLOCK))), dim3(BLOCK), 0, ctx->stream, ctx->svHost, ctx->ws, depth & 1);
-                else if (ctx->genMode > 1 || ctx->svHost.nInstances > 0) hipLaunchKernelGGL(k_route_hits<true>, dim3(g), dim3(RBLOCK), 0, ctx->stream, ctx->svHost, ctx->ws, depth & 1);
-                else hipLaunchKernelGGL(k_route_hits<false>, dim3(g), dim3(RBLOCK), 0, ctx->stream, ctx->svHost, ctx->ws, depth & 1);
-            }
+        const WalkKernels &k = ctx->walk;
+        // the work cursor starts at 0: zeroed by the stage's "Reset queues" launch (wf_reset_stage_queues) — a memset node of its own
+        // cost a launch's latency per traversal launch (139 fillBuffer launches, 6 ms, in three renders of the spec scene, round 4);
+        // only a caller that launches twice without that reset in between pays for one here
+        int *cursor = ctx->ws.counters + CNT_CURSOR * CNT_STRIDE;
+        if (ctx->cursorDirty[0]) HIPCHK(hipMemsetAsync(cursor, 0, sizeof(int), ctx->stream));
+        ctx->cursorDirty[0] = true;
+        ctx->ws.drainEpoch = (ctx->ws.drainEpoch + 1) & 0x7fffffff;   // tag of this launch's near-tie queue entries (DrainRetrace)
+        if (ctx->ws.drainEpoch == 0) ctx->ws.drainEpoch = 1;
+        if (k.closestGen) {
+            // TWO-CLASS TRAVERSAL: every ray through the triangle kernel; the rays it hands over (deferQ) through the general kernel
+            // (the triangle kernels know one near-tie band: the triangles' own, 2^-20 — the scene-wide band of FastBVH is the wide one of
+            //  the pairs that involve a quadric, which only the general kernel's rays can meet)
+            FastBVH triFast = ctx->fast;
+            triFast.absBand = triFast.absBandTri; triFast.tieRel = triFast.tieRelTri;
+            LAUNCHT("Intersect closest", k.closest, k.grid, ctx->svHost, ctx->ws, triFast, depth & 1, ctx->spillArea(), cursor, ctx->cursorChunk, (const int *)nullptr);
+            LAUNCHT("Intersect closest: rays that met a general primitive", k.closestGen, k.gridGen, ctx->svHost, ctx->ws, ctx->fast, depth & 1, ctx->spillArea(), (int *)nullptr, ctx->cursorChunk, (const int *)ctx->ws.deferQ);
+        } else
+            LAUNCHT("Intersect closest", k.closest, k.grid, ctx->svHost, ctx->ws, ctx->fast, depth & 1, ctx->spillArea(), cursor, ctx->cursorChunk, (const int *)nullptr);
+        // The near-tie re-trace of the scenes whose walk does not resolve its ties itself (genMode >= 2: quadrics, curves, texture-graph
+        // alpha; RetraceInline) is a handful of long single walks: it runs on a second stream beside the routing pass (and, in the
+        // fused pass, the next sample-generation launch) — they touch disjoint rays and share only the queue counters, through
+        // atomics — and the main stream waits for it before anything consumes the queues.
+        const bool overlap = !RetraceInline(ctx->genMode) && ctx->profile != 1 && !ctx->traceLaunch;   // (the full per-stage profile times every launch on the main stream)
+        if (overlap) {
+            HIPCHK(hipEventRecord(ctx->evFork, ctx->stream));
+            HIPCHK(hipStreamWaitEvent(ctx->stream2, ctx->evFork, 0));
+            hipLaunchKernelGGL(k_closest_retrace, dim3(128), dim3(BLOCK), 0, ctx->stream2, ctx->svHost, ctx->ws, depth & 1, ctx->stackSpill);   // (nothing that runs beside it walks a tree: the spill rows are its own)
+            HIPCHK(hipEventRecord(ctx->evJoin, ctx->stream2));
+            ctx->retracePending = true;
+        }
+        {
+            Prof prof_(ctx, "Route hits");
+            const int g = std::min(MAX_GRID, std::max(1, (ctx->maxQueueSize + RBLOCK - 1) / RBLOCK));
+            if (anim)   // (two-level)
+                hipLaunchKernelGGL((k_route_hits<true, true>), dim3(std::min(MAX_GRID, std::max(1, (ctx->maxQueueSize + BLOCK - 1) / BLOCK))), dim3(BLOCK), 0, ctx->stream, ctx->svHost, ctx->ws, depth & 1);
+            else if (ctx->genMode > 1 || ctx->svHost.nInstances > 0) hipLaunchKernelGGL(k_route_hits<true>, dim3(g), dim3(RBLOCK), 0, ctx->stream, ctx->svHost, ctx->ws, depth & 1);
+            else hipLaunchKernelGGL(k_route_hits<false>, dim3(g), dim3(RBLOCK), 0, ctx->stream, ctx->svHost, ctx->ws, depth & 1);
         }
         if (ctx->retracePending) {
             if (ctx->deferJoin) return 0;   // the fused pass joins after its sample-generation launch (JoinRetrace)
             if (int e = JoinRetrace(ctx)) return e;
         } else if (!RetraceInline(ctx->genMode))
-        LAUNCH("Intersect closest: near-tie re-trace", k_closest_retrace, 128, ctx->svHost, ctx->ws, depth & 1, ctx->stackSpill);
-        if (ctx->svHost.haveMix) {
-            if (ctx->svHost.haveAnimated) LAUNCH("Resolve MixMaterial hits", k_resolve_mix<true>, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
-            else LAUNCH("Resolve MixMaterial hits", k_resolve_mix<false>, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
-        }
+            LAUNCH("Intersect closest: near-tie re-trace", k_closest_retrace, 128, ctx->svHost, ctx->ws, depth & 1, ctx->stackSpill);
+        if (ctx->svHost.haveMix) LAUNCH("Resolve MixMaterial hits", (anim ? k_resolve_mix<true> : k_resolve_mix<false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
     } else
-        { if (ctx->svHost.haveAnimated) LAUNCH("Intersect closest", (k_intersect_closest<false, true>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1, ctx->stackSpill);
-          else LAUNCH("Intersect closest", k_intersect_closest<false>, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1, ctx->stackSpill); }
+        LAUNCH("Intersect closest", (anim ? k_intersect_closest<false, true> : k_intersect_closest<false, false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1, ctx->stackSpill);
     return 0;
 }
 // SampleMediumInteraction (wavefront/media.cpp:22-257): K5, then K6 for the Henyey-Greenstein phase function
 int wf_medium_sample(wf_ctx *ctx, int depth) {
     if (int e = checkReady(ctx)) return e;
     if (!ctx->svHost.haveMedia) return 0;
-    if (ctx->mediumLean) LAUNCH("Sample medium interaction", k_medium_sample<true>, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
-    else LAUNCH("Sample medium interaction", k_medium_sample<false>, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
-    if (ctx->svHost.haveAnimated) LAUNCH("Sample medium interaction: route surface hits", k_medium_route<true>, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
-    else LAUNCH("Sample medium interaction: route surface hits", k_medium_route<false>, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
+    LAUNCH("Sample medium interaction", (ctx->mediumLean ? k_medium_sample<true> : k_medium_sample<false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
+    LAUNCH("Sample medium interaction: route surface hits", (ctx->svHost.haveAnimated ? k_medium_route<true> : k_medium_route<false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
     if (depth == ctx->maxDepth) return 0;
-    if (ctx->rareLights) LAUNCH("Sample direct/indirect - Henyey-Greenstein", k_medium_scatter<true>, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
-    else LAUNCH("Sample direct/indirect - Henyey-Greenstein", k_medium_scatter<false>, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
+    LAUNCH("Sample direct/indirect - Henyey-Greenstein", (ctx->rareLights ? k_medium_scatter<true> : k_medium_scatter<false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
     return 0;
 }
 // TraceShadowRays with media: IntersectShadowTr (wavefront/aggregate.cpp:70-88, intersect.h:165-274)
@@ -3046,33 +3031,23 @@ int wf_intersect_shadow_tr(wf_ctx *ctx, int depth) {
         LAUNCH("Intersect shadow (Tr): begin", k_tr_begin, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws);
         for (int seg = 0; seg < WF_TR_SEGMENTS; ++seg) {
             const int cur = seg & 1;
-            if (ctx->svHost.nInstances > 0) {
-                if (ctx->genMode == 0) LAUNCHT("Intersect shadow (Tr): trace", (k_tr_trace<0, true>), ctx->persistentGrid, ctx->svHost, ctx->ws, ctx->fast, cur, ctx->spillArea());
-                else LAUNCHT("Intersect shadow (Tr): trace", (k_tr_trace<1, true>), ctx->persistentGrid, ctx->svHost, ctx->ws, ctx->fast, cur, ctx->spillArea());
-            } else {
-                if (ctx->genMode == 0) LAUNCHT("Intersect shadow (Tr): trace", (k_tr_trace<0, false>), ctx->persistentGrid, ctx->svHost, ctx->ws, ctx->fast, cur, ctx->spillArea());
-                else LAUNCHT("Intersect shadow (Tr): trace", (k_tr_trace<1, false>), ctx->persistentGrid, ctx->svHost, ctx->ws, ctx->fast, cur, ctx->spillArea());
-            }
-            if (ctx->mediumLean) LAUNCH("Intersect shadow (Tr): segment", k_tr_segment<true>, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, cur);
-            else LAUNCH("Intersect shadow (Tr): segment", k_tr_segment<false>, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, cur);
+            LAUNCHT("Intersect shadow (Tr): trace", ctx->walk.trTrace, ctx->walk.grid, ctx->svHost, ctx->ws, ctx->fast, cur, ctx->spillArea());
+            LAUNCH("Intersect shadow (Tr): segment", (ctx->mediumLean ? k_tr_segment<true> : k_tr_segment<false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, cur);
             LAUNCH("Reset transmittance queues", k_reset, 1, ctx->ws, 1u << (CNT_TR0 + cur), -1, 0);
         }
         LAUNCH("Intersect shadow (Tr): rest", k_tr_rest, 128, ctx->svHost, ctx->ws, WF_TR_SEGMENTS & 1, ctx->stackSpill);
     } else if (ctx->fastOk && !ctx->animFast && !ctx->countTraversal && ctx->svHost.nInstances == 0)  // (the per-lane production walk has no two-level variant)
-        if (ctx->svHost.haveAlpha || ctx->svHost.nQuadrics > 0) LAUNCHT("Intersect shadow (Tr)", k_shadow_tr_fast<true>, ctx->persistentGrid, ctx->svHost, ctx->ws, ctx->fast, ctx->spillArea());
-        else if (ctx->mediumLean) LAUNCHT("Intersect shadow (Tr)", (k_shadow_tr_fast<false, true>), ctx->persistentGrid, ctx->svHost, ctx->ws, ctx->fast, ctx->spillArea());
-        else LAUNCHT("Intersect shadow (Tr)", k_shadow_tr_fast<false>, ctx->persistentGrid, ctx->svHost, ctx->ws, ctx->fast, ctx->spillArea());
+        LAUNCHT("Intersect shadow (Tr)", (ctx->svHost.haveAlpha || ctx->svHost.nQuadrics > 0 ? k_shadow_tr_fast<true> : ctx->mediumLean ? k_shadow_tr_fast<false, true> : k_shadow_tr_fast<false>), ctx->walk.grid,
+                ctx->svHost, ctx->ws, ctx->fast, ctx->spillArea());
     else
-        { if (ctx->svHost.haveAnimated) LAUNCH("Intersect shadow (Tr)", k_shadow_tr<true>, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, ctx->stackSpill);
-          else LAUNCH("Intersect shadow (Tr)", k_shadow_tr<false>, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, ctx->stackSpill); }
+        LAUNCH("Intersect shadow (Tr)", (ctx->svHost.haveAnimated ? k_shadow_tr<true> : k_shadow_tr<false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, ctx->stackSpill);
     LAUNCH("Reset shadowRayQueue", k_reset, 1, ctx->ws, (1u << CNT_SHADOW), 65 + statDepth(depth), CNT_SHADOW);
     return 0;
 }
 int wf_handle_escaped(wf_ctx *ctx, int depth) {
     if (int e = checkReady(ctx)) return e;
     if (ctx->svHost.nInfiniteLights == 0) return 0;  // escapedRayQueue == nullptr (integrator.cpp:496-497)
-    if (ctx->portalLights) LAUNCH("Handle escaped rays", k_handle_escaped<true>, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
-    else LAUNCH("Handle escaped rays", k_handle_escaped<false>, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
+    LAUNCH("Handle escaped rays", (ctx->portalLights ? k_handle_escaped<true> : k_handle_escaped<false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
     return 0;
 }
 int wf_handle_emissive(wf_ctx *ctx, int depth) {
@@ -3080,43 +3055,7 @@ int wf_handle_emissive(wf_ctx *ctx, int depth) {
     LAUNCH("Handle emitters hit by indirect rays", k_handle_emissive, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
     return 0;
 }
-static int EvalMaterialOn(wf_ctx *ctx, int material_type, int depth, hipStream_t stream, bool timed);
-int wf_eval_material(wf_ctx *ctx, int material_type, int depth) {
-    if (int e = checkReady(ctx)) return e;
-    return EvalMaterialOn(ctx, material_type, depth, ctx->stream, true);
-}
-// The material stage of one depth for every type present.  The kernels of different types share nothing but queue counters (atomic pushes
-// into the next ray queue and the shadow queue; every item touches only its own pixel sample's state): with WF_MAT_STREAMS=1
-// each type's pair of kernels runs on a stream of its own, forked from and joined to the render stream.  MEASURED AND LEFT OFF (round 5,
-// spec scene, 16 spp, same box, profiles/r05_material_split_ab_sm16.txt): 0.111-0.112 s per render with the streams against 0.108 s
-// without — the kernels run at 2-4 waves per SIMD by their register need, a second kernel finds no free slots beside the first, and the
-// interleaved queues only cost cache locality; VERDICT r4 item 8 asked for the experiment.
-static int EvalMaterials(wf_ctx *ctx, int depth) {
-    int present = 0;
-    for (int m = 1; m < WF_MAT_NTYPES; ++m) present += ctx->matPresent[m] ? 1 : 0;
-    const bool parallel = ctx->matStreams && present > 1 && ctx->profile != 1 && !ctx->traceLaunch;
-    if (!parallel) {
-        for (int m = 1; m < WF_MAT_NTYPES; ++m)
-            if (ctx->matPresent[m])
-                if (int e = EvalMaterialOn(ctx, m, depth, ctx->stream, true)) return e;
-        return 0;
-    }
-    Prof prof_(ctx, "Material stage: all types, shade + next-event estimation (parallel streams)");   // (profile 2: what bench.py prices; on the render stream, fork to join)
-    HIPCHK(hipEventRecord(ctx->evMatFork, ctx->stream));
-    for (int m = 1; m < WF_MAT_NTYPES; ++m) {
-        if (!ctx->matPresent[m]) continue;
-        if (!ctx->matStream[m]) {
-            HIPCHK(hipStreamCreateWithFlags(&ctx->matStream[m], hipStreamNonBlocking));
-            HIPCHK(hipEventCreateWithFlags(&ctx->evMatJoin[m], hipEventDisableTiming));
-        }
-        HIPCHK(hipStreamWaitEvent(ctx->matStream[m], ctx->evMatFork, 0));
-        if (int e = EvalMaterialOn(ctx, m, depth, ctx->matStream[m], false)) return e;
-        HIPCHK(hipEventRecord(ctx->evMatJoin[m], ctx->matStream[m]));
-        HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->evMatJoin[m], 0));
-    }
-    return 0;
-}
-static int EvalMaterialOn(wf_ctx *ctx, int material_type, int depth, hipStream_t stream, bool timed) {
+static int EvalMaterial(wf_ctx *ctx, int material_type, int depth) {
     const int g = gridFor(ctx->maxQueueSize), cur = depth & 1;
     static const char *names[WF_MAT_NTYPES] = {"", "DiffuseMaterial + BxDF eval (Basic tex)", "ConductorMaterial + BxDF eval (Basic tex)",
                                                "DielectricMaterial + BxDF eval (Basic tex)", "ThinDielectricMaterial + BxDF eval (Basic tex)",
@@ -3130,64 +3069,49 @@ static int EvalMaterialOn(wf_ctx *ctx, int material_type, int depth, hipStream_t
                     (ctx->svHost.haveCurves && ctx->svHost.haveQuadricAlpha);   // the variant that fills the visible surface / differentiates a moving camera / meets animated instances or alpha-textured curves
     // the two halves (wf_kernels.h MatShade / MatNee; the items' NeeItems stay in ws.neeRec between them)
     {
-        Prof prof_(ctx, timed ? names[material_type] : "(untimed)", stream);
+        Prof prof_(ctx, names[material_type]);
         // shade variant: 0 / 1 the LEAN kernels (triangle-only scenes whose textures are all constants, image maps or bilerps: SceneLean),
         // without / with the texture footprint and bump block; 2 general; 3 general + visible surface / moving camera
         const int v = vs ? 3 : (!ctx->leanType[material_type] ? 2 : (tex ? 1 : 0));
-        switch (material_type) {
-        case 1: (v == 3 ? wf_launch_mat_shade_1_3 : v == 2 ? wf_launch_mat_shade_1_2 : v == 1 ? wf_launch_mat_shade_1_1 : wf_launch_mat_shade_1_0)(stream, g, &ctx->svHost, &ctx->ws, cur); break;
-        case 2: (v == 3 ? wf_launch_mat_shade_2_3 : v == 2 ? wf_launch_mat_shade_2_2 : v == 1 ? wf_launch_mat_shade_2_1 : wf_launch_mat_shade_2_0)(stream, g, &ctx->svHost, &ctx->ws, cur); break;
-        case 3: (v == 3 ? wf_launch_mat_shade_3_3 : v == 2 ? wf_launch_mat_shade_3_2 : v == 1 ? wf_launch_mat_shade_3_1 : wf_launch_mat_shade_3_0)(stream, g, &ctx->svHost, &ctx->ws, cur); break;
-        case 4: (v == 3 ? wf_launch_mat_shade_4_3 : v == 2 ? wf_launch_mat_shade_4_2 : v == 1 ? wf_launch_mat_shade_4_1 : wf_launch_mat_shade_4_0)(stream, g, &ctx->svHost, &ctx->ws, cur); break;
-        case 5: (v == 3 ? wf_launch_mat_shade_5_3 : v == 2 ? wf_launch_mat_shade_5_2 : v == 1 ? wf_launch_mat_shade_5_1 : wf_launch_mat_shade_5_0)(stream, g, &ctx->svHost, &ctx->ws, cur); break;
-        case 6: (v == 3 ? wf_launch_mat_shade_6_3 : v == 2 ? wf_launch_mat_shade_6_2 : v == 1 ? wf_launch_mat_shade_6_1 : wf_launch_mat_shade_6_0)(stream, g, &ctx->svHost, &ctx->ws, cur); break;
-        case 7: (v == 3 ? wf_launch_mat_shade_7_3 : v == 2 ? wf_launch_mat_shade_7_2 : v == 1 ? wf_launch_mat_shade_7_1 : wf_launch_mat_shade_7_0)(stream, g, &ctx->svHost, &ctx->ws, cur); break;
-        case 8: (v == 3 ? wf_launch_mat_shade_8_3 : v == 2 ? wf_launch_mat_shade_8_2 : v == 1 ? wf_launch_mat_shade_8_1 : wf_launch_mat_shade_8_0)(stream, g, &ctx->svHost, &ctx->ws, cur); break;
-        case 9: (v == 3 ? wf_launch_mat_shade_9_3 : v == 2 ? wf_launch_mat_shade_9_2 : v == 1 ? wf_launch_mat_shade_9_1 : wf_launch_mat_shade_9_0)(stream, g, &ctx->svHost, &ctx->ws, cur); break;
-        case 10: (v == 3 ? wf_launch_mat_shade_10_3 : v == 2 ? wf_launch_mat_shade_10_2 : v == 1 ? wf_launch_mat_shade_10_1 : wf_launch_mat_shade_10_0)(stream, g, &ctx->svHost, &ctx->ws, cur); break;
-        }
+        kMatShade[material_type][v](ctx->stream, g, &ctx->svHost, &ctx->ws, cur);
     }
     {
         static const char *neeNames[WF_MAT_NTYPES] = {"", "DiffuseMaterial: next-event estimation", "ConductorMaterial: next-event estimation", "DielectricMaterial: next-event estimation",
                                                       "ThinDielectricMaterial: next-event estimation", "DiffuseTransmissionMaterial: next-event estimation",
                                                       "CoatedDiffuseMaterial: next-event estimation", "CoatedConductorMaterial: next-event estimation",
                                                       "SubsurfaceMaterial: next-event estimation", "HairMaterial: next-event estimation", "MeasuredMaterial: next-event estimation"};
-        Prof prof_(ctx, timed ? neeNames[material_type] : "(untimed)", stream);
-        switch (material_type) {
-        case 1: (ctx->rareLights ? wf_launch_mat_nee_1_1 : wf_launch_mat_nee_1_0)(stream, g, &ctx->svHost, &ctx->ws); break;
-        case 2: (ctx->rareLights ? wf_launch_mat_nee_2_1 : wf_launch_mat_nee_2_0)(stream, g, &ctx->svHost, &ctx->ws); break;
-        case 3: (ctx->rareLights ? wf_launch_mat_nee_3_1 : wf_launch_mat_nee_3_0)(stream, g, &ctx->svHost, &ctx->ws); break;
-        case 4: (ctx->rareLights ? wf_launch_mat_nee_4_1 : wf_launch_mat_nee_4_0)(stream, g, &ctx->svHost, &ctx->ws); break;
-        case 5: (ctx->rareLights ? wf_launch_mat_nee_5_1 : wf_launch_mat_nee_5_0)(stream, g, &ctx->svHost, &ctx->ws); break;
-        case 6: (ctx->rareLights ? wf_launch_mat_nee_6_1 : wf_launch_mat_nee_6_0)(stream, g, &ctx->svHost, &ctx->ws); break;
-        case 7: (ctx->rareLights ? wf_launch_mat_nee_7_1 : wf_launch_mat_nee_7_0)(stream, g, &ctx->svHost, &ctx->ws); break;
-        case 8: (ctx->rareLights ? wf_launch_mat_nee_8_1 : wf_launch_mat_nee_8_0)(stream, g, &ctx->svHost, &ctx->ws); break;
-        case 9: (ctx->rareLights ? wf_launch_mat_nee_9_1 : wf_launch_mat_nee_9_0)(stream, g, &ctx->svHost, &ctx->ws); break;
-        case 10: (ctx->rareLights ? wf_launch_mat_nee_10_1 : wf_launch_mat_nee_10_0)(stream, g, &ctx->svHost, &ctx->ws); break;
-        }
+        Prof prof_(ctx, neeNames[material_type]);
+        kMatNee[material_type][ctx->rareLights ? 1 : 0](ctx->stream, g, &ctx->svHost, &ctx->ws);
     }
+    return 0;
+}
+int wf_eval_material(wf_ctx *ctx, int material_type, int depth) {
+    if (int e = checkReady(ctx)) return e;
+    return EvalMaterial(ctx, material_type, depth);
+}
+// The material stage of one depth: every type present, one after the other on the render stream.  (Measured and dropped, round 5: each
+// type's pair of kernels on a stream of its own — 0.111-0.112 s per render against 0.108 s, profiles/r05_material_split_ab_sm16.txt.)
+static int EvalMaterials(wf_ctx *ctx, int depth) {
+    for (int m = 1; m < WF_MAT_NTYPES; ++m)
+        if (ctx->matPresent[m])
+            if (int e = EvalMaterial(ctx, m, depth)) return e;
     return 0;
 }
 int wf_intersect_shadow(wf_ctx *ctx, int depth) {
     if (int e = checkReady(ctx)) return e;
+    const bool anim = ctx->svHost.haveAnimated;
     if (ctx->countTraversal)
-        { if (ctx->svHost.haveAnimated) LAUNCH("Intersect shadow", (k_intersect_shadow<true, true>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, ctx->stackSpill);
-          else LAUNCH("Intersect shadow", k_intersect_shadow<true>, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, ctx->stackSpill); }
+        LAUNCH("Intersect shadow", (anim ? k_intersect_shadow<true, true> : k_intersect_shadow<true, false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, ctx->stackSpill);
     else if (ctx->fastOk) {
-        int *cursor = nullptr;
-        if (ctx->splitRoute > 1) {
-            cursor = ctx->ws.counters + CNT_CURSOR_SHADOW * CNT_STRIDE;   // (zeroed by the "Reset shadowRayQueue" launch that follows every any-hit launch)
-            if (ctx->cursorDirty[1]) HIPCHK(hipMemsetAsync(cursor, 0, sizeof(int), ctx->stream));
-            ctx->cursorDirty[1] = true;
-        }
-        if (ctx->deferGeneral && ctx->splitRoute) {
-            LAUNCHT_VARIANT_GEN("Intersect shadow", k_shadow_fast, 4 + ctx->genTri, ctx->persistentGridShadow, ctx->svHost, ctx->ws, ctx->fast, ctx->spillArea(), cursor, ctx->cursorChunkShadow, (const int *)nullptr);
-            LAUNCHT_VARIANT_GEN("Intersect shadow: rays that met a general primitive", k_shadow_fast, ctx->genMode, ctx->persistentGridShadowGen, ctx->svHost, ctx->ws, ctx->fast, ctx->spillArea(), (int *)nullptr, ctx->cursorChunkShadow, (const int *)ctx->ws.deferQ);
-        } else
-        LAUNCHT_VARIANT_GEN("Intersect shadow", k_shadow_fast, ctx->animFast ? 8 + ctx->genMode : ctx->genMode, ctx->persistentGridShadow, ctx->svHost, ctx->ws, ctx->fast, ctx->spillArea(), cursor, ctx->cursorChunkShadow, (const int *)nullptr);
+        const WalkKernels &k = ctx->walk;
+        int *cursor = ctx->ws.counters + CNT_CURSOR_SHADOW * CNT_STRIDE;   // (zeroed by the "Reset shadowRayQueue" launch that follows every any-hit launch)
+        if (ctx->cursorDirty[1]) HIPCHK(hipMemsetAsync(cursor, 0, sizeof(int), ctx->stream));
+        ctx->cursorDirty[1] = true;
+        LAUNCHT("Intersect shadow", k.shadow, k.gridShadow, ctx->svHost, ctx->ws, ctx->fast, ctx->spillArea(), cursor, ctx->cursorChunkShadow, (const int *)nullptr);
+        if (k.shadowGen)   // TWO-CLASS TRAVERSAL
+            LAUNCHT("Intersect shadow: rays that met a general primitive", k.shadowGen, k.gridShadowGen, ctx->svHost, ctx->ws, ctx->fast, ctx->spillArea(), (int *)nullptr, ctx->cursorChunkShadow, (const int *)ctx->ws.deferQ);
     } else
-        { if (ctx->svHost.haveAnimated) LAUNCH("Intersect shadow", (k_intersect_shadow<false, true>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, ctx->stackSpill);
-          else LAUNCH("Intersect shadow", k_intersect_shadow<false>, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, ctx->stackSpill); }
+        LAUNCH("Intersect shadow", (anim ? k_intersect_shadow<false, true> : k_intersect_shadow<false, false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, ctx->stackSpill);
     // "Reset shadowRayQueue": stats->shadowRays[depth] += size; Reset (integrator.cpp:581-585)
     LAUNCH("Reset shadowRayQueue", k_reset, 1, ctx->ws, (1u << CNT_SHADOW) | (1u << CNT_CURSOR_SHADOW) | (1u << CNT_DEFER_SHADOW), 65 + statDepth(depth), CNT_SHADOW);
     ctx->cursorDirty[1] = false;
@@ -3205,8 +3129,7 @@ int wf_intersect_one_random(wf_ctx *ctx) {
     if (int e = checkReady(ctx)) return e;
     if (!ctx->svHost.haveSubsurface) return 0;
     // reference-order walk (the chain of probe hits is a dependent sequence per item; the subsurface path is a side path)
-    if (ctx->svHost.haveAnimated) LAUNCH("Intersect one random (subsurface probe)", k_intersect_one_random<true>, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, ctx->stackSpill);
-    else LAUNCH("Intersect one random (subsurface probe)", k_intersect_one_random<false>, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, ctx->stackSpill);
+    LAUNCH("Intersect one random (subsurface probe)", (ctx->svHost.haveAnimated ? k_intersect_one_random<true> : k_intersect_one_random<false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, ctx->stackSpill);
     return 0;
 }
 int wf_subsurface_scatter(wf_ctx *ctx, int depth) {
@@ -3234,7 +3157,7 @@ int wf_render_pass(wf_ctx *ctx, int y0, int sample_index) {
         if ((e = wf_reset_stage_queues(ctx, depth))) return e;
         // (GenerateRaySamples does not depend on the intersections: it is issued after the closest-hit launch so that it runs beside
         // the re-trace; the per-stage entry points keep the reference's order)
-        ctx->deferJoin = ctx->overlapRetrace && ctx->fastOk && ctx->splitRoute && !ctx->countTraversal && !ctx->svHost.haveMix;
+        ctx->deferJoin = ctx->fastOk && !ctx->countTraversal && !ctx->svHost.haveMix;
         if ((e = wf_intersect_closest(ctx, depth))) { ctx->deferJoin = false; return e; }
         ctx->deferJoin = false;
         if ((e = wf_gen_ray_samples(ctx, depth, sample_index))) return e;
@@ -3452,7 +3375,7 @@ int wf_trace_closest_device(wf_ctx *ctx, int n, const float *rays7, wf_hit_recor
     useDevice(ctx);
     if (n <= 0) return 0;
     if (!ctx->fastOk) { LAUNCH("trace closest (device rays)", k_trace_closest, gridFor(n), ctx->svHost, n, rays7, out, ctx->stackSpill, 0); return 0; }
-    LAUNCHT_VARIANT("trace closest fast (device rays)", k_trace_closest_fast, 0, ctx->persistentGrid, ctx->svHost, ctx->fast, n, rays7, out, ctx->spillArea());
+    LAUNCHT("trace closest fast (device rays)", ctx->walk.traceClosest, ctx->walk.grid, ctx->svHost, ctx->fast, n, rays7, out, ctx->spillArea());
     // (the variants that do not resolve their near ties inside the walk mark them: re-traced in reference order)
     if (!RetraceInline(ctx->genMode)) LAUNCH("trace closest (near-tie re-trace)", k_trace_closest, gridFor(n), ctx->svHost, n, rays7, out, ctx->stackSpill, 1);
     return 0;
@@ -3463,7 +3386,7 @@ int wf_trace_any_device(wf_ctx *ctx, int n, const float *rays7, int32_t *occlude
     useDevice(ctx);
     if (n <= 0) return 0;
     if (!ctx->fastOk) { LAUNCH("trace any (device rays)", k_trace_any, gridFor(n), ctx->svHost, n, rays7, occluded, (int32_t *)nullptr, (int32_t *)nullptr, ctx->stackSpill); return 0; }
-    LAUNCHT_VARIANT("trace any fast (device rays)", k_trace_any_fast, 0, ctx->persistentGrid, ctx->svHost, ctx->fast, n, rays7, occluded, ctx->spillArea());
+    LAUNCHT("trace any fast (device rays)", ctx->walk.traceAny, ctx->walk.grid, ctx->svHost, ctx->fast, n, rays7, occluded, ctx->spillArea());
     return 0;
 }
 int wf_device_alloc(wf_ctx *ctx, uint64_t nbytes, void **dptr) {
@@ -3554,8 +3477,7 @@ static int TraceShadowTrHost(wf_ctx *ctx, const char *fn, int n, const float *o,
         if ((e = up(&ws.pathTime, time, n * sizeof(float)))) return e;
         LAUNCH("shadow Tr (host rays, timed)", k_shadow_tr<true>, gridFor(n), ctx->svHost, ws, ctx->stackSpill);
     } else if (ctx->fastOk && ctx->svHost.nInstances == 0) {
-        if (ctx->svHost.haveAlpha || ctx->svHost.nQuadrics > 0) LAUNCHT("shadow Tr (host rays)", k_shadow_tr_fast<true>, ctx->persistentGrid, ctx->svHost, ws, ctx->fast, ctx->spillArea());
-        else LAUNCHT("shadow Tr (host rays)", k_shadow_tr_fast<false>, ctx->persistentGrid, ctx->svHost, ws, ctx->fast, ctx->spillArea());
+        LAUNCHT("shadow Tr (host rays)", (ctx->svHost.haveAlpha || ctx->svHost.nQuadrics > 0 ? k_shadow_tr_fast<true> : k_shadow_tr_fast<false>), ctx->walk.grid, ctx->svHost, ws, ctx->fast, ctx->spillArea());
     } else LAUNCH("shadow Tr (host rays)", k_shadow_tr<false>, gridFor(n), ctx->svHost, ws, ctx->stackSpill);
     HIPCHK(hipMemcpyAsync(out_L, ws.L, n * sizeof(F4), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
