@@ -372,7 +372,13 @@ typedef struct wf_instance {
     int32_t def;                        /* index into instance_defs */
     int32_t anim_plus1;                 /* AnimatedPrimitive (cpu/primitive.h:103): 1 + index into wf_scene_desc.animated, 0 = a static instance
                                            (render_from_instance then holds the start transformation) */
-    int32_t pad[2];
+    /* An animated shape inside an instance definition (scene.cpp:287-288, 1530-1551: an AnimatedPrimitive among the definition's primitives)
+       is a NESTED PLACEMENT: the definition's bvh_prims names it as n_triangles + n_quadrics + k (k = 0, 1, ... in the definition's order), and
+       every use of the definition is followed in `instances` by one record per nested placement: def = the moving entity's own (hidden)
+       definition, anim_plus1 = its AnimatedTransform, render_from_instance = that at its start.  A hit inside nested placement k of use j is
+       reported with instance = instances[j].nested_first + k; its interaction is transformed by that record first, then by the outer use. */
+    int32_t outer_plus1;                /* a nested placement: 1 + index of the use of the definition that holds it; 0 = a top-level instance */
+    int32_t nested_first;               /* a use of a definition with nested placements: index of the first of their records; else 0 */
 } wf_instance;
 typedef struct wf_instance_def {
     int32_t bvh_root;                   /* root of the definition's BVH in bvh_nodes */
@@ -482,7 +488,10 @@ typedef struct wf_scene_desc {
     const int32_t *tri_mesh;     /* [n_triangles + n_quadrics] mesh id of every primitive */
     const wf_mesh *meshes;
     const wf_bvh_node *bvh_nodes;
-    const int32_t *bvh_prims;    /* [n_triangles + n_quadrics] primitive ids in BVH leaf order */
+    const int32_t *bvh_prims;    /* primitive ids in BVH leaf order.  Length = what the leaves of bvh_nodes index (max offset + nprims): every
+                                    triangle / quadric once, every top-level instance once (n_triangles + n_quadrics + index), and every
+                                    nested placement once per DEFINITION (wf_instance) — not n_instances entries: a nested placement's
+                                    record repeats per use, its leaf entry does not.  wf_scene_check_instances reports the length. */
     float scene_bounds[6];
     /* shading */
     int32_t n_spectra, n_spectrum_floats, n_textures, n_materials;
@@ -804,7 +813,8 @@ int wf_debug_counters(wf_ctx *ctx, uint64_t out[4], int reset);
 /* Which kernel variants the uploaded scene runs (tests assert that a scene takes the path they mean to cover): key = "fast_ok" (the
    production traversal layout is in use), "gen_mode" (0 - 3: strength of the walk kernels), "gen_tri", "defer_general" (the two-class
    traversal), "anim_fast" (AnimatedPrimitives on the production walk), "lean_shade", "lean_type_<material type>", "rare_lights", "medium_lean" (the lean delta-tracking / transmittance kernels),
-   "instances".  Introspection only; nothing in the reference corresponds. */
+   "instances", "nested_animated" (records of `instances` that are nested placements: animated shapes inside instance definitions, per use).
+   Introspection only; nothing in the reference corresponds. */
 int wf_ctx_query(wf_ctx *ctx, const char *key, int64_t *value);
 /* Host-only self-check of the production traversal layout (no device needed; CPU suite, tests/test_fastbvh_host.py): builds the
    QNode / LeafTri / instance-entry arrays wf_scene_upload would upload for `d` (round 6: with the top-level tree rebuilt over
@@ -814,6 +824,12 @@ int wf_ctx_query(wf_ctx *ctx, const char *key, int64_t *value);
    out[5] of those NOT among the triangles the walk tested (must be 0: the tree owes a superset), out[6] triangles tested,
    out[7] instance entries taken.  Replaces nothing in the reference (its accelerator is OptiX's, gpu/optix/aggregate.cpp). */
 int wf_debug_fastbvh_check(const wf_scene_desc *d, int n_rays, uint64_t seed, int64_t out[8]);
+/* Host-only range check of the instance tables (no device needed; wf_scene_upload runs it first): leaf and definition ranges inside
+   bvh_prims, every instance's def / anim_plus1 in range and, in a scene with animated primitives, the nested-placement words of wf_instance
+   consistent (outer_plus1 names a use whose group holds the record, nested_first + the definition's nested entries inside `instances`, a
+   nested placement animated and without nested placements of its own).  out (may be null): [0] entries of bvh_prims the trees index,
+   [1] top-level instance records, [2] nested-placement records, [3] nested placements named by the definitions' leaves. */
+int wf_scene_check_instances(const wf_scene_desc *d, int64_t out[4]);
 
 #ifdef __cplusplus
 }

@@ -812,10 +812,15 @@ WF_HD const wf_instance &InstanceAt(const SceneView &sv, const wf_instance &in, 
     return *tmp;
 }
 
-// BVHAggregate::Intersect / IntersectP of an instance definition's own BVH (triangles only), on the shared stack above
+// BVHAggregate::Intersect / IntersectP of an instance definition's own BVH, on the shared stack above
 // its current top.  tMax is updated in place; returns whether a hit was recorded.
-template <typename Stack>
-WF_HD bool BVHIntersectClosestDef(const SceneView &sv, int root, V3 o, V3 d, float *tMaxIO, Stack &stack, ClosestHit *out) {
+// ANIM: the definition may hold NESTED PLACEMENTS (animated shapes created inside it: an AnimatedPrimitive among its primitives, wf_abi.h
+// wf_instance): entry n_triangles + n_quadrics + k of its bvh_prims is record sv.instances[inst].nested_first + k, entered as the top level
+// enters an instance — the ray transformed a second time at `time` (cpu/primitive.cpp:140-153), the entity's tree walked on the same stack
+// above this walk's entries (a third level), tMax staying the innermost ray's parameter.  A nested entity holds none itself: its walk is the
+// static one.
+template <bool ANIM = false, typename Stack>
+WF_HD bool BVHIntersectClosestDef(const SceneView &sv, int root, V3 o, V3 d, float *tMaxIO, Stack &stack, ClosestHit *out, int inst, float time = 0) {
     float tMax = *tMaxIO;
     bool hitAny = false;
     const int base = stack.n;
@@ -829,12 +834,28 @@ WF_HD bool BVHIntersectClosestDef(const SceneView &sv, int root, V3 o, V3 d, flo
             if (node->nprims > 0) {
                 for (int i = 0; i < node->nprims; ++i) {
                     int tri = sv.bvhPrims[node->offset + i];
+                    if constexpr (ANIM)
+                        if (tri >= sv.nTriangles + sv.nQuadrics) {
+                            const int nested = sv.instances[inst].nested_first + (tri - sv.nTriangles - sv.nQuadrics);
+                            wf_instance inTmp;
+                            const wf_instance &in = InstanceAt<true>(sv, sv.instances[nested], time, &inTmp);
+                            float tI = tMax;
+                            V3 oI, dI;
+                            InstanceRay(in, o, d, &tI, &oI, &dI);
+                            if (BVHIntersectClosestDef<false>(sv, sv.instanceDefs[in.def].bvh_root, oI, dI, &tI, stack, out, nested)) {
+                                out->inst = nested;
+                                tMax = tI;
+                                hitAny = true;
+                            }
+                            continue;
+                        }
                     ++out->trisTested;
                     if (tri >= sv.nTriangles) {
                         // a quadric or bilinear patch of the definition, in the definition's space
                         QuadricHit qh;
                         if (QuadricIntersect(sv, tri, o, d, tMax, &qh)) {
                             out->prim = tri;
+                            if constexpr (ANIM) out->inst = inst;
                             out->h.t = qh.tHit; out->h.b0 = qh.pObj.x; out->h.b1 = qh.pObj.y; out->h.b2 = qh.pObj.z;
                             tMax = qh.tHit;
                             hitAny = true;
@@ -847,6 +868,7 @@ WF_HD bool BVHIntersectClosestDef(const SceneView &sv, int root, V3 o, V3 d, flo
                     if (IntersectTriangle(o, d, tMax, p0, p1, p2, &h)) {
                         if (!sv.haveAlpha || AlphaTestPasses(sv, tri, h.b0, h.b1, h.b2, o, d)) {
                             out->prim = tri;
+                            if constexpr (ANIM) out->inst = inst;
                             out->h = h;
                             tMax = h.t;
                             hitAny = true;
@@ -872,8 +894,8 @@ WF_HD bool BVHIntersectClosestDef(const SceneView &sv, int root, V3 o, V3 d, flo
     *tMaxIO = tMax;
     return hitAny;
 }
-template <typename Stack>
-WF_HD bool BVHIntersectAnyDef(const SceneView &sv, int root, V3 o, V3 d, float tMax, Stack &stack, int *nv, int *nt) {
+template <bool ANIM = false, typename Stack>
+WF_HD bool BVHIntersectAnyDef(const SceneView &sv, int root, V3 o, V3 d, float tMax, Stack &stack, int *nv, int *nt, int inst = -1, float time = 0) {
     const int base = stack.n;
     V3 invDir{1.f / d.x, 1.f / d.y, 1.f / d.z};
     int negMask = int(invDir.x < 0) | (int(invDir.y < 0) << 1) | (int(invDir.z < 0) << 2);
@@ -886,6 +908,16 @@ WF_HD bool BVHIntersectAnyDef(const SceneView &sv, int root, V3 o, V3 d, float t
             if (node->nprims > 0) {
                 for (int i = 0; i < node->nprims && !found; ++i) {
                     int tri = sv.bvhPrims[node->offset + i];
+                    if constexpr (ANIM)
+                        if (tri >= sv.nTriangles + sv.nQuadrics) {   // a nested placement: see BVHIntersectClosestDef
+                            wf_instance inTmp;
+                            const wf_instance &in = InstanceAt<true>(sv, sv.instances[sv.instances[inst].nested_first + (tri - sv.nTriangles - sv.nQuadrics)], time, &inTmp);
+                            float tI = tMax;
+                            V3 oI, dI;
+                            InstanceRay(in, o, d, &tI, &oI, &dI);
+                            if (BVHIntersectAnyDef<false>(sv, sv.instanceDefs[in.def].bvh_root, oI, dI, tI, stack, nv, nt)) found = true;
+                            continue;
+                        }
                     ++*nt;
                     if (tri >= sv.nTriangles) {
                         QuadricHit qh;
@@ -948,8 +980,8 @@ WF_HD bool BVHIntersectClosest(const SceneView &sv, V3 o, V3 d, float tMax, Stac
                         float tI = tMax;
                         V3 oI, dI;
                         InstanceRay(in, o, d, &tI, &oI, &dI);
-                        if (BVHIntersectClosestDef(sv, sv.instanceDefs[in.def].bvh_root, oI, dI, &tI, stack, out)) {
-                            out->inst = inst;
+                        if (BVHIntersectClosestDef<ANIM>(sv, sv.instanceDefs[in.def].bvh_root, oI, dI, &tI, stack, out, inst, time)) {
+                            if constexpr (!ANIM) out->inst = inst;   // (ANIM: set with each hit — by this use, or by a nested placement of it)
                             tMax = tI;
                         }
                         continue;
@@ -1013,11 +1045,12 @@ WF_HD bool BVHIntersectAny(const SceneView &sv, V3 o, V3 d, float tMax, Stack &s
                     int tri = sv.bvhPrims[node->offset + i];
                     if (tri >= sv.nTriangles + sv.nQuadrics) {
                         wf_instance inTmp;
-                        const wf_instance &in = InstanceAt<ANIM>(sv, sv.instances[tri - sv.nTriangles - sv.nQuadrics], time, &inTmp);
+                        const int inst = tri - sv.nTriangles - sv.nQuadrics;
+                        const wf_instance &in = InstanceAt<ANIM>(sv, sv.instances[inst], time, &inTmp);
                         float tI = tMax;
                         V3 oI, dI;
                         InstanceRay(in, o, d, &tI, &oI, &dI);
-                        if (BVHIntersectAnyDef(sv, sv.instanceDefs[in.def].bvh_root, oI, dI, tI, stack, &nv, &nt)) found = true;
+                        if (BVHIntersectAnyDef<ANIM>(sv, sv.instanceDefs[in.def].bvh_root, oI, dI, tI, stack, &nv, &nt, inst, time)) found = true;
                         continue;
                     }
                     ++nt;
@@ -1056,7 +1089,7 @@ WF_HD bool BVHIntersectAny(const SceneView &sv, V3 o, V3 d, float tMax, Stack &s
 }
 
 struct ArrayStack {  // int nodesToVisit[64], cpu/aggregates.cpp:538
-    int s[128];  // the top-level walk's entries + an instance definition's on top of them
+    int s[192];  // the top-level walk's entries + an instance definition's on top of them + a nested moving entity's on top of those (3 x 64)
     int n = 0;
     WF_HD void push(int v) { s[n++] = v; }
     WF_HD int pop() { return s[--n]; }
@@ -1630,6 +1663,20 @@ WF_HD V3 IntrWo(const SceneView &sv, int prim, int inst, V3 minusD, float time =
         V3 w;
         wf_instance inTmp;
         const wf_instance *in = &InstanceAt<ANIM>(sv, sv.instances[inst], time, &inTmp);
+        if constexpr (ANIM)
+            if (sv.instances[inst].outer_plus1 != 0) {
+                // a nested placement (wf_abi.h wf_instance): the ray passed the outer use, then the moving entity; wo comes back through both,
+                // normalised after each (util/transform.cpp:235)
+                wf_instance outTmp;
+                const wf_instance *outer = &InstanceAt<true>(sv, sv.instances[sv.instances[inst].outer_plus1 - 1], time, &outTmp);
+                const V3 vO = XfVector3(outer->render_from_instance.mInv, minusD);
+                if (GENERAL && prim >= sv.nTriangles) {
+                    const V3 vI = XfVector3(in->render_from_instance.mInv, vO);
+                    SphereWoP(sv.quadrics + (prim - sv.nTriangles), vI.x, vI.y, vI.z, &w.x, &w.y, &w.z);
+                    w = Normalize(XfVector3(in->render_from_instance.m, w));
+                } else InstanceWoP(in, vO.x, vO.y, vO.z, &w.x, &w.y, &w.z);
+                return Normalize(XfVector3(outer->render_from_instance.m, w));
+            }
         if (GENERAL && prim >= sv.nTriangles) {
             // a quadric inside an instance: built in object space from the instance-space ray (normalised there and after the transform
             // back to instance space), then taken to render space by the instance transform (normalised again)
@@ -1677,6 +1724,12 @@ WF_HD bool IsCurvePrim(const SceneView &sv, int prim) { return sv.haveCurves && 
 template <bool GENERAL = !WF_DEV_LEAN, bool CURVE_ALPHA = false, bool ANIM = false>
 WF_HD void HitInteraction(const SceneView &sv, int prim, int inst, float b0, float b1, float b2, SurfIntr *si, V3 ro, V3 rd, float time = 0) {
     wf_instance inTmp;
+    // a hit inside a nested placement (wf_abi.h wf_instance): the ray passed the outer use of the definition, then the moving entity, and the
+    // interaction comes back through the entity's transformation, then the use's — two separate applications (cpu/primitive.cpp:112-158)
+    int outer = -1;
+    if constexpr (ANIM) if (inst >= 0) outer = sv.instances[inst].outer_plus1 - 1;
+    if constexpr (GENERAL && ANIM)
+        if (outer >= 0 && IsCurvePrim(sv, prim)) { float tm = WF_INFINITY; InstanceRay(InstanceAt<true>(sv, sv.instances[outer], time, &inTmp), ro, rd, &tm, &ro, &rd); }
     const wf_instance *inp = inst >= 0 ? &InstanceAt<ANIM>(sv, sv.instances[inst], time, &inTmp) : nullptr;
     if constexpr (!GENERAL) TriangleInteraction(sv, prim, b0, b1, b2, si);
     else
@@ -1698,6 +1751,12 @@ WF_HD void HitInteraction(const SceneView &sv, int prim, int inst, float b0, flo
         *si = tmp;
         }
     }
+    if constexpr (ANIM)
+        if (outer >= 0) {
+            SurfIntr tmp = *si;
+            InstanceInteractionP(&InstanceAt<true>(sv, sv.instances[outer], time, &inTmp), &tmp);
+            *si = tmp;
+        }
 }
 
 // GeometricPrimitive::Intersect (cpu/primitive.cpp:50-78) for a sphere / disk / cylinder / bilinear patch with an alpha texture: a hit

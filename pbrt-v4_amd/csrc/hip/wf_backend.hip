@@ -123,6 +123,7 @@ struct wf_ctx {
     int genMode = 0;             // general-primitive strength of the traversal kernels: 0 triangles only, 1 simple alpha, 2 anything but curves and alpha on quadrics, 3 anything (see GeneralPrims)
     bool deferGeneral = false;   // TWO-CLASS TRAVERSAL (see WalkKernels)
     int genTri = 0;
+    int nestedAnimated = 0;      // records of `instances` that are nested placements (animated shapes inside instance definitions); such scenes keep the reference-order walks
     bool animFast = false;       // the scene's AnimatedPrimitives are walked by the production kernels' ANIM variants (round 6; genMode <= 1 only)
     WalkKernels walk;
     int cursorChunk = 2;         // 64-ray batches a closest-hit wave takes per cursor fetch (chosen from the tree size at upload)
@@ -225,12 +226,15 @@ struct LdsStack {
     int *spill;   // &stackSpill[global thread], stride = total threads
     int spillStride;
     int n;
-    __device__ void push(int v) {
+    // always inline: the three-level walks of the ANIM kernels have enough call sites for the inliner to leave push / pop out of line, and an
+    // out-of-line function that touches g_sstack moves EVERY LDS array of the unit that such functions reach (g_tstack: LdsStackT::push) from a
+    // fixed address to a per-kernel table look-up — in the static scenes' kernels too
+    __device__ __forceinline__ void push(int v) {
         if (n < STACK_LDS) g_sstack[n * BLOCK + threadIdx.x] = v;
         else spill[(size_t)(n - STACK_LDS) * spillStride] = v;
         ++n;
     }
-    __device__ int pop() {
+    __device__ __forceinline__ int pop() {
         --n;
         int v = g_sstack[(n < STACK_LDS ? n : 0) * BLOCK + threadIdx.x];  // always a ds_read
         if (__builtin_expect(n >= STACK_LDS, 0)) v = spill[(size_t)(n - STACK_LDS) * spillStride];
@@ -1660,16 +1664,94 @@ struct TopTreeBuilder {
     }
 };
 
+// Nested placements (wf_abi.h wf_instance) exist in scenes with animated primitives only; without any, the two words that describe them are
+// never read (callers that predate them may have left them unset).
+static int NestedPlacements(const wf_scene_desc *d) {
+    int n = 0;
+    if (d->n_animated > 0)
+        for (int i = 0; i < d->n_instances; ++i) n += d->instances[i].outer_plus1 != 0;
+    return n;
+}
+// Entries of bvh_prims: what the leaves of the trees index.  Every triangle / quadric once, every top-level instance once, and every nested
+// placement ONCE PER DEFINITION (its records in `instances` repeat per use, its entry in the definition's leaves does not) — so this is
+// n_triangles + n_quadrics + n_instances only while no definition with a nested placement is used more than once.
+static int64_t BvhPrimCount(const wf_scene_desc *d) {
+    int64_t n = 0;
+    for (int i = 0; i < d->n_bvh_nodes; ++i)
+        if (d->bvh_nodes[i].nprims > 0) n = std::max(n, (int64_t)d->bvh_nodes[i].offset + d->bvh_nodes[i].nprims);
+    return n;
+}
+int wf_scene_check_instances(const wf_scene_desc *d, int64_t out[4]) {
+    if (!d) return fail(-1, "wf_scene_check_instances: null argument");
+    const int nGeom = d->n_triangles + d->n_quadrics, nI = d->n_instances, nD = d->n_instance_defs;
+    const int64_t nPrims = BvhPrimCount(d);
+    for (int i = 0; i < d->n_bvh_nodes; ++i) {
+        const wf_bvh_node &n = d->bvh_nodes[i];
+        if (n.offset < 0 || (n.nprims == 0 && n.offset >= d->n_bvh_nodes)) return fail(-1, "bvh_nodes[%d]: offset %d out of range", i, n.offset);
+    }
+    const int64_t nTop = nI > 0 ? d->n_top_prims : nPrims;
+    if (nTop < 0 || nTop > nPrims) return fail(-1, "n_top_prims %d outside bvh_prims (%lld entries)", d->n_top_prims, (long long)nPrims);
+    const bool anim = d->n_animated > 0;   // (the nested-placement words are read in such scenes only)
+    int64_t nNestedRecords = 0, nNestedEntries = 0;
+    // per definition: its range of bvh_prims, and how many nested placements its leaves name (entries nGeom + 0 .. nGeom + c - 1)
+    std::vector<int> defNested((size_t)std::max(nD, 0), 0);
+    for (int k = 0; k < nD; ++k) {
+        const wf_instance_def &def = d->instance_defs[k];
+        if (def.n_prims < 0 || def.first_prim < 0 || (int64_t)def.first_prim + def.n_prims > nPrims) return fail(-1, "instance_defs[%d]: bvh_prims range %d + %d outside the %lld entries", k, def.first_prim, def.n_prims, (long long)nPrims);
+        if (def.bvh_root >= d->n_bvh_nodes) return fail(-1, "instance_defs[%d]: bvh_root %d out of range", k, def.bvh_root);
+        int c = 0, hi = -1;
+        for (int j = def.first_prim; j < def.first_prim + def.n_prims; ++j) {
+            const int t = d->bvh_prims[j];
+            if (t < 0) return fail(-1, "bvh_prims[%d] = %d", j, t);
+            if (t >= nGeom) { ++c; hi = std::max(hi, t - nGeom); }
+        }
+        if (c > 0 && !anim) return fail(-1, "instance_defs[%d] names an instance in its leaves: only a scene with animated primitives can hold nested placements", k);
+        if (hi >= c) return fail(-1, "instance_defs[%d]: nested placement %d named, %d present", k, hi, c);
+        defNested[k] = c;
+        nNestedEntries += c;
+    }
+    for (int64_t j = 0; j < nTop; ++j) {
+        const int t = d->bvh_prims[j];
+        if (t < 0 || t >= nGeom + nI) return fail(-1, "bvh_prims[%lld] = %d outside the primitives and instances", (long long)j, t);
+        if (anim && t >= nGeom && d->instances[t - nGeom].outer_plus1 != 0) return fail(-1, "bvh_prims[%lld]: a nested placement's record among the top-level primitives", (long long)j);
+    }
+    for (int i = 0; i < nI; ++i) {
+        const wf_instance &in = d->instances[i];
+        if (in.def < 0 || in.def >= nD) return fail(-1, "instances[%d]: def %d out of range", i, in.def);
+        if (in.anim_plus1 < 0 || in.anim_plus1 > d->n_animated) return fail(-1, "instances[%d]: anim_plus1 %d out of range", i, in.anim_plus1);
+        if (!anim) continue;
+        if (in.outer_plus1 != 0) {
+            // a nested placement: animated, holds none itself, and belongs to the group of the use it names
+            ++nNestedRecords;
+            const int o = in.outer_plus1 - 1;
+            if (o < 0 || o >= nI || d->instances[o].outer_plus1 != 0) return fail(-1, "instances[%d]: outer_plus1 %d does not name a use of a definition", i, in.outer_plus1);
+            const int first = d->instances[o].nested_first, c = defNested[d->instances[o].def];
+            if (first <= 0 || i < first || i >= first + c) return fail(-1, "instances[%d]: not among the %d nested records of instances[%d] (nested_first %d)", i, c, o, first);
+            if (in.anim_plus1 == 0 || in.nested_first != 0 || defNested[in.def] != 0) return fail(-1, "instances[%d]: a nested placement is an animated primitive around a definition without nested placements", i);
+        } else {
+            const int c = defNested[in.def];
+            if (c == 0) continue;   // (nested_first is not read)
+            if (in.nested_first <= 0 || (int64_t)in.nested_first + c > nI) return fail(-1, "instances[%d]: nested_first %d + %d nested placements outside instances", i, in.nested_first, c);
+            for (int k = 0; k < c; ++k)
+                if (d->instances[in.nested_first + k].outer_plus1 != i + 1) return fail(-1, "instances[%d]: record %d is not nested placement %d of this use", i, in.nested_first + k, k);
+        }
+    }
+    if (out) { out[0] = nPrims; out[1] = nI - nNestedRecords; out[2] = nNestedRecords; out[3] = nNestedEntries; }
+    return 0;
+}
 static bool BuildFastBVH(const wf_scene_desc *d, std::vector<QNode> *nodes, std::vector<LeafTri> *tris, std::vector<FastDef> *defs, std::vector<SubEntry> *subs,
                          FastBVH *out, FastDepths *depths) {
     const wf_bvh_node *L = d->bvh_nodes;   // (rebound to the extended array once the re-braided top-level tree has been appended)
     int n = d->n_bvh_nodes;
     const int nRef = n;                    // nodes of the reference's trees
     const int nGeom = d->n_triangles + d->n_quadrics;
-    const int nPrims = nGeom + d->n_instances;  // entries of bvh_prims: every triangle / quadric once, every instance once
+    const int nPrims = (int)BvhPrimCount(d);    // entries of bvh_prims: every triangle / quadric once, every instance once (no nested placements here: below)
     if (n == 0 || (size_t)nPrims >= (size_t)INST_FIRST || d->n_instances >= INST_FIRST) return false;
     for (int i = 0; i < n; ++i)
         if (L[i].nprims > 16) return false;
+    // nested placements (animated shapes inside instance definitions, wf_abi.h wf_instance) have no entry form in the production tree: such
+    // scenes keep the reference-order walks, which take the third level from BVHIntersectClosestDef / BVHIntersectAnyDef<ANIM>
+    if (NestedPlacements(d) > 0) return false;
     tris->resize((size_t)nPrims);
     for (int k = 0; k < nPrims; ++k) {
         int t = d->bvh_prims[k];
@@ -2476,7 +2558,10 @@ int wf_scene_upload(wf_ctx *ctx, const wf_scene_desc *d) {
     sv.nQuadrics = d->n_quadrics;
     if ((e = devUpload(ctx, &sv.meshes, d->meshes, (size_t)d->n_meshes))) return e;
     if ((e = devUpload(ctx, &sv.bvhNodes, d->bvh_nodes, (size_t)d->n_bvh_nodes))) return e;
-    if ((e = devUpload(ctx, &sv.bvhPrims, d->bvh_prims, (size_t)d->n_triangles + d->n_quadrics + d->n_instances))) return e;
+    // (the instance tables are range-checked before anything indexes through them, on the host or on the device)
+    int64_t counts[4];
+    if ((e = wf_scene_check_instances(d, counts))) return e;
+    if ((e = devUpload(ctx, &sv.bvhPrims, d->bvh_prims, (size_t)counts[0]))) return e;
     if ((e = devUpload(ctx, &sv.instances, d->instances, (size_t)d->n_instances))) return e;
     if ((e = devUpload(ctx, &sv.instanceDefs, d->instance_defs, (size_t)d->n_instance_defs))) return e;
     sv.nInstances = d->n_instances;
@@ -2694,6 +2779,7 @@ int wf_scene_upload(wf_ctx *ctx, const wf_scene_desc *d) {
         std::vector<FastDef> fdefs;
         std::vector<SubEntry> fsubs;
         FastDepths fdep;
+        ctx->nestedAnimated = NestedPlacements(d);
         ctx->fastOk = BuildFastBVH(d, &qn, &lt, &fdefs, &fsubs, &ctx->fast, &fdep);
         {
             // traversal stacks: LDS entries per lane + rows of `stackSpill` behind them, sized from the trees' ACTUAL depths: the
@@ -2715,7 +2801,8 @@ int wf_scene_upload(wf_ctx *ctx, const wf_scene_desc *d) {
             };
             int depthTop = d->n_bvh_nodes > 0 ? treeDepth(0) : 0, depthDef = 0;
             for (int k = 0; k < d->n_instance_defs; ++k) depthDef = std::max(depthDef, treeDepth(d->instance_defs[k].bvh_root));
-            const int needRef = depthTop + depthDef + 4;
+            // (a definition with nested placements carries a third level: a moving entity's tree on top of the definition's)
+            const int needRef = depthTop + (ctx->nestedAnimated > 0 ? 2 : 1) * depthDef + 4;
             const int needFast = 3 * fdep.top + fdep.maxLeafInstances + 3 * fdep.def + 6;
             const int rows = std::max(std::max(needRef - std::min(STACK_LDS, TSTACK), needFast - TSTACK), STACK_MAX - std::min(STACK_LDS, TSTACK));
             if (rows > 2048) return fail(-1, "BVH too deep for the traversal stacks (depth %d + %d)", depthTop, depthDef);
@@ -2785,6 +2872,7 @@ int wf_ctx_query(wf_ctx *ctx, const char *key, int64_t *value) {
     else if (k == "medium_lean") *value = ctx->mediumLean;   // k_medium_sample<true> / k_tr_segment<true>: every medium is homogeneous or a non-emissive uniform grid
     else if (k.rfind("lean_type_", 0) == 0 && atoi(key + 10) >= 0 && atoi(key + 10) < WF_MAT_NTYPES) *value = ctx->leanType[atoi(key + 10)];
     else if (k == "instances") *value = ctx->svHost.nInstances;
+    else if (k == "nested_animated") *value = ctx->nestedAnimated;
     else return fail(-1, "wf_ctx_query: unknown key '%s'", key);
     return 0;
 }

@@ -610,11 +610,11 @@ struct Interpreter {
                 e.outsideMedium = gs.currentOutsideMedium;
                 if (animated) {
                     // AnimatedShapeSceneEntity -> AnimatedPrimitive(BVH of the entity's shapes, renderFromShape) (scene.cpp:1452-1506): here a hidden
-                    // instance definition with this one entity, used once with the animated transformation RenderFromObject()
-                    if (activeInstance) Fatal(loc, "animated shapes inside an object instance definition are not supported by this build");
+                    // instance definition with this one entity, used once with the animated transformation RenderFromObject() — at the top level,
+                    // or inside the active definition (scene.cpp:287-288; renderFromShape includes renderFromWorld there too)
                     if (e.lightIndex >= 0) Fatal(loc, "Animated area lights are not supported.");   // scene.cpp:1485-1488
                     InstanceUse u;
-                    u.name = std::string("\x01animated-shape#") + std::to_string(scene->animatedShapes.size());
+                    u.name = std::string("\x01animated-shape#") + std::to_string(scene->nHiddenDefinitions++);
                     u.animated = true;
                     u.renderFromInstance = RenderFromObject();
                     u.renderFromInstanceEnd = Transform((renderFromWorld * gs.ctmEnd).m);
@@ -622,7 +622,8 @@ struct Interpreter {
                     u.loc = loc;
                     scene->instanceDefinitions[u.name].name = u.name;
                     scene->instanceDefinitions[u.name].shapes.push_back(std::move(e));
-                    scene->animatedShapes.push_back(std::move(u));
+                    if (activeInstance) activeInstance->animatedShapes.push_back(std::move(u));
+                    else scene->animatedShapes.push_back(std::move(u));
                 } else
                 if (activeInstance) activeInstance->shapes.push_back(std::move(e));
                 else scene->shapes.push_back(std::move(e));

@@ -80,7 +80,6 @@ struct ShapeEntity : Entity {
     int lightIndex = -1;
     std::string insideMedium, outsideMedium;
 };
-struct InstanceDefinition { std::string name; std::vector<ShapeEntity> shapes; };
 struct InstanceUse {
     std::string name;
     Transform renderFromInstance;   // (animated: the start-time transformation)
@@ -90,6 +89,10 @@ struct InstanceUse {
     float startTime = 0, endTime = 1;
     std::string loc;
 };
+// animatedShapes: the shapes created under an animated CTM inside the definition (scene.cpp:287-288: entity.animatedShapes), each a hidden
+// definition of its own placed INSIDE this one with the animated transformation; they follow the static shapes among the definition's
+// primitives (scene.cpp:1530-1551)
+struct InstanceDefinition { std::string name; std::vector<ShapeEntity> shapes; std::vector<InstanceUse> animatedShapes; };
 
 struct RenderOptions {  // subset of PBRTOptions (options.h)
     int seed = 0;
@@ -126,6 +129,7 @@ struct ParsedScene {
     // shapes created under an animated CTM (scene.cpp:277-290: AnimatedShapeSceneEntity): each is a hidden instance definition (its shapes in
     // object space) used once with the animated transformation; they precede the object instances among the top-level primitives (scene.cpp:1511-1577)
     std::vector<InstanceUse> animatedShapes;
+    int nHiddenDefinitions = 0;   // hidden definitions made so far (top level and nested): their names' running number
     std::vector<std::pair<std::string, Entity>> media;
     std::map<std::string, Transform> mediaTransforms;
     std::string baseDir;

@@ -2832,6 +2832,10 @@ void BuildSceneTables(const ParsedScene &scene, const RenderOptions &optIn, Scen
             auto it = scene.instanceDefinitions.find(u.name);
             if (it == scene.instanceDefinitions.end() || !seenDefs.insert(u.name).second) continue;
             for (const ShapeEntity &sh : it->second.shapes) want(sh);
+            for (const InstanceUse &nu : it->second.animatedShapes) {
+                auto nit = scene.instanceDefinitions.find(nu.name);
+                if (nit != scene.instanceDefinitions.end()) for (const ShapeEntity &sh : nit->second.shapes) want(sh);
+            }
         }
         if (files.size() >= 8) {
             std::vector<MeshSource> loaded(files.size());
@@ -2859,6 +2863,9 @@ void BuildSceneTables(const ParsedScene &scene, const RenderOptions &optIn, Scen
     // gets its own BVH; only definitions that are used are built
     std::map<std::string, int> defIndex;
     std::vector<PrimList> defPrims;
+    // per definition: its nested placements (animated shapes created inside it) — the record every use of the definition repeats
+    struct NestedPlacement { const InstanceUse *use = nullptr; wf_instance record{}; };
+    std::vector<std::vector<NestedPlacement>> defNested;
     // the animated shapes' hidden definitions first, then the object instances: the order of the reference's top-level primitives
     // (shapes, animated shapes, instances: scene.cpp:1441-1577)
     std::vector<InstanceUse> allUses(scene.animatedShapes);
@@ -2867,11 +2874,26 @@ void BuildSceneTables(const ParsedScene &scene, const RenderOptions &optIn, Scen
         auto it = scene.instanceDefinitions.find(u.name);
         if (it == scene.instanceDefinitions.end()) Die("", u.name + ": object instance not defined");
         if (defIndex.count(u.name)) continue;
-        defIndex[u.name] = (int)defPrims.size();
+        const int di = (int)defPrims.size();
+        defIndex[u.name] = di;
         defPrims.emplace_back();
+        defNested.emplace_back();
         for (const ShapeEntity &sh : it->second.shapes) {
             if (sh.lightIndex >= 0) fprintf(stderr, "Warning: %s: Area lights not supported with object instancing\n", sh.loc.c_str());
             addShape(sh, &defPrims.back(), true);
+        }
+        // the definition's animated shape entities (scene.cpp:1535-1539), after its static shapes: each a hidden definition of its own, placed
+        // inside this one once the bounds are known (below, with the instances)
+        for (const InstanceUse &nu : it->second.animatedShapes) {
+            const int hi = (int)defPrims.size();
+            defIndex[nu.name] = hi;
+            defPrims.emplace_back();
+            defNested.emplace_back();
+            for (const ShapeEntity &sh : scene.instanceDefinitions.at(nu.name).shapes) addShape(sh, &defPrims[hi], true);
+            NestedPlacement np;
+            np.use = &nu;
+            np.record.def = hi;
+            defNested[di].push_back(np);
         }
     }
     if (T->triIndices.empty() && spheres.empty()) {
@@ -3600,74 +3622,116 @@ void BuildSceneTables(const ParsedScene &scene, const RenderOptions &optIn, Scen
                 });
             for (auto &th : pool) th.join();
         }
-        // the instances (scene.cpp:1560-1577): TransformedPrimitive(definition, renderFromInstance), after the shapes
         const int nTrisAll = (int)T->triIndices.size() / 3, nQuads = (int)T->quadrics.size();
+        // AnimatedPrimitive around the aggregate with the bounds `db` (a top-level animated shape, an animated use of a definition, an animated
+        // shape inside a definition): records its AnimatedTransform, returns its Bounds()
+        auto animatedPlacement = [&](const InstanceUse &u, const B3 &db, wf_instance *in) {
+            const float b[6] = {db.pMin.x, db.pMin.y, db.pMin.z, db.pMax.x, db.pMax.y, db.pMax.z};
+            B3 wb;
+            // AnimatedPrimitive (cpu/primitive.cpp:132-153): Bounds() = renderFromPrimitive.MotionBounds(primitive.Bounds())
+            // (util/transform.cpp:1083-1096).  Without rotation that is the union of the start and end boxes — restated exactly.  WITH
+            // rotation the reference bounds every corner's path through the zeros of the motion derivative (its c1..c5 terms: 530
+            // lines of generated coefficient code, not restated): here the path of every corner is sampled at 1025 times and the box
+            // widened by the largest step between neighbouring samples, which contains the path.  A top-level box only decides which
+            // nodes a ray visits, not what it hits; the tree built over this box can differ from the reference's, which matters for
+            // the ORDER of candidates at exactly coincident geometry only (stated in DESIGN.md 2).
+            for (int j = 0; j < 3; ++j)
+                if (u.renderFromInstanceEnd.m.m[3][j] != 0 || u.renderFromInstanceEnd.m.m[3][3] != 1) Die(u.loc, "only affine animated transformations are supported");
+            // (every material: the consumers of a hit interpolate the transformation at the ray's time — the walks, the transmittance trace,
+            // the interface skip and MixMaterial resolve of the routing, the material stage: wf_shapes.h InstanceAt<ANIM>; the subsurface
+            // probes at time 0, as the reference's)
+            const wf_animated_transform A = MakeAnimatedTransform(u.renderFromInstance, u.startTime, u.renderFromInstanceEnd, u.endTime);
+            in->anim_plus1 = (int)T->animated.size() + 1;
+            T->animated.push_back(A);
+            {
+                // Transform::Decompose leaves a mirror in R ("XXX TODO FIXME deal with flip", util/transform.cpp:223): the quaternion of an
+                // improper R is not a unit one, and the reference's in-between matrices and motion bounds are off.  The matrices are
+                // restated (so the motion is the reference's); the bounds are this build's samples of it — say so.
+                const auto &m = u.renderFromInstance.m.m;
+                const float det = m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) +
+                                  m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
+                if (det < 0 && A.actually_animated)
+                    fprintf(stderr, "Warning: %s: animated transformation with a mirror: the reference's decomposition does not handle the flip; images may differ from it where its motion bounds cut the primitive\n", u.loc.c_str());
+            }
+            auto corner = [&](int c) { return V3{b[(c & 1) ? 3 : 0], b[(c & 2) ? 4 : 1], b[(c & 4) ? 5 : 2]}; };
+            if (!A.has_rotation) {
+                for (int c = 0; c < 8; ++c) wb = Union(wb, u.renderFromInstance.Point(corner(c)));
+                B3 we;
+                for (int c = 0; c < 8; ++c) we = Union(we, u.renderFromInstanceEnd.Point(corner(c)));
+                wb = Union(wb, we);
+            } else {
+                constexpr int NS = 1024;
+                float pad = 0;
+                for (int c = 0; c < 8; ++c) {
+                    V3 prev{0, 0, 0};
+                    for (int k = 0; k <= NS; ++k) {
+                        const float time = u.startTime + (u.endTime - u.startTime) * ((float)k / NS);
+                        const V3 q = AnimatedAt(A, k == 0 ? u.startTime : k == NS ? u.endTime : time).Point(corner(c));
+                        wb = Union(wb, q);
+                        if (k > 0) pad = std::max(pad, Length(q - prev));
+                        prev = q;
+                    }
+                }
+                wb.pMin = wb.pMin - V3{pad, pad, pad};
+                wb.pMax = wb.pMax + V3{pad, pad, pad};
+            }
+            return wb;
+        };
+        // (nested: an animated shape inside a definition — its hidden definition's name is no message for a user: the Shape's location instead)
+        auto requireAffine = [&](const InstanceUse &u, bool nested = false) {
+            for (int j = 0; j < 3; ++j)
+                if (u.renderFromInstance.m.m[3][j] != 0 || u.renderFromInstance.m.m[3][3] != 1) {
+                    if (nested) Die(u.loc, "only affine transformations are supported for an animated shape inside an object instance definition");
+                    Die("", u.name + ": only affine instance transformations are supported");
+                }
+        };
+        // the animated shapes inside definitions (scene.cpp:1535-1551): AnimatedPrimitive(the entity's aggregate, renderFromShape) joins the
+        // definition's primitives after its static shapes, under MotionBounds of the entity's box; the definition's tree and root box are built over that
+        for (size_t d = 0; d < defPrims.size(); ++d) {
+            if (defNested[d].empty()) continue;
+            std::vector<NestedPlacement> kept;
+            for (NestedPlacement &np : defNested[d]) {
+                if (defPrims[np.record.def].empty()) continue;   // (an entity whose shapes made no primitive)
+                requireAffine(*np.use, true);
+                np.record.render_from_instance = np.use->renderFromInstance.abi();
+                const B3 nb = animatedPlacement(*np.use, defBounds[np.record.def], &np.record);
+                for (int c = 0; c < 3; ++c)
+                    if (!std::isfinite(nb.pMin[c]) || !std::isfinite(nb.pMax[c])) Die(np.use->loc, "the bounds of an animated shape are not finite (its transformation?)");
+                defPrims[d].emplace_back(nTrisAll + nQuads + (int)kept.size(), nb);
+                kept.push_back(np);
+            }
+            defNested[d] = kept;
+            requireFinite(defPrims[d], "object instance definition");
+            B3 b;
+            for (const auto &p : defPrims[d]) b = Union(b, p.second);
+            defBounds[d] = b;
+        }
+        // the instances (scene.cpp:1560-1577): TransformedPrimitive(definition, renderFromInstance), after the shapes
         for (const InstanceUse &u : allUses) {
             const int d = defIndex.at(u.name);
             if (defPrims[d].empty()) continue;  // empty instance
             wf_instance in{};
             in.render_from_instance = u.renderFromInstance.abi();
-            for (int j = 0; j < 3; ++j)
-                if (u.renderFromInstance.m.m[3][j] != 0 || u.renderFromInstance.m.m[3][3] != 1) Die("", u.name + ": only affine instance transformations are supported");
+            requireAffine(u);
             in.def = d;
             // TransformedPrimitive::Bounds = (*renderFromPrimitive)(primitive.Bounds()): the 8 corners (util/transform.cpp:134-139)
             const B3 &db = defBounds[d];
             const float b[6] = {db.pMin.x, db.pMin.y, db.pMin.z, db.pMax.x, db.pMax.y, db.pMax.z};
             B3 wb;
-            if (u.animated) {
-                // AnimatedPrimitive (cpu/primitive.cpp:132-153): Bounds() = renderFromPrimitive.MotionBounds(primitive.Bounds())
-                // (util/transform.cpp:1083-1096).  Without rotation that is the union of the start and end boxes — restated exactly.  WITH
-                // rotation the reference bounds every corner's path through the zeros of the motion derivative (its c1..c5 terms: 530
-                // lines of generated coefficient code, not restated): here the path of every corner is sampled at 1025 times and the box
-                // widened by the largest step between neighbouring samples, which contains the path.  A top-level box only decides which
-                // nodes a ray visits, not what it hits; the tree built over this box can differ from the reference's, which matters for
-                // the ORDER of candidates at exactly coincident geometry only (stated in DESIGN.md 2).
-                for (int j = 0; j < 3; ++j)
-                    if (u.renderFromInstanceEnd.m.m[3][j] != 0 || u.renderFromInstanceEnd.m.m[3][3] != 1) Die(u.loc, "only affine animated transformations are supported");
-                // (every material: the consumers of a hit interpolate the transformation at the ray's time — the walks, the transmittance trace,
-                // the interface skip and MixMaterial resolve of the routing, the material stage: wf_shapes.h InstanceAt<ANIM>; the subsurface
-                // probes at time 0, as the reference's)
-                const wf_animated_transform A = MakeAnimatedTransform(u.renderFromInstance, u.startTime, u.renderFromInstanceEnd, u.endTime);
-                in.anim_plus1 = (int)T->animated.size() + 1;
-                T->animated.push_back(A);
-                {
-                    // Transform::Decompose leaves a mirror in R ("XXX TODO FIXME deal with flip", util/transform.cpp:223): the quaternion of an
-                    // improper R is not a unit one, and the reference's in-between matrices and motion bounds are off.  The matrices are
-                    // restated (so the motion is the reference's); the bounds are this build's samples of it — say so.
-                    const auto &m = u.renderFromInstance.m.m;
-                    const float det = m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) +
-                                      m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
-                    if (det < 0 && A.actually_animated)
-                        fprintf(stderr, "Warning: %s: animated transformation with a mirror: the reference's decomposition does not handle the flip; images may differ from it where its motion bounds cut the primitive\n", u.loc.c_str());
-                }
-                auto corner = [&](int c) { return V3{b[(c & 1) ? 3 : 0], b[(c & 2) ? 4 : 1], b[(c & 4) ? 5 : 2]}; };
-                if (!A.has_rotation) {
-                    for (int c = 0; c < 8; ++c) wb = Union(wb, u.renderFromInstance.Point(corner(c)));
-                    B3 we;
-                    for (int c = 0; c < 8; ++c) we = Union(we, u.renderFromInstanceEnd.Point(corner(c)));
-                    wb = Union(wb, we);
-                } else {
-                    constexpr int NS = 1024;
-                    float pad = 0;
-                    for (int c = 0; c < 8; ++c) {
-                        V3 prev{0, 0, 0};
-                        for (int k = 0; k <= NS; ++k) {
-                            const float time = u.startTime + (u.endTime - u.startTime) * ((float)k / NS);
-                            const V3 q = AnimatedAt(A, k == 0 ? u.startTime : k == NS ? u.endTime : time).Point(corner(c));
-                            wb = Union(wb, q);
-                            if (k > 0) pad = std::max(pad, Length(q - prev));
-                            prev = q;
-                        }
-                    }
-                    wb.pMin = wb.pMin - V3{pad, pad, pad};
-                    wb.pMax = wb.pMax + V3{pad, pad, pad};
-                }
-            } else
-            for (int c = 0; c < 8; ++c) wb = Union(wb, u.renderFromInstance.Point(V3{b[(c & 1) ? 3 : 0], b[(c & 2) ? 4 : 1], b[(c & 4) ? 5 : 2]}));
+            if (u.animated) wb = animatedPlacement(u, db, &in);
+            else for (int c = 0; c < 8; ++c) wb = Union(wb, u.renderFromInstance.Point(V3{b[(c & 1) ? 3 : 0], b[(c & 2) ? 4 : 1], b[(c & 4) ? 5 : 2]}));
             for (int c = 0; c < 3; ++c)
                 if (!std::isfinite(wb.pMin[c]) || !std::isfinite(wb.pMax[c])) Die("", u.name + ": the bounds of an object instance are not finite (its transformation?)");
             topPrims.emplace_back(nTrisAll + nQuads + (int)T->instances.size(), wb);
+            const int outer = (int)T->instances.size();
+            if (!defNested[d].empty()) in.nested_first = outer + 1;
             T->instances.push_back(in);
+            // one record per nested placement of this use (include/wf_abi.h wf_instance): a hit names the pair (use, moving entity) by its index
+            for (const NestedPlacement &np : defNested[d]) {
+                wf_instance rec = np.record;
+                rec.outer_plus1 = outer + 1;
+                T->instances.push_back(rec);
+            }
         }
         std::string topError;
         std::thread topBuild([&] {

@@ -44,6 +44,7 @@ class StressRandom(random.Random):
 
 STRESS = False
 EXTENDED_OPTIONS = False
+NESTED_ANIMATED = False   # --nested-animated: a definition may hold a moving entity (off: every seed generates the scene it always did)
 
 
 class Gen:
@@ -440,7 +441,14 @@ class Gen:
         if have_def:
             solid = [m for m in self.materials if m[1] != "interface"]
             def_mat = self.pick(solid) if solid else ("m0", self.materials[0][1] if self.materials else "diffuse")
-            out.append('ObjectBegin "thing"\n  NamedMaterial "%s"\n  %s\n  Translate 0 0 1.2\n  %s\nObjectEnd' % (def_mat[0], self.shape(), self.shape()))
+            first, second = self.shape(), self.shape()
+            if NESTED_ANIMATED and self.r.random() < 0.5:
+                # an animated shape inside the definition (scene.cpp:287-288): a translation, half of the time a scale too, no rotation (see placed())
+                anim = "ActiveTransform EndTime\n  Translate %s\n" % f(self.u(-0.6, 0.6), self.u(-0.6, 0.6), self.u(-0.3, 0.5))
+                if self.r.random() < 0.5:
+                    anim += "  Scale %s\n" % f(self.u(0.7, 1.4), self.u(0.7, 1.4), self.u(0.7, 1.4))
+                second = anim + "  ActiveTransform All\n  " + second
+            out.append('ObjectBegin "thing"\n  NamedMaterial "%s"\n  %s\n  Translate 0 0 1.2\n  %s\nObjectEnd' % (def_mat[0], first, second))
         for i in range(self.r.randrange(2, 7)):
             name, t = self.pick(self.materials)
             body = '  NamedMaterial "%s"\n' % name
@@ -508,10 +516,12 @@ def main():
     ap.add_argument("--first", type=int, default=0, help="index of the first scene of the seed's sequence (re-run one scene: --first I --n 1)")
     ap.add_argument("--options", action="store_true", help="also draw the Option directives disablepixeljitter / disablewavelengthjitter / disabletexturefiltering / seed / displacementedgescale")
     ap.add_argument("--stress", action="store_true", help="rare grammar features two to three times as often (StressRandom)")
+    ap.add_argument("--nested-animated", action="store_true", help="half of the object instance definitions hold a shape under an animated CTM (an AnimatedPrimitive inside the definition)")
     a = ap.parse_args()
-    global STRESS, EXTENDED_OPTIONS
+    global STRESS, EXTENDED_OPTIONS, NESTED_ANIMATED
     STRESS = a.stress
     EXTENDED_OPTIONS = a.options
+    NESTED_ANIMATED = a.nested_animated
     work = tempfile.mkdtemp(prefix="wf_diff_")
     stats = {"identical": 0, "both_refuse": 0, "mismatch": 0, "status_differs": 0}
     for i in range(a.first, a.first + a.n):

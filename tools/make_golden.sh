@@ -169,4 +169,9 @@ oracle/_ref/pbrt_ref --wavefront --quiet --seed 0 --spp 4 --outfile $G/animated_
 oracle/_ref/pbrt_ref --wavefront --quiet --seed 0 --spp 4 --outfile $G/animated_mix_ref.pfm $G/animated_mix.pbrt
 oracle/_ref/pbrt_ref --wavefront --quiet --seed 0 --spp 4 --outfile $G/animated_subsurface_ref.pfm $G/animated_subsurface.pbrt
 oracle/_ref/pbrt_ref --wavefront --quiet --seed 0 --spp 4 --outfile $G/animated_light_ref.pfm $G/animated_light.pbrt
+# animated shapes inside object-instance definitions (hand-written scenes): triangles; general primitives; a moving interface; subsurface
+oracle/_ref/pbrt_ref --wavefront --quiet --seed 0 --spp 4 --outfile $G/animated_in_definition_ref.pfm $G/animated_in_definition.pbrt
+oracle/_ref/pbrt_ref --wavefront --quiet --seed 0 --spp 4 --outfile $G/animated_in_definition_general_ref.pfm $G/animated_in_definition_general.pbrt
+oracle/_ref/pbrt_ref --wavefront --quiet --seed 0 --spp 4 --outfile $G/animated_in_definition_media_ref.pfm $G/animated_in_definition_media.pbrt
+oracle/_ref/pbrt_ref --wavefront --quiet --seed 0 --spp 4 --outfile $G/animated_in_definition_sss_ref.pfm $G/animated_in_definition_sss.pbrt
 oracle/_ref/pbrt_ref --wavefront --quiet --seed 0 --spp 4 --outfile $G/face_indices_ref.pfm $G/face_indices.pbrt
