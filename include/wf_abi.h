@@ -830,6 +830,13 @@ int wf_debug_fastbvh_check(const wf_scene_desc *d, int n_rays, uint64_t seed, in
    nested placement animated and without nested placements of its own).  out (may be null): [0] entries of bvh_prims the trees index,
    [1] top-level instance records, [2] nested-placement records, [3] nested placements named by the definitions' leaves. */
 int wf_scene_check_instances(const wf_scene_desc *d, int64_t out[4]);
+/* Host-only form of wf_ctx_query (no device and no context needed; CPU suite, tests/test_scene_plan_host.py): runs the planning step of
+   wf_scene_upload on `d` under the current environment switches (every check of the description, the classification, the production
+   trees) and answers the keys that follow from the description alone: "fast_ok", "gen_mode", "gen_tri", "defer_general", "anim_fast",
+   "lean_shade", "lean_type_<material type>", "rare_lights", "medium_lean", "instances", "nested_animated".  A description that
+   wf_scene_upload would reject fails here with the same message.  Every call plans the scene anew, tree build included: meant for
+   tests and tools on small scenes, not for asking many keys of a large one. */
+int wf_scene_plan_query(const wf_scene_desc *d, const char *key, int64_t *value);
 
 #ifdef __cplusplus
 }

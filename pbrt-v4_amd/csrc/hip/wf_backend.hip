@@ -66,8 +66,8 @@ constexpr int MAX_GRID = 256 * 8;  // 256 CUs x up to 8 resident 256-thread work
 
 struct SpillArea { int *base; int rows; int *dbg; };   // the context's stackSpill rows + the debug words (kernel argument of the production traversal)
 
-// The production walk kernels of the uploaded scene and their resident grids: filled once, by PickWalkKernels at the end of the traversal
-// set-up of wf_scene_upload, the only place that turns (genMode, genTri, deferGeneral, animFast, nInstances) into template instantiations.
+// The production walk kernels of the uploaded scene and their resident grids: filled once, by PickWalkKernels in the traversal step of
+// wf_scene_upload, the only place that turns the plan's (genMode, genTri, deferGeneral, animFast, nInstances) into template instantiations.
 // Every launch below goes through these pointers, so the kernel whose occupancy sized a grid is the kernel launched on it.
 // (every instantiation of a walk kernel template has the signature of its pointer type)
 using ClosestWalkFn = void (*)(const SceneView, WorkState, FastBVH, int, SpillArea, int *, int, const int *);   // k_closest_fast
@@ -90,6 +90,91 @@ struct WalkKernels {
     TraceAnyFn traceAny = nullptr;
 };
 
+// ---------------------------------------------------------------------------------------------
+// The environment switches of context creation, scene upload and queue allocation, read in one place.  Each of those three calls takes a
+// fresh copy when it runs (the tests set switches between calls); the code they steer sees values, not the environment.
+struct Switches {
+    bool shadeTris = true;        // WF_SHADE_TRIS=0: the indexed vertex tables only (wf_scene.h ShadeTri)
+    bool gridCorners = true;      // WF_GRID_CORNERS=0: no corner-packed copies of the density grids
+    double gridCornersGB = 32.0;  // WF_GRID_CORNERS_GB: tables beyond this many gigabytes in all are left out
+    bool mediumLean = true;       // WF_MEDIUM_LEAN=0
+    bool leanShade = true;        // WF_LEAN_SHADE=0
+    bool leanPerType = true;      // WF_LEAN_PER_TYPE=0
+    int deferGeneral = -1;        // WF_DEFER_GENERAL=1 | 0 forces / forbids the two-class traversal; -1 (unset): by the scene's counts
+    bool noFast = false;          // WF_NO_FAST (set to anything): the reference-order walks only
+    bool animFast = true;         // WF_ANIM_FAST=0
+    bool pixelMajor = true;       // WF_PIXEL_MAJOR=0: items of a pass ordered sample by sample
+    bool noSampleTops = false;    // WF_NO_SAMPLE_TOPS (set to anything)
+    int trWavefront = -1;         // WF_TR_WAVEFRONT (wf_ctx::trWavefront)
+    int frameOverlap = 1;         // WF_FRAME_OVERLAP: 0 | 1 | 2 (wf_ctx::frameOverlap)
+    bool samplesShaded = true;    // WF_SAMPLES_SHADED=0
+    bool traceLaunch = false;     // WF_TRACE_LAUNCH (set to anything)
+    bool scratchPrime = true;     // WF_SCRATCH_PRIME=0
+    static Switches FromEnv() {
+        auto isSet = [](const char *name) { return getenv(name) != nullptr; };
+        auto on = [](const char *name) { const char *e = getenv(name); return !(e && atoi(e) == 0); };   // on unless set to 0
+        auto number = [](const char *name, int unset) { const char *e = getenv(name); return e ? atoi(e) : unset; };
+        Switches s;
+        s.shadeTris = on("WF_SHADE_TRIS");
+        s.gridCorners = on("WF_GRID_CORNERS");
+        if (const char *e = getenv("WF_GRID_CORNERS_GB")) s.gridCornersGB = atof(e);
+        s.mediumLean = on("WF_MEDIUM_LEAN");
+        s.leanShade = on("WF_LEAN_SHADE");
+        s.leanPerType = on("WF_LEAN_PER_TYPE");
+        if (isSet("WF_DEFER_GENERAL")) s.deferGeneral = number("WF_DEFER_GENERAL", 0) != 0;
+        s.noFast = isSet("WF_NO_FAST");
+        s.animFast = on("WF_ANIM_FAST");
+        s.pixelMajor = on("WF_PIXEL_MAJOR");
+        s.noSampleTops = isSet("WF_NO_SAMPLE_TOPS");
+        s.trWavefront = number("WF_TR_WAVEFRONT", -1);
+        s.frameOverlap = std::min(2, std::max(0, number("WF_FRAME_OVERLAP", 1)));
+        s.samplesShaded = on("WF_SAMPLES_SHADED");
+        s.traceLaunch = isSet("WF_TRACE_LAUNCH");
+        s.scratchPrime = on("WF_SCRATCH_PRIME");
+        return s;
+    }
+};
+
+// Everything decided about a scene: a pure function of the description and the switches (PlanScene), made before anything is uploaded.
+// wf_ctx::plan is the one copy; wf_scene_plan_query gives the same answers without a context.
+struct ScenePlan {
+    // what the description holds (the upload copies these into SceneView)
+    int64_t nBvhPrims = 0;       // entries of bvh_prims the trees index (wf_scene_check_instances)
+    int nInstances = 0;
+    int nestedAnimated = 0;      // records of `instances` that are nested placements (animated shapes inside instance definitions); such scenes keep the reference-order walks
+    bool haveAlpha = false, texNeedsFootprint = false, haveMix = false, haveSubsurface = false, haveQuadricAlpha = false, haveCurves = false, haveAnimated = false;
+    int matTypeMask = 0;
+    bool matPresent[WF_MAT_NTYPES] = {};
+    // the stage kernels' variants
+    bool mediumLean = false;     // every medium is homogeneous or a non-emissive uniform grid: k_medium_sample<true>
+    bool portalLights = false;   // the scene has a portal infinite light (k_handle_escaped<RARE>)
+    bool leanShade = false;      // the scene qualifies for the lean shade kernels (SceneLean)
+    // ... per MATERIAL TYPE since round 6: a type none of whose materials sits on a quadric / patch / curve keeps its lean shade kernel
+    // when such shapes appear elsewhere in the scene (their hits are items of other types' queues)
+    bool leanType[WF_MAT_NTYPES] = {};
+    bool rareLights = false;     // the scene has a light type only the VARIANT 2 material kernels sample (portal infinite lights)
+    // the walk kernels' variants (PickWalkKernels turns these into template instantiations)
+    int genMode = 0;             // general-primitive strength of the traversal kernels: 0 triangles only, 1 simple alpha, 2 anything but curves and alpha on quadrics, 3 anything (see GeneralPrims)
+    bool deferGeneral = false;   // TWO-CLASS TRAVERSAL (see WalkKernels)
+    int genTri = 0;
+    bool fastBuilt = false;      // BuildFastBVH gave a production layout (FastTrees): it is uploaded, in use or not
+    bool fastOk = false;         // ... and the scene's walks use it; false (leaf sizes > 16, nested placements, WF_NO_FAST, ...): the reference-order kernels only
+    bool animFast = false;       // the scene's AnimatedPrimitives are walked by the production kernels' ANIM variants (round 6; genMode <= 1 only)
+    int cursorChunk = 2;         // 64-ray batches a closest-hit wave takes per cursor fetch (chosen from the tree size)
+    int cursorChunkShadow = 2;   // ... an any-hit wave (round 6, with the descent scheduling, 10 M-triangle scene: closest-hit 27.7 ms at 1, 26.7 at 3, 27.0 at 4, 27.4 at 8, 29.9 at 16;
+                                 // any-hit 12.15 at 1, 12.16 at 3, 12.4 at 4, 13.0 at 8: profiles/r06_cursor_chunk_ab_sm16.txt)
+                                 // (-3 %), but on a 30 k-triangle scene one fetch per 64 rays is 83 atomics/us on one counter: the kernel's bound
+    int spillRows = 0;           // rows of wf_ctx::stackSpill behind the LDS stack entries, from the trees' depths
+};
+// The production traversal layout as BuildFastBVH leaves it on the host: what the upload copies once PlanScene has succeeded.
+struct FastTrees {
+    std::vector<QNode> nodes;
+    std::vector<LeafTri> tris;
+    std::vector<FastDef> defs;
+    std::vector<SubEntry> subs;
+    FastBVH header{};
+};
+
 struct wf_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -98,12 +183,10 @@ struct wf_ctx {
     const SceneView *svDev = nullptr;  // the same struct in device memory, for the out-of-line callbacks of the traversal kernels
     WorkState ws{};
     int maxQueueSize = 0;
-    int *stackSpill = nullptr;   // [rows][MAX_GRID*BLOCK], rows from the trees' depths (wf_scene_upload)
-    int spillRows = 0;
+    int *stackSpill = nullptr;   // [plan.spillRows][MAX_GRID*BLOCK]
     int *dbgWords = nullptr;     // [4] spilled stack entries, stack-overflow flag, inline near-tie re-traces, cursor path taken (wf_debug_counters)
-    SpillArea spillArea() const { return SpillArea{stackSpill, spillRows, dbgWords}; }
+    SpillArea spillArea() const { return SpillArea{stackSpill, plan.spillRows, dbgWords}; }
     FastBVH fast{};              // production traversal layout (wf_traverse.h); built at upload
-    bool fastOk = false;         // false: leaf sizes > 16 -> only the reference-order kernels are used
     hipStream_t stream2 = nullptr;   // the near-tie re-trace runs here, beside the routing pass and the next stage's sample generation
     hipEvent_t evFork = nullptr, evJoin = nullptr;
     bool retracePending = false, deferJoin = false;
@@ -126,25 +209,9 @@ struct wf_ctx {
     // per-lane loop keeps its state in registers; with object instances the per-lane alternative is the reference-order walk (1 wave / SIMD)
     int trWavefront = -1;
     bool cursorDirty[2] = {false, false};   // the closest-hit / any-hit work cursor has been used since a k_reset last zeroed it
-    bool mediumLean = false;     // every medium is homogeneous or a non-emissive uniform grid: k_medium_sample<true>
-    bool portalLights = false;   // the scene has a portal infinite light (k_handle_escaped<RARE>)
-    bool leanShade = false;      // the scene qualifies for the lean shade kernels (SceneLean: set at upload)
-    // ... per MATERIAL TYPE since round 6: a type none of whose materials sits on a quadric / patch / curve keeps its lean shade kernel
-    // when such shapes appear elsewhere in the scene (their hits are items of other types' queues)
-    bool leanType[WF_MAT_NTYPES] = {};
-    bool rareLights = false;     // the scene has a light type only the VARIANT 2 material kernels sample (portal infinite lights)
-    int genMode = 0;             // general-primitive strength of the traversal kernels: 0 triangles only, 1 simple alpha, 2 anything but curves and alpha on quadrics, 3 anything (see GeneralPrims)
-    bool deferGeneral = false;   // TWO-CLASS TRAVERSAL (see WalkKernels)
-    int genTri = 0;
-    int nestedAnimated = 0;      // records of `instances` that are nested placements (animated shapes inside instance definitions); such scenes keep the reference-order walks
-    bool animFast = false;       // the scene's AnimatedPrimitives are walked by the production kernels' ANIM variants (round 6; genMode <= 1 only)
+    ScenePlan plan;              // what the uploaded scene runs: written by PlanScene, read by PickWalkKernels, the launch sites and wf_queues_alloc
     WalkKernels walk;
-    int cursorChunk = 2;         // 64-ray batches a closest-hit wave takes per cursor fetch (chosen from the tree size at upload)
-    int cursorChunkShadow = 2;   // ... an any-hit wave (round 6, with the descent scheduling, 10 M-triangle scene: closest-hit 27.7 ms at 1, 26.7 at 3, 27.0 at 4, 27.4 at 8, 29.9 at 16;
-                                 // any-hit 12.15 at 1, 12.16 at 3, 12.4 at 4, 13.0 at 8: profiles/r06_cursor_chunk_ab_sm16.txt)
-                                 // (-3 %), but on a 30 k-triangle scene one fetch per 64 rays is 83 atomics/us on one counter: the kernel's bound
     int32_t *probeCursor = nullptr;
-    bool matPresent[WF_MAT_NTYPES] = {};
     int W = 0, H = 0;
     int maxDepth = 5;
     float sceneBounds[6] = {};
@@ -166,8 +233,13 @@ struct wf_ctx {
 // (the transmittance queues; ws.sq refilled between the two stages).  Scenes with animated primitives too: their closest-hit walk
 // stores the path's time (ws.pathTime) that the any-hit walk's rays read.  The reference-order walks (!fastOk) are not worth it.
 static bool FrameOverlapScene(const wf_ctx *ctx) {
-    return ctx->frameOverlap > 0 && ctx->fastOk && !ctx->svHost.haveMedia && !ctx->svHost.haveSubsurface && !ctx->svHost.haveAnimated;
+    return ctx->frameOverlap > 0 && ctx->plan.fastOk && !ctx->svHost.haveMedia && !ctx->svHost.haveSubsurface && !ctx->svHost.haveAnimated;
 }
+// ... and the context has the second set of spill rows that walk needs (a profiling / tracing / counting pass is serial all the same)
+static bool FrameOverlapActive(const wf_ctx *ctx) { return FrameOverlapScene(ctx) && ctx->stackSpill2 != nullptr; }
+// The fused pass draws no ray samples at the last depth, where it leaves before the material stage, their only reader (media and
+// subsurface scenes keep the launch: their scatter stages are not that loop's material stage)
+static bool SkipLastSamples(const wf_ctx *ctx) { return ctx->samplesShaded && !ctx->svHost.haveMedia && !ctx->svHost.haveSubsurface; }
 constexpr int FRAME_OVERLAP_THIN_DEPTH = 2;   // WF_FRAME_OVERLAP=2: the depths from here on (8 % of the spec scene's rays) are the "thin" ones
 
 template <typename T>
@@ -175,8 +247,8 @@ static int devAlloc(wf_ctx *c, T **p, size_t n) {
     void *d = nullptr;
     size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
     HIPCHK(hipMalloc(&d, bytes));
-    HIPCHK(hipMemsetAsync(d, 0, bytes, c->stream));
     c->allocs.push_back(d);
+    HIPCHK(hipMemsetAsync(d, 0, bytes, c->stream));
     *p = (T *)d;
     return 0;
 }
@@ -195,6 +267,45 @@ static int devUpload(wf_ctx *c, wf::GPtr<const T> *p, const T *src, size_t n) { 
     if (int e = devUpload(c, &d, src, n)) return e;
     *p = d;
     return 0;
+}
+
+// The device scratch of one boundary call (wf_trace_*_host, the probes): freed when the call returns, on whichever path.
+struct DeviceScratch {
+    hipStream_t stream;
+    std::vector<void *> ptrs;
+    explicit DeviceScratch(hipStream_t s) : stream(s) {}
+    DeviceScratch(const DeviceScratch &) = delete;
+    DeviceScratch &operator=(const DeviceScratch &) = delete;
+    ~DeviceScratch() { for (void *p : ptrs) (void)hipFree(p); }   // (hipFree waits for the work that uses the memory)
+    template <typename T>
+    int alloc(T **dst, size_t n) {
+        void *p = nullptr;
+        HIPCHK(hipMalloc(&p, n * sizeof(T)));
+        ptrs.push_back(p);
+        *dst = (T *)p;
+        return 0;
+    }
+    template <typename T>
+    int zeroed(T **dst, size_t n) {
+        if (int e = alloc(dst, n)) return e;
+        HIPCHK(hipMemsetAsync(*dst, 0, n * sizeof(T), stream));
+        return 0;
+    }
+    template <typename T, typename S>
+    int upload(T **dst, const S *src, size_t n) {   // n elements of T from src (S: T, or void for a caller's untyped array)
+        if (int e = alloc(dst, n)) return e;
+        HIPCHK(hipMemcpyAsync(*dst, src, n * sizeof(T), hipMemcpyHostToDevice, stream));
+        return 0;
+    }
+};
+// n rays as the trace kernels read them: (o, d, tmax), seven floats each
+static std::vector<float> PackRays7(const float *o, const float *d, const float *tmax, int n) {
+    std::vector<float> rays((size_t)n * 7);
+    for (int i = 0; i < n; ++i) {
+        for (int k = 0; k < 3; ++k) { rays[(size_t)i * 7 + k] = o[3 * i + k]; rays[(size_t)i * 7 + 3 + k] = d[3 * i + k]; }
+        rays[(size_t)i * 7 + 6] = tmax[i];
+    }
+    return rays;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -271,7 +382,7 @@ __device__ inline unsigned long long waveSum(unsigned long long v) {
 }
 
 // ANIM: the scene has animated shapes / instances (AnimatedPrimitive, round 5): the walk interpolates their transformation at the ray's time.
-// Such scenes are walked by these reference-order kernels only (no production tree: ctx->fastOk is false for them).
+// Such scenes are walked by these reference-order kernels only (no production tree: ctx->plan.fastOk is false for them).
 template <bool COUNT, bool ANIM = false>
 __global__ void __launch_bounds__(BLOCK) k_intersect_closest(const SceneView sv, WorkState ws, int cur, int *stackSpill) {
     const int n = ws.counters[(CNT_RAY0 + cur) * CNT_STRIDE];
@@ -1193,7 +1304,7 @@ __global__ void __launch_bounds__(BLOCK) k_resolve_mix(const SceneView sv, WorkS
 #endif
 // (round 6, measured and dropped: a persistent form of this kernel with wave-level refill of the delta-tracking loop, VERDICT r5 item 8 —
 //  a wave whose active lanes dropped below a threshold took new items for its idle lanes from a shared work cursor)
-// LEAN: every medium of the scene is homogeneous or a non-emissive uniform grid (ctx->mediumLean, set at upload): the kernel is built without the
+// LEAN: every medium of the scene is homogeneous or a non-emissive uniform grid (ctx->plan.mediumLean, set at upload): the kernel is built without the
 // procedural cloud, NanoVDB, RGB-grid and blackbody code and compiled for WF_MEDIUM_WAVES_LEAN waves
 #ifndef WF_MEDIUM_WAVES_LEAN
 #define WF_MEDIUM_WAVES_LEAN 3
@@ -1242,7 +1353,7 @@ struct TrPrims {  // the same callbacks for the transmittance walk, whose ray is
     __device__ bool accept(int prim, float b0, float b1, float b2) const { return AlphaTestPasses(sv, prim, b0, b1, b2, o, d); }
     __device__ bool sphere(int prim, float tMax, QuadricHit *qh) const { return QuadricIntersect(sv, prim, o, d, tMax, qh); }
 };
-// MLEAN: the lean medium code (ctx->mediumLean, as k_medium_sample<true>)
+// MLEAN: the lean medium code (ctx->plan.mediumLean, as k_medium_sample<true>)
 template <bool ALPHA, bool MLEAN = false>
 __global__ void __launch_bounds__(TBLOCK) k_shadow_tr_fast(const SceneView sv, WorkState ws, FastBVH bvh, SpillArea sp) {
     const int n = ws.counters[(CNT_SHADOW) * CNT_STRIDE];
@@ -2330,21 +2441,21 @@ static typename K::Fn PickWalk(int genx, bool inst, std::integer_sequence<int, G
 static int PickWalkKernels(wf_ctx *ctx) {
     using QueueWalks = std::integer_sequence<int, 0, 1, 2, 3, GenX(0, true, false), GenX(1, true, false), GenX(0, false, true), GenX(1, false, true)>;
     const bool inst = ctx->svHost.nInstances > 0;
-    const int gen = ctx->genMode;
+    const int gen = ctx->plan.genMode;
     // what every ray of a queue walks through: the triangle kernel that hands general primitives over, or the scene's one kernel
-    const int first = ctx->deferGeneral ? GenX(ctx->genTri, true, false) : GenX(gen, false, ctx->animFast);
+    const int first = ctx->plan.deferGeneral ? GenX(ctx->plan.genTri, true, false) : GenX(gen, false, ctx->plan.animFast);
     WalkKernels k;
     k.closest = PickWalk<ClosestWalk>(first, inst, QueueWalks{});
     k.shadow = PickWalk<ShadowWalk>(first, inst, QueueWalks{});
-    if (ctx->deferGeneral) {
+    if (ctx->plan.deferGeneral) {
         k.closestGen = PickWalk<ClosestWalk>(gen, inst, QueueWalks{});
         k.shadowGen = PickWalk<ShadowWalk>(gen, inst, QueueWalks{});
     }
     k.traceClosest = PickWalk<TraceClosestWalk>(gen, inst, std::integer_sequence<int, 0, 1, 2, 3>{});
     k.traceAny = PickWalk<TraceAnyWalk>(gen, inst, std::integer_sequence<int, 0, 1, 2, 3>{});
     if (RetraceInline(gen)) k.trTrace = PickWalk<TrTraceWalk>(gen, inst, std::integer_sequence<int, 0, 1>{});   // (resolves its near ties inside the walk)
-    if (!k.closest || !k.shadow || !k.traceClosest || !k.traceAny || (ctx->deferGeneral && (!k.closestGen || !k.shadowGen)) || (RetraceInline(gen) && !k.trTrace))
-        return fail(-1, "no walk kernel for this scene (genMode %d, genTri %d, two-class %d, animated %d, instances %d)", gen, ctx->genTri, (int)ctx->deferGeneral, (int)ctx->animFast, (int)inst);
+    if (!k.closest || !k.shadow || !k.traceClosest || !k.traceAny || (ctx->plan.deferGeneral && (!k.closestGen || !k.shadowGen)) || (RetraceInline(gen) && !k.trTrace))
+        return fail(-1, "no walk kernel for this scene (genMode %d, genTri %d, two-class %d, animated %d, instances %d)", gen, ctx->plan.genTri, (int)ctx->plan.deferGeneral, (int)ctx->plan.animFast, (int)inst);
     // resident workgroups of the queue walks (closest-hit and shadow differ in registers)
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, ctx->device));
@@ -2357,9 +2468,217 @@ static int PickWalkKernels(wf_ctx *ctx) {
     };
     int e;
     if ((e = residentGrid(k.closest, &k.grid)) || (e = residentGrid(k.shadow, &k.gridShadow))) return e;
-    if (ctx->deferGeneral && ((e = residentGrid(k.closestGen, &k.gridGen)) || (e = residentGrid(k.shadowGen, &k.gridShadowGen)))) return e;
+    if (ctx->plan.deferGeneral && ((e = residentGrid(k.closestGen, &k.gridGen)) || (e = residentGrid(k.shadowGen, &k.gridShadowGen)))) return e;
     ctx->walk = k;
     return 0;
+}
+
+// ---- the scene's plan (ScenePlan) ------------------------------------------------------------------------------------------------
+// PlanScene, in its order: check the description, classify it, build the production trees, decide the walks.  Host code without a HIP
+// call: wf_scene_upload runs it before it allocates anything (a rejected description leaves the context as it was), and
+// wf_scene_plan_query runs it without a context.
+
+// Every array the five interpolants of measured material i point to must lie inside table_data (the kernels index them unchecked)
+static int CheckMeasuredTable(const wf_scene_desc *d, int i) {
+    const int64_t nT = d->n_table_floats, h = d->materials[i].measured_table;
+    if (h < 0 || h + WF_MEASURED_HEADER_WORDS > nT) return fail(-1, "measured material %d: header outside table_data", i);
+    auto word = [&](int64_t k) { int32_t v; memcpy(&v, &d->table_data[h + k], 4); return (int64_t)v; };
+    static const int nParams[5] = {0, 0, 2, 2, 3};
+    static const bool hasCdf[5] = {false, false, true, true, false};
+    for (int k = 0; k < 5; ++k) {
+        const int64_t b = 16 + 16 * k, sx = word(b), sy = word(b + 1);
+        if (sx < 2 || sy < 2 || sx > (1 << 20) || sy > (1 << 20)) return fail(-1, "measured material %d: interpolant %d has size %lld x %lld", i, k, (long long)sx, (long long)sy);
+        int64_t slices = 1;
+        for (int p = nParams[k] - 1; p >= 0; --p) {
+            const int64_t ps = word(b + 2 + p), st = word(b + 5 + p), po = word(b + 8 + p);
+            if (ps < 1 || ps > (1 << 20) || po < 0 || po + ps > nT || st != (ps > 1 ? slices : 0)) return fail(-1, "measured material %d: interpolant %d, parameter %d invalid", i, k, p);
+            slices *= ps;
+            if (slices > nT) return fail(-1, "measured material %d: interpolant %d larger than table_data", i, k);
+        }
+        const int64_t dataOff = word(b + 11), margOff = word(b + 12), condOff = word(b + 13);
+        if (dataOff < 0 || dataOff + slices * sx * sy > nT) return fail(-1, "measured material %d: interpolant %d data outside table_data", i, k);
+        if (hasCdf[k] && (margOff < 0 || margOff + slices * sy > nT || condOff < 0 || condOff + slices * sx * sy > nT))
+            return fail(-1, "measured material %d: interpolant %d cdf outside table_data", i, k);
+    }
+    return 0;
+}
+// Step 1: everything that rejects a description, before anything indexes through its tables (on the host or on the device).
+// counts: wf_scene_check_instances' out.
+static int CheckAbi(const wf_scene_desc *d) {
+    return d->abi_version == WF_ABI_VERSION ? 0 : fail(-1, "ABI version mismatch: desc %d, library %d", d->abi_version, WF_ABI_VERSION);
+}
+static int CheckScene(const wf_scene_desc *d, int64_t counts[4]) {
+    if (int e = CheckAbi(d)) return e;
+    if (d->sampler.type == WF_SAMPLER_SOBOL && (!d->sobol_matrices || !d->vdc_sobol || !d->vdc_sobol_inv)) return fail(-1, "the Sobol sampler needs the sobol_matrices / vdc_sobol tables");
+    if (int e = wf_scene_check_instances(d, counts)) return e;
+    if (d->sampler.type < WF_SAMPLER_ZSOBOL || d->sampler.type > WF_SAMPLER_SOBOL) return fail(-1, "unknown sampler type %d", d->sampler.type);
+    if (d->sampler.type == WF_SAMPLER_HALTON && (!d->halton_primes || (d->sampler.randomize == WF_RAND_PERMUTE_DIGITS && (!d->halton_perm_offsets || !d->halton_perms))))
+        return fail(-1, "Halton sampler without its prime / digit-permutation tables");
+    for (int i = 0; i < d->n_materials; ++i) {
+        const wf_material &m = d->materials[i];
+        if (m.type == WF_MAT_MIX) {
+            if (m.mix[0] < 0 || m.mix[0] >= d->n_materials || m.mix[1] < 0 || m.mix[1] >= d->n_materials || m.mix[0] >= i || m.mix[1] >= i)
+                return fail(-1, "mix material %d must name two earlier materials", i);
+            continue;
+        }
+        if (m.type < 0 || m.type >= WF_MAT_NTYPES) return fail(-1, "material %d has unknown type %d", i, m.type);
+        if (m.type == WF_MAT_SUBSURFACE && (m.sss_table < 0 || (size_t)m.sss_table + BSSRDF_TABLE_FLOATS > (size_t)d->n_table_floats))
+            return fail(-1, "subsurface material %d: BSSRDF table outside table_data", i);
+        if (m.type == WF_MAT_MEASURED)
+            if (int e = CheckMeasuredTable(d, i)) return e;
+    }
+    if (d->film.type == WF_FILM_SPECTRAL && (d->film.n_buckets < 1 || d->film.n_buckets > 4096 || !(d->film.lambda_max > d->film.lambda_min)))
+        return fail(-1, "spectral film: bad bucket count / wavelength range");
+    return 0;
+}
+// Step 2: what the scene holds, and which variants of the stage and walk kernels that asks for.
+static void ClassifyScene(const wf_scene_desc *d, const Switches &sw, ScenePlan *plan) {
+    plan->nInstances = d->n_instances;
+    plan->nestedAnimated = NestedPlacements(d);
+    plan->haveAnimated = d->n_animated > 0;
+    for (int i = 0; i < d->n_meshes; ++i)
+        if (d->meshes[i].alpha_tex >= 0) plan->haveAlpha = true;
+    for (int i = 0; i < d->n_textures; ++i)
+        if (d->textures[i].type >= WF_TEX_FLOAT_IMAGE) plan->texNeedsFootprint = true;
+    for (int i = 0; i < d->n_materials; ++i)
+        if (d->materials[i].displacement >= 0 || d->materials[i].normalmap >= 0) plan->texNeedsFootprint = true;
+    // the lean delta-tracking kernel (k_medium_sample<true>): no procedural cloud, NanoVDB, RGB grid or emissive grid in the scene (WF_MEDIUM_LEAN=0: off)
+    plan->mediumLean = d->n_media > 0 && sw.mediumLean;
+    for (int m = 0; m < d->n_media; ++m)
+        if (!(d->media[m].type == WF_MEDIUM_HOMOGENEOUS || (d->media[m].type == WF_MEDIUM_GRID && !d->media[m].is_emissive))) plan->mediumLean = false;
+    // the lean shade kernels (wf_scene.h "LEAN DEVICE VARIANTS"): no quadrics / patches / curves, every texture a constant, an image map or a
+    // bilerp (WF_LEAN_SHADE=0 turns them off)
+    bool simpleTextures = true;
+    for (int i = 0; i < d->n_textures && simpleTextures; ++i)
+        if (!wf::IsSimpleFloatTexture(d->textures[i].type) && !wf::IsSimpleSpectrumTexture(d->textures[i].type)) simpleTextures = false;
+    plan->leanShade = d->n_quadrics == 0 && d->n_animated == 0 && sw.leanShade && simpleTextures;
+    {
+        // the material types met on shapes that are not triangles (through MixMaterials, whose hits join the queue of the chosen material's type)
+        bool onGeneral[WF_MAT_NTYPES] = {};
+        std::vector<int> todo;
+        for (int i = 0; i < d->n_quadrics; ++i) {
+            const int m = d->meshes[d->quadrics[i].mesh].material;
+            if (m >= 0 && m < d->n_materials) todo.push_back(m);
+        }
+        std::vector<char> seen((size_t)std::max(d->n_materials, 1), 0);
+        while (!todo.empty()) {
+            const int m = todo.back();
+            todo.pop_back();
+            if (m < 0 || m >= d->n_materials || seen[m]) continue;
+            seen[m] = 1;
+            const int t = d->materials[m].type;
+            if (t == WF_MAT_MIX) { todo.push_back(d->materials[m].mix[0]); todo.push_back(d->materials[m].mix[1]); }
+            else if (t >= 0 && t < WF_MAT_NTYPES) onGeneral[t] = true;
+        }
+        const bool wanted = sw.leanShade && sw.leanPerType;
+        for (int t = 0; t < WF_MAT_NTYPES; ++t) plan->leanType[t] = plan->leanShade || (wanted && simpleTextures && d->n_animated == 0 && !onGeneral[t]);
+    }
+    // ... and, since round 5, emitters that are not triangles (sphere / disk / cylinder / patch / curve lights: an out-of-line sampler of
+    // 214 VGPRs) and emitters with an alpha texture (the texture-graph evaluator): LightSampleLi<RARE>, AreaLightL<ALPHA> (wf_lights.h)
+    for (int i = 0; i < d->n_lights; ++i) {
+        const wf_light &l = d->lights[i];
+        if (l.type == WF_LIGHT_PORTAL_INFINITE) plan->rareLights = plan->portalLights = true;
+        if (l.type == WF_LIGHT_DIFFUSE_AREA && (l.tri >= d->n_triangles || l.alpha_tex_plus1 != 0)) plan->rareLights = true;
+    }
+    for (int i = 0; i < d->n_quadrics; ++i) {
+        if (d->meshes[d->quadrics[i].mesh].alpha_tex >= 0) plan->haveQuadricAlpha = true;
+        if (d->quadrics[i].type == WF_QUADRIC_CURVE) plan->haveCurves = true;
+    }
+    for (int i = 0; i < d->n_materials; ++i) {
+        const int t = d->materials[i].type;
+        if (t == WF_MAT_MIX) { plan->haveMix = true; continue; }
+        plan->matPresent[t] = true;
+        plan->matTypeMask |= 1 << t;
+        if (t == WF_MAT_SUBSURFACE) plan->haveSubsurface = true;
+    }
+    if (d->n_quadrics > 0) plan->genMode = (plan->haveCurves || plan->haveQuadricAlpha) ? 3 : 2;
+    int alphaGen = 0;   // what the TRIANGLES of the scene ask of the walk: 0 nothing, 1 simple alpha cut-outs, 2 texture-graph alpha
+    for (int i = 0; i < d->n_meshes && alphaGen < 2; ++i)
+        if (d->meshes[i].alpha_tex >= 0) {
+            const int tt = d->textures[d->meshes[i].alpha_tex].type;
+            // the inline test looks an image map up without a footprint (MIPFilterFloatZeroP): uv-mapped, not EWA-filtered
+            const wf_texture &at = d->textures[d->meshes[i].alpha_tex];
+            const bool lean = tt == WF_TEX_FLOAT_CONSTANT || (at.mapping == WF_TEXMAP_UV && (tt != WF_TEX_FLOAT_IMAGE || d->tex_images[at.i0].filter != WF_MIP_EWA));
+            alphaGen = std::max(alphaGen, ((tt == WF_TEX_FLOAT_CONSTANT || tt == WF_TEX_FLOAT_IMAGE || tt == WF_TEX_FLOAT_BILERP) && lean) ? 1 : 2);
+        }
+    plan->genMode = std::max(plan->genMode, alphaGen);
+    // TWO-CLASS TRAVERSAL: the scene's quadrics / patches / curves are few beside its triangles, and the triangles themselves need no
+    // more than the simple alpha test — the triangle kernels walk first, the general kernels only the rays handed over
+    // (WF_DEFER_GENERAL=1 | 0 forces / forbids it for any scene with such shapes)
+    plan->genTri = std::min(alphaGen, 1);
+    if (d->n_quadrics > 0 && alphaGen <= 1 && plan->genMode >= 2) {
+        const bool few = (int64_t)d->n_quadrics * 16 <= (int64_t)d->n_triangles;
+        plan->deferGeneral = sw.deferGeneral >= 0 ? sw.deferGeneral != 0 : few;
+    }
+}
+// levels of the reference's binary tree under `root`
+static int RefTreeDepth(const wf_scene_desc *d, int root) {
+    int best = 0;
+    if (root < 0 || root >= d->n_bvh_nodes) return best;
+    std::vector<std::pair<int, int>> st{{root, 1}};
+    while (!st.empty()) {
+        auto [i, dep] = st.back();
+        st.pop_back();
+        best = std::max(best, dep);
+        if (d->bvh_nodes[i].nprims == 0) { st.push_back({i + 1, dep + 1}); st.push_back({d->bvh_nodes[i].offset, dep + 1}); }
+    }
+    return best;
+}
+static int PlanScene(const wf_scene_desc *d, const Switches &sw, ScenePlan *plan, FastTrees *trees) {
+    *plan = ScenePlan{};
+    int64_t counts[4];
+    if (int e = CheckScene(d, counts)) return e;
+    plan->nBvhPrims = counts[0];
+    ClassifyScene(d, sw, plan);
+    // Step 3: the production trees, and the traversal stacks behind them.
+    FastDepths fdep;
+    plan->fastBuilt = BuildFastBVH(d, &trees->nodes, &trees->tris, &trees->defs, &trees->subs, &trees->header, &fdep);
+    {
+        // LDS entries per lane + rows of `stackSpill` behind them, sized from the trees' ACTUAL depths: the
+        // reference-order walk pushes one sibling per level of the reference's binary trees (top level, then an instance
+        // definition's on top); the four-wide production walk up to three per level of ITS collapsed trees (BuildFastBVH records
+        // their depths: the greedy largest-area collapse does not halve the depth of an unbalanced tree), one entry per instance
+        // of a leaf, and the two instance markers.  A push past the rows is dropped and flagged (LdsStackT, wf_sync).
+        int depthTop = d->n_bvh_nodes > 0 ? RefTreeDepth(d, 0) : 0, depthDef = 0;
+        for (int k = 0; k < d->n_instance_defs; ++k) depthDef = std::max(depthDef, RefTreeDepth(d, d->instance_defs[k].bvh_root));
+        // (a definition with nested placements carries a third level: a moving entity's tree on top of the definition's)
+        const int needRef = depthTop + (plan->nestedAnimated > 0 ? 2 : 1) * depthDef + 4;
+        const int needFast = 3 * fdep.top + fdep.maxLeafInstances + 3 * fdep.def + 6;
+        plan->spillRows = std::max(std::max(needRef - std::min(STACK_LDS, TSTACK), needFast - TSTACK), STACK_MAX - std::min(STACK_LDS, TSTACK));
+        if (plan->spillRows > 2048) return fail(-1, "BVH too deep for the traversal stacks (depth %d + %d)", depthTop, depthDef);
+    }
+    // Step 4: which walks use the trees.
+    plan->fastOk = plan->fastBuilt && !sw.noFast;
+    if (plan->fastBuilt) {
+        // rays of a scene whose trees do not fit the caches walk long enough for one cursor fetch per 64 rays (measured: -3 % on
+        // the 10 M-triangle scene); a cache-resident scene traces so fast that the cursor's atomics would bound it (see cursorChunk)
+        const bool big = trees->nodes.size() * sizeof(QNode) + trees->tris.size() * sizeof(LeafTri) > ((size_t)256 << 20);
+        plan->cursorChunk = big ? 3 : 2;
+        plan->cursorChunkShadow = big ? 1 : 2;
+    }
+    // AnimatedPrimitive: the production walks' ANIM variants (triangles + simple alpha cut-outs, two-level: an animated shape entity is an
+    // instance) interpolate the transformation per ray since round 6; scenes that also hold quadrics / curves / texture-graph alpha keep the
+    // reference-order walks (WF_ANIM_FAST=0: every animated scene does)
+    plan->animFast = d->n_animated > 0 && plan->fastOk && plan->genMode <= 1 && plan->nInstances > 0 && sw.animFast;
+    if (d->n_animated > 0 && !plan->animFast) plan->fastOk = false;
+    return 0;
+}
+// The answers of wf_ctx_query / wf_scene_plan_query that the plan alone gives; false: not one of its keys.
+static bool PlanValue(const ScenePlan &plan, const char *key, int64_t *value) {
+    const std::string k = key;
+    if (k == "fast_ok") *value = plan.fastOk;
+    else if (k == "gen_mode") *value = plan.genMode;
+    else if (k == "gen_tri") *value = plan.genTri;
+    else if (k == "defer_general") *value = plan.deferGeneral;
+    else if (k == "anim_fast") *value = plan.animFast;
+    else if (k == "lean_shade") *value = plan.leanShade;
+    else if (k == "rare_lights") *value = plan.rareLights;
+    else if (k == "medium_lean") *value = plan.mediumLean;   // k_medium_sample<true> / k_tr_segment<true>: every medium is homogeneous or a non-emissive uniform grid
+    else if (k.rfind("lean_type_", 0) == 0 && atoi(key + 10) >= 0 && atoi(key + 10) < WF_MAT_NTYPES) *value = plan.leanType[atoi(key + 10)];
+    else if (k == "instances") *value = plan.nInstances;
+    else if (k == "nested_animated") *value = plan.nestedAnimated;
+    else return false;
+    return true;
 }
 
 extern "C" {
@@ -2369,32 +2688,28 @@ int wf_abi_version(void) { return WF_ABI_VERSION; }
 
 int wf_debug_fastbvh_check(const wf_scene_desc *d, int n_rays, uint64_t seed, int64_t out[8]) {
     if (!d || !out || n_rays < 0) return fail(-1, "wf_debug_fastbvh_check: bad arguments");
-    std::vector<QNode> qn;
-    std::vector<LeafTri> lt;
-    std::vector<FastDef> fdefs;
-    std::vector<SubEntry> fsubs;
-    FastBVH fast{};
+    FastTrees trees;
     FastDepths fdep;
     for (int k = 0; k < 8; ++k) out[k] = 0;
-    if (!BuildFastBVH(d, &qn, &lt, &fdefs, &fsubs, &fast, &fdep)) return fail(-1, "wf_debug_fastbvh_check: the scene has no production layout");
-    out[0] = (int64_t)qn.size(); out[1] = (int64_t)lt.size(); out[2] = (int64_t)fsubs.size(); out[3] = fdep.top;
+    if (!BuildFastBVH(d, &trees.nodes, &trees.tris, &trees.defs, &trees.subs, &trees.header, &fdep)) return fail(-1, "wf_debug_fastbvh_check: the scene has no production layout");
+    out[0] = (int64_t)trees.nodes.size(); out[1] = (int64_t)trees.tris.size(); out[2] = (int64_t)trees.subs.size(); out[3] = fdep.top;
     // structure: every child reference names a node / a leaf run / an entry inside the arrays
-    for (size_t i = 0; i < qn.size(); ++i)
+    for (size_t i = 0; i < trees.nodes.size(); ++i)
         for (int c = 0; c < 4; ++c) {
-            const int r = qn[i].child[c];
+            const int r = trees.nodes[i].child[c];
             if (r == NODE_NONE) continue;
-            if (r >= 0) { if ((size_t)r >= qn.size()) return fail(-1, "wf_debug_fastbvh_check: node %zu child %d out of range", i, c); continue; }
+            if (r >= 0) { if ((size_t)r >= trees.nodes.size()) return fail(-1, "wf_debug_fastbvh_check: node %zu child %d out of range", i, c); continue; }
             const unsigned u = ~(unsigned)r;
             const size_t first = u >> 4, count = (u & 15u) + 1;
-            if (first >= (size_t)INST_FIRST ? first - INST_FIRST >= fsubs.size() : first + count > lt.size()) return fail(-1, "wf_debug_fastbvh_check: node %zu child %d: leaf run out of range", i, c);
+            if (first >= (size_t)INST_FIRST ? first - INST_FIRST >= trees.subs.size() : first + count > trees.tris.size()) return fail(-1, "wf_debug_fastbvh_check: node %zu child %d: leaf run out of range", i, c);
         }
-    for (const SubEntry &se : fsubs)
-        if (se.inst < 0 || se.inst >= d->n_instances || (se.node >= 0 && (size_t)se.node >= qn.size())) return fail(-1, "wf_debug_fastbvh_check: entry out of range");
+    for (const SubEntry &se : trees.subs)
+        if (se.inst < 0 || se.inst >= d->n_instances || (se.node >= 0 && (size_t)se.node >= trees.nodes.size())) return fail(-1, "wf_debug_fastbvh_check: entry out of range");
     // coverage with random rays through the scene's box
     uint64_t rng = seed * 0x9E3779B97F4A7C15ull + 0xD1B54A32D192ED03ull;
     auto rnd = [&]() { rng ^= rng << 13; rng ^= rng >> 7; rng ^= rng << 17; return (double)(rng >> 11) * (1.0 / 9007199254740992.0); };
     const wf_bvh_node &root = d->bvh_nodes[0];
-    CheckWalk cw{qn, lt, fdefs, fsubs, d, fast, {}};
+    CheckWalk cw{trees.nodes, trees.tris, trees.defs, trees.subs, d, trees.header, {}};
     const int nGeom = d->n_triangles + d->n_quadrics;
     for (int r = 0; r < n_rays; ++r) {
         double o[3], dir[3], tgt[3];
@@ -2405,7 +2720,7 @@ int wf_debug_fastbvh_check(const wf_scene_desc *d, int n_rays, uint64_t seed, in
             dir[a] = tgt[a] - o[a];
         }
         cw.tested.clear();
-        cw.Tree(0, fast.base, fast.cell, -1, o, dir);
+        cw.Tree(0, trees.header.base, trees.header.cell, -1, o, dir);
         std::sort(cw.tested.begin(), cw.tested.end());
         out[6] += (int64_t)cw.tested.size();
         auto check = [&](int tri, int inst, const double oo[3], const double dd[3]) {
@@ -2451,6 +2766,47 @@ __global__ void k_scratch_prime(int *out, int n) {
     for (int i = 0; i < n; ++i) buf[(i * 131) % SCRATCH_PRIME_WORDS] = i;
     out[threadIdx.x] = buf[(n * 7) % SCRATCH_PRIME_WORDS];
 }
+// (what wf_ctx_create made so far, or a whole context: null members are skipped)
+static void DestroyCtx(wf_ctx *ctx) {
+    (void)hipSetDevice(ctx->device);
+    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+    if (ctx->stream3) (void)hipStreamSynchronize(ctx->stream3);
+    for (void *p : ctx->allocs) (void)hipFree(p);
+    for (auto &e : ctx->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
+    for (auto e : ctx->eventPool) (void)hipEventDestroy(e);
+    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
+    if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
+    if (ctx->stream3) (void)hipStreamDestroy(ctx->stream3);
+    if (ctx->evShadowFork) (void)hipEventDestroy(ctx->evShadowFork);
+    if (ctx->evShadowJoin) (void)hipEventDestroy(ctx->evShadowJoin);
+    if (ctx->evFork) (void)hipEventDestroy(ctx->evFork);
+    if (ctx->evJoin) (void)hipEventDestroy(ctx->evJoin);
+    delete ctx;
+}
+static int InitCtx(wf_ctx *c, const Switches &sw) {
+    HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    HIPCHK(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
+    HIPCHK(hipStreamCreateWithFlags(&c->stream3, hipStreamNonBlocking));
+    HIPCHK(hipEventCreateWithFlags(&c->evFork, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&c->evJoin, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&c->evShadowFork, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&c->evShadowJoin, hipEventDisableTiming));
+    c->frameOverlap = sw.frameOverlap;
+    c->samplesShaded = sw.samplesShaded;
+    c->traceLaunch = sw.traceLaunch;
+    if (sw.scratchPrime) {
+        DeviceScratch tmp(c->stream);
+        int *out = nullptr;
+        if (int e = tmp.alloc(&out, (size_t)64)) return e;
+        hipLaunchKernelGGL(k_scratch_prime, dim3(1), dim3(64), 0, c->stream, out, 8);
+        hipLaunchKernelGGL(k_scratch_prime, dim3(1), dim3(64), 0, c->stream2, out, 8);
+        hipLaunchKernelGGL(k_scratch_prime, dim3(1), dim3(64), 0, c->stream3, out, 8);
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream2));
+        HIPCHK(hipStreamSynchronize(c->stream3));
+    }
+    return 0;
+}
 int wf_ctx_create(int device, wf_ctx **out) {
     if (!out) return fail(-1, "null out");
     int ndev = 0;
@@ -2460,47 +2816,13 @@ int wf_ctx_create(int device, wf_ctx **out) {
     HIPCHK(hipSetDevice(device));
     wf_ctx *c = new wf_ctx();
     c->device = device;
-    HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&c->stream3, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&c->evFork, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&c->evJoin, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&c->evShadowFork, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&c->evShadowJoin, hipEventDisableTiming));
-    if (const char *e = getenv("WF_FRAME_OVERLAP")) c->frameOverlap = std::min(2, std::max(0, atoi(e)));
-    if (const char *e = getenv("WF_SAMPLES_SHADED")) c->samplesShaded = atoi(e) != 0;
-    c->traceLaunch = getenv("WF_TRACE_LAUNCH") != nullptr;
-    if (const char *e = getenv("WF_SCRATCH_PRIME"); !e || atoi(e) != 0) {
-        int *tmp = nullptr;
-        HIPCHK(hipMalloc(&tmp, 64 * sizeof(int)));
-        hipLaunchKernelGGL(k_scratch_prime, dim3(1), dim3(64), 0, c->stream, tmp, 8);
-        hipLaunchKernelGGL(k_scratch_prime, dim3(1), dim3(64), 0, c->stream2, tmp, 8);
-        hipLaunchKernelGGL(k_scratch_prime, dim3(1), dim3(64), 0, c->stream3, tmp, 8);
-        HIPCHK(hipStreamSynchronize(c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream2));
-        HIPCHK(hipStreamSynchronize(c->stream3));
-        HIPCHK(hipFree(tmp));
-    }
+    if (int e = InitCtx(c, Switches::FromEnv())) { DestroyCtx(c); return e; }   // (g_err keeps the failing call's message)
     *out = c;
     return 0;
 }
 
 int wf_ctx_destroy(wf_ctx *ctx) {
-    if (!ctx) return 0;
-    (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->stream3) (void)hipStreamSynchronize(ctx->stream3);
-    for (void *p : ctx->allocs) (void)hipFree(p);
-    for (auto &e : ctx->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-    for (auto e : ctx->eventPool) (void)hipEventDestroy(e);
-    (void)hipStreamDestroy(ctx->stream);
-    if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
-    if (ctx->stream3) (void)hipStreamDestroy(ctx->stream3);
-    if (ctx->evShadowFork) (void)hipEventDestroy(ctx->evShadowFork);
-    if (ctx->evShadowJoin) (void)hipEventDestroy(ctx->evShadowJoin);
-    if (ctx->evFork) (void)hipEventDestroy(ctx->evFork);
-    if (ctx->evJoin) (void)hipEventDestroy(ctx->evJoin);
-    delete ctx;
+    if (ctx) DestroyCtx(ctx);
     return 0;
 }
 
@@ -2512,7 +2834,7 @@ int wf_sync(wf_ctx *ctx) {
     if (ctx->dbgWords) {
         int overflow = 0;
         HIPCHK(hipMemcpy(&overflow, ctx->dbgWords + 1, sizeof(int), hipMemcpyDeviceToHost));
-        if (overflow) return fail(-1, "traversal stack overflow: a walk needed more than %d + %d node-stack entries (results are incomplete)", TSTACK, ctx->spillRows);
+        if (overflow) return fail(-1, "traversal stack overflow: a walk needed more than %d + %d node-stack entries (results are incomplete)", TSTACK, ctx->plan.spillRows);
         int unresolved = 0;
         HIPCHK(hipMemcpy(&unresolved, ctx->dbgWords + 6, sizeof(int), hipMemcpyDeviceToHost));
         if (unresolved & 1) return fail(-1, "a near-tie re-walk found no hit where the production walk had one (results are incomplete)");
@@ -2549,12 +2871,10 @@ int wf_debug_counters(wf_ctx *ctx, uint64_t out[4], int reset) {
 }
 void *wf_stream(wf_ctx *ctx) { return ctx ? (void *)ctx->stream : nullptr; }
 
-int wf_scene_upload(wf_ctx *ctx, const wf_scene_desc *d) {
-    if (!ctx || !d) return fail(-1, "null argument");
-    if (d->abi_version != WF_ABI_VERSION) return fail(-1, "ABI version mismatch: desc %d, library %d", d->abi_version, WF_ABI_VERSION);
-    if (ctx->sceneLoaded) return fail(-1, "a scene is already uploaded to this context");
-    HIPCHK(hipSetDevice(ctx->device));
+// The first step of the upload after PlanScene: the description's tables, the ones derived from them, and the scalars of SceneView.
+static int UploadTables(wf_ctx *ctx, const wf_scene_desc *d, const Switches &sw) {
     SceneView &sv = ctx->svHost;
+    const ScenePlan &plan = ctx->plan;
     int e = 0;
     if ((e = devUpload(ctx, &sv.P, d->P, (size_t)3 * d->n_vertices))) return e;
     if ((e = devUpload(ctx, &sv.N, d->N, (size_t)3 * d->n_vertices))) return e;
@@ -2564,7 +2884,7 @@ int wf_scene_upload(wf_ctx *ctx, const wf_scene_desc *d) {
     if ((e = devUpload(ctx, &sv.triMesh, d->tri_mesh, (size_t)d->n_triangles + d->n_quadrics))) return e;
     // the de-indexed per-triangle vertex records of the material stage (wf_scene.h ShadeTri); WF_SHADE_TRIS=0: the indexed tables only
     sv.shadeTris = nullptr;
-    if (d->n_triangles > 0 && !(getenv("WF_SHADE_TRIS") && atoi(getenv("WF_SHADE_TRIS")) == 0)) {
+    if (d->n_triangles > 0 && sw.shadeTris) {
         std::vector<ShadeTri> st((size_t)d->n_triangles);
         for (size_t t = 0; t < (size_t)d->n_triangles; ++t) {
             const int32_t *ix = d->tri_indices + 3 * t;
@@ -2587,22 +2907,18 @@ int wf_scene_upload(wf_ctx *ctx, const wf_scene_desc *d) {
         (e = devUpload(ctx, &sv.vdcSobol, d->vdc_sobol, d->vdc_sobol ? (size_t)25 * 52 : (size_t)0)) ||
         (e = devUpload(ctx, &sv.vdcSobolInv, d->vdc_sobol_inv, d->vdc_sobol_inv ? (size_t)26 * 52 : (size_t)0)))
         return e;
-    if (d->sampler.type == WF_SAMPLER_SOBOL && (!d->sobol_matrices || !d->vdc_sobol || !d->vdc_sobol_inv)) return fail(-1, "the Sobol sampler needs the sobol_matrices / vdc_sobol tables");
     if ((e = devUpload(ctx, &sv.haltonPrimes, d->halton_primes, d->halton_primes ? (size_t)1000 : (size_t)0))) return e;
     if ((e = devUpload(ctx, &sv.haltonPermOffsets, d->halton_perm_offsets, d->halton_perm_offsets ? (size_t)1000 : (size_t)0))) return e;
     if ((e = devUpload(ctx, &sv.haltonPerms, d->halton_perms, (size_t)d->n_halton_perms))) return e;
     sv.nQuadrics = d->n_quadrics;
     if ((e = devUpload(ctx, &sv.meshes, d->meshes, (size_t)d->n_meshes))) return e;
     if ((e = devUpload(ctx, &sv.bvhNodes, d->bvh_nodes, (size_t)d->n_bvh_nodes))) return e;
-    // (the instance tables are range-checked before anything indexes through them, on the host or on the device)
-    int64_t counts[4];
-    if ((e = wf_scene_check_instances(d, counts))) return e;
-    if ((e = devUpload(ctx, &sv.bvhPrims, d->bvh_prims, (size_t)counts[0]))) return e;
+    if ((e = devUpload(ctx, &sv.bvhPrims, d->bvh_prims, (size_t)plan.nBvhPrims))) return e;
     if ((e = devUpload(ctx, &sv.instances, d->instances, (size_t)d->n_instances))) return e;
     if ((e = devUpload(ctx, &sv.instanceDefs, d->instance_defs, (size_t)d->n_instance_defs))) return e;
-    sv.nInstances = d->n_instances;
+    sv.nInstances = plan.nInstances;
     if ((e = devUpload(ctx, &sv.animated, d->animated, (size_t)d->n_animated))) return e;
-    sv.haveAnimated = d->n_animated > 0;
+    sv.haveAnimated = plan.haveAnimated;
     sv.nTriangles = d->n_triangles;
     sv.nBvhNodes = d->n_bvh_nodes;
     if ((e = devUpload(ctx, &sv.spectra, d->spectra, (size_t)d->n_spectra))) return e;
@@ -2635,9 +2951,8 @@ int wf_scene_upload(wf_ctx *ctx, const wf_scene_desc *d) {
         // just uploaded.  WF_GRID_CORNERS=0: none (A/B); tables beyond WF_GRID_CORNERS_GB (default 32) gigabytes in all are left out
         sv.gridCorners = nullptr;
         sv.gridCornerBase = nullptr;
-        const char *knob = getenv("WF_GRID_CORNERS");
-        if (d->n_media > 0 && !(knob && atoi(knob) == 0)) {
-            const double budget = (getenv("WF_GRID_CORNERS_GB") ? atof(getenv("WF_GRID_CORNERS_GB")) : 32.0) * 1024.0 * 1024.0 * 1024.0;
+        if (d->n_media > 0 && sw.gridCorners) {
+            const double budget = sw.gridCornersGB * 1024.0 * 1024.0 * 1024.0;
             std::vector<long long> base(d->n_media, -1);
             size_t total = 0;
             for (int m = 0; m < d->n_media; ++m) {
@@ -2675,224 +2990,112 @@ int wf_scene_upload(wf_ctx *ctx, const wf_scene_desc *d) {
     sv.filter = d->filter;
     if ((e = devUpload(ctx, &sv.filterData, d->filter_data, (size_t)d->n_filter_floats))) return e;
     sv.sampler = d->sampler;
-    if (d->sampler.type < WF_SAMPLER_ZSOBOL || d->sampler.type > WF_SAMPLER_SOBOL) return fail(-1, "unknown sampler type %d", d->sampler.type);
-    if (d->sampler.type == WF_SAMPLER_HALTON && (!d->halton_primes || (d->sampler.randomize == WF_RAND_PERMUTE_DIGITS && (!d->halton_perm_offsets || !d->halton_perms))))
-        return fail(-1, "Halton sampler without its prime / digit-permutation tables");
-    static uint32_t sobol[WF_SOBOL_WORDS];
-    FillSobol2D(sobol);
-    if ((e = devUpload(ctx, &sv.sobol, sobol, (size_t)WF_SOBOL_WORDS))) return e;
-    sv.texNeedsFootprint = 0;
-    sv.haveAlpha = 0;
-    for (int i = 0; i < d->n_meshes; ++i)
-        if (d->meshes[i].alpha_tex >= 0) sv.haveAlpha = 1;
-    for (int i = 0; i < d->n_textures; ++i)
-        if (d->textures[i].type >= WF_TEX_FLOAT_IMAGE) sv.texNeedsFootprint = 1;
-    for (int i = 0; i < d->n_materials; ++i)
-        if (d->materials[i].displacement >= 0 || d->materials[i].normalmap >= 0) sv.texNeedsFootprint = 1;
+    // (filled once per process: uploads of several contexts run on several threads)
+    static const std::vector<uint32_t> sobol = [] { std::vector<uint32_t> t(WF_SOBOL_WORDS); FillSobol2D(t.data()); return t; }();
+    if ((e = devUpload(ctx, &sv.sobol, sobol.data(), sobol.size()))) return e;
+    sv.texNeedsFootprint = plan.texNeedsFootprint;
+    sv.haveAlpha = plan.haveAlpha;
     sv.maxDepth = d->max_depth;
     sv.regularize = d->regularize;
     sv.haveMedia = d->have_media;
-    // the lean delta-tracking kernel (k_medium_sample<true>): no procedural cloud, NanoVDB, RGB grid or emissive grid in the scene (WF_MEDIUM_LEAN=0: off)
-    ctx->mediumLean = d->n_media > 0 && !(getenv("WF_MEDIUM_LEAN") && atoi(getenv("WF_MEDIUM_LEAN")) == 0);
-    for (int m = 0; m < d->n_media; ++m)
-        if (!(d->media[m].type == WF_MEDIUM_HOMOGENEOUS || (d->media[m].type == WF_MEDIUM_GRID && !d->media[m].is_emissive))) ctx->mediumLean = false;
     sv.options = d->options;
-    for (int m = 0; m < WF_MAT_NTYPES; ++m) ctx->matPresent[m] = false;
-    sv.matTypeMask = 0;
-    sv.haveMix = 0;
-    sv.haveSubsurface = 0;
-    ctx->rareLights = ctx->portalLights = false;
-    // the lean shade kernels (wf_scene.h "LEAN DEVICE VARIANTS"): no quadrics / patches / curves, every texture a constant, an image map or a
-    // bilerp (WF_LEAN_SHADE=0 turns them off)
-    ctx->leanShade = d->n_quadrics == 0 && d->n_animated == 0 && !(getenv("WF_LEAN_SHADE") && atoi(getenv("WF_LEAN_SHADE")) == 0);
-    bool simpleTextures = true;
-    for (int i = 0; i < d->n_textures && simpleTextures; ++i)
-        if (!wf::IsSimpleFloatTexture(d->textures[i].type) && !wf::IsSimpleSpectrumTexture(d->textures[i].type)) simpleTextures = false;
-    ctx->leanShade = ctx->leanShade && simpleTextures;
-    {
-        // the material types met on shapes that are not triangles (through MixMaterials, whose hits join the queue of the chosen material's type)
-        bool onGeneral[WF_MAT_NTYPES] = {};
-        std::vector<int> todo;
-        for (int i = 0; i < d->n_quadrics; ++i) {
-            const int m = d->meshes[d->quadrics[i].mesh].material;
-            if (m >= 0 && m < d->n_materials) todo.push_back(m);
-        }
-        std::vector<char> seen((size_t)std::max(d->n_materials, 1), 0);
-        while (!todo.empty()) {
-            const int m = todo.back();
-            todo.pop_back();
-            if (m < 0 || m >= d->n_materials || seen[m]) continue;
-            seen[m] = 1;
-            const int t = d->materials[m].type;
-            if (t == WF_MAT_MIX) { todo.push_back(d->materials[m].mix[0]); todo.push_back(d->materials[m].mix[1]); }
-            else if (t >= 0 && t < WF_MAT_NTYPES) onGeneral[t] = true;
-        }
-        const bool wanted = !(getenv("WF_LEAN_SHADE") && atoi(getenv("WF_LEAN_SHADE")) == 0) && !(getenv("WF_LEAN_PER_TYPE") && atoi(getenv("WF_LEAN_PER_TYPE")) == 0);
-        for (int t = 0; t < WF_MAT_NTYPES; ++t) ctx->leanType[t] = ctx->leanShade || (wanted && simpleTextures && d->n_animated == 0 && !onGeneral[t]);
+    sv.matTypeMask = plan.matTypeMask;
+    sv.haveMix = plan.haveMix;
+    sv.haveSubsurface = plan.haveSubsurface;
+    sv.haveQuadricAlpha = plan.haveQuadricAlpha;
+    sv.haveCurves = plan.haveCurves;
+    return 0;
+}
+// ... then the traversal stacks, the production trees and the kernels that walk them
+static int UploadTraversal(wf_ctx *ctx, const FastTrees &trees) {
+    const ScenePlan &plan = ctx->plan;
+    int e = 0;
+    if ((e = devAlloc(ctx, &ctx->stackSpill, (size_t)plan.spillRows * MAX_GRID * BLOCK))) return e;
+    if ((e = devAlloc(ctx, &ctx->dbgWords, (size_t)8 + 32))) return e;   // [8..39]: -DWF_WALK_STATS builds: sixteen 64-bit phase counters (WalkStats)   // [4..7]: near-tie queue diagnostics (pushes, re-walks without a hit, -, -)
+    HIPCHK(hipMemset(ctx->dbgWords, 0, (8 + 32) * sizeof(int)));
+    ctx->fast = trees.header;
+    if (plan.fastBuilt) {
+        if ((e = devUpload(ctx, &ctx->fast.nodes, trees.nodes.data(), trees.nodes.size()))) return e;
+        if ((e = devUpload(ctx, &ctx->fast.tris, trees.tris.data(), trees.tris.size()))) return e;
+        if ((e = devUpload(ctx, &ctx->fast.defs, trees.defs.data(), trees.defs.size()))) return e;
+        if ((e = devUpload(ctx, &ctx->fast.subs, trees.subs.data(), trees.subs.size()))) return e;
+        ctx->fast.instances = ctx->svHost.instances;
+        HIPCHK(hipStreamSynchronize(ctx->stream));
     }
-    // ... and, since round 5, emitters that are not triangles (sphere / disk / cylinder / patch / curve lights: an out-of-line sampler of
-    // 214 VGPRs) and emitters with an alpha texture (the texture-graph evaluator): LightSampleLi<RARE>, AreaLightL<ALPHA> (wf_lights.h)
-    for (int i = 0; i < d->n_lights; ++i) {
-        const wf_light &l = d->lights[i];
-        if (l.type == WF_LIGHT_PORTAL_INFINITE) ctx->rareLights = ctx->portalLights = true;
-        if (l.type == WF_LIGHT_DIFFUSE_AREA && (l.tri >= d->n_triangles || l.alpha_tex_plus1 != 0)) ctx->rareLights = true;
-    }
-    sv.haveQuadricAlpha = 0;
-    for (int i = 0; i < d->n_quadrics; ++i) if (d->meshes[d->quadrics[i].mesh].alpha_tex >= 0) sv.haveQuadricAlpha = 1;
-    sv.haveCurves = 0;
-    for (int i = 0; i < d->n_quadrics; ++i) if (d->quadrics[i].type == WF_QUADRIC_CURVE) sv.haveCurves = 1;
-    for (int i = 0; i < d->n_materials; ++i) {
-        int t = d->materials[i].type;
-        if (t == WF_MAT_MIX) {
-            const int32_t *mx = d->materials[i].mix;
-            if (mx[0] < 0 || mx[0] >= d->n_materials || mx[1] < 0 || mx[1] >= d->n_materials || mx[0] >= i || mx[1] >= i)
-                return fail(-1, "mix material %d must name two earlier materials", i);
-            sv.haveMix = 1;
-            continue;
-        }
-        if (t < 0 || t >= WF_MAT_NTYPES) return fail(-1, "material %d has unknown type %d", i, t);
-        ctx->matPresent[t] = true;
-        sv.matTypeMask |= 1 << t;
-        if (t == WF_MAT_SUBSURFACE) {
-            sv.haveSubsurface = 1;
-            if (d->materials[i].sss_table < 0 || (size_t)d->materials[i].sss_table + BSSRDF_TABLE_FLOATS > (size_t)d->n_table_floats)
-                return fail(-1, "subsurface material %d: BSSRDF table outside table_data", i);
-        }
-        if (t == WF_MAT_MEASURED) {
-            // every array the five interpolants point to must lie inside table_data (the kernels index them unchecked)
-            const int64_t nT = d->n_table_floats, h = d->materials[i].measured_table;
-            if (h < 0 || h + WF_MEASURED_HEADER_WORDS > nT) return fail(-1, "measured material %d: header outside table_data", i);
-            auto word = [&](int64_t k) { int32_t v; memcpy(&v, &d->table_data[h + k], 4); return (int64_t)v; };
-            static const int nParams[5] = {0, 0, 2, 2, 3};
-            static const bool hasCdf[5] = {false, false, true, true, false};
-            for (int k = 0; k < 5; ++k) {
-                const int64_t b = 16 + 16 * k, sx = word(b), sy = word(b + 1);
-                if (sx < 2 || sy < 2 || sx > (1 << 20) || sy > (1 << 20)) return fail(-1, "measured material %d: interpolant %d has size %lld x %lld", i, k, (long long)sx, (long long)sy);
-                int64_t slices = 1;
-                for (int p = nParams[k] - 1; p >= 0; --p) {
-                    const int64_t ps = word(b + 2 + p), st = word(b + 5 + p), po = word(b + 8 + p);
-                    if (ps < 1 || ps > (1 << 20) || po < 0 || po + ps > nT || st != (ps > 1 ? slices : 0)) return fail(-1, "measured material %d: interpolant %d, parameter %d invalid", i, k, p);
-                    slices *= ps;
-                    if (slices > nT) return fail(-1, "measured material %d: interpolant %d larger than table_data", i, k);
-                }
-                const int64_t dataOff = word(b + 11), margOff = word(b + 12), condOff = word(b + 13);
-                if (dataOff < 0 || dataOff + slices * sx * sy > nT) return fail(-1, "measured material %d: interpolant %d data outside table_data", i, k);
-                if (hasCdf[k] && (margOff < 0 || margOff + slices * sy > nT || condOff < 0 || condOff + slices * sx * sy > nT))
-                    return fail(-1, "measured material %d: interpolant %d cdf outside table_data", i, k);
-            }
-        }
-    }
+    if ((e = PickWalkKernels(ctx))) return e;
+    if ((e = devAlloc(ctx, &ctx->probeCursor, (size_t)1))) return e;
+    // the walk on stream3 pushes into spill rows of its own: a column is indexed by the global thread, which both walks have
+    if (FrameOverlapScene(ctx) && (e = devAlloc(ctx, &ctx->stackSpill2, (size_t)plan.spillRows * MAX_GRID * BLOCK))) return e;
+    return 0;
+}
+// ... and the film, the counters and the device copy of SceneView
+static int UploadFilmAndView(wf_ctx *ctx, const wf_scene_desc *d) {
+    int e = 0;
     ctx->W = d->film.pixel_max[0] - d->film.pixel_min[0];
     ctx->H = d->film.pixel_max[1] - d->film.pixel_min[1];
     ctx->maxDepth = d->max_depth;
     for (int i = 0; i < 6; ++i) ctx->sceneBounds[i] = d->scene_bounds[i];
-    {
-        std::vector<QNode> qn;
-        std::vector<LeafTri> lt;
-        {
-            ctx->genMode = 0;
-            if (d->n_quadrics > 0) ctx->genMode = (sv.haveCurves || sv.haveQuadricAlpha) ? 3 : 2;
-            int alphaGen = 0;   // what the TRIANGLES of the scene ask of the walk: 0 nothing, 1 simple alpha cut-outs, 2 texture-graph alpha
-            for (int i = 0; i < d->n_meshes && alphaGen < 2; ++i)
-                if (d->meshes[i].alpha_tex >= 0) {
-                    const int tt = d->textures[d->meshes[i].alpha_tex].type;
-                    // the inline test looks an image map up without a footprint (MIPFilterFloatZeroP): uv-mapped, not EWA-filtered
-                    const wf_texture &at = d->textures[d->meshes[i].alpha_tex];
-                    const bool lean = tt == WF_TEX_FLOAT_CONSTANT || (at.mapping == WF_TEXMAP_UV && (tt != WF_TEX_FLOAT_IMAGE || d->tex_images[at.i0].filter != WF_MIP_EWA));
-                    alphaGen = std::max(alphaGen, ((tt == WF_TEX_FLOAT_CONSTANT || tt == WF_TEX_FLOAT_IMAGE || tt == WF_TEX_FLOAT_BILERP) && lean) ? 1 : 2);
-                }
-            ctx->genMode = std::max(ctx->genMode, alphaGen);
-            // TWO-CLASS TRAVERSAL: the scene's quadrics / patches / curves are few beside its triangles, and the triangles themselves need no
-            // more than the simple alpha test — the triangle kernels walk first, the general kernels only the rays handed over
-            // (WF_DEFER_GENERAL=1 | 0 forces / forbids it for any scene with such shapes)
-            ctx->genTri = std::min(alphaGen, 1);
-            ctx->deferGeneral = false;
-            if (d->n_quadrics > 0 && alphaGen <= 1 && ctx->genMode >= 2) {
-                const bool few = (int64_t)d->n_quadrics * 16 <= (int64_t)d->n_triangles;
-                ctx->deferGeneral = getenv("WF_DEFER_GENERAL") ? atoi(getenv("WF_DEFER_GENERAL")) != 0 : few;
-            }
-        }
-        std::vector<FastDef> fdefs;
-        std::vector<SubEntry> fsubs;
-        FastDepths fdep;
-        ctx->nestedAnimated = NestedPlacements(d);
-        ctx->fastOk = BuildFastBVH(d, &qn, &lt, &fdefs, &fsubs, &ctx->fast, &fdep);
-        {
-            // traversal stacks: LDS entries per lane + rows of `stackSpill` behind them, sized from the trees' ACTUAL depths: the
-            // reference-order walk pushes one sibling per level of the reference's binary trees (top level, then an instance
-            // definition's on top); the four-wide production walk up to three per level of ITS collapsed trees (BuildFastBVH records
-            // their depths: the greedy largest-area collapse does not halve the depth of an unbalanced tree), one entry per instance
-            // of a leaf, and the two instance markers.  A push past the rows is dropped and flagged (LdsStackT, wf_sync).
-            auto treeDepth = [&](int root) {
-                int best = 0;
-                if (root < 0 || root >= d->n_bvh_nodes) return best;
-                std::vector<std::pair<int, int>> st{{root, 1}};
-                while (!st.empty()) {
-                    auto [i, dep] = st.back();
-                    st.pop_back();
-                    best = std::max(best, dep);
-                    if (d->bvh_nodes[i].nprims == 0) { st.push_back({i + 1, dep + 1}); st.push_back({d->bvh_nodes[i].offset, dep + 1}); }
-                }
-                return best;
-            };
-            int depthTop = d->n_bvh_nodes > 0 ? treeDepth(0) : 0, depthDef = 0;
-            for (int k = 0; k < d->n_instance_defs; ++k) depthDef = std::max(depthDef, treeDepth(d->instance_defs[k].bvh_root));
-            // (a definition with nested placements carries a third level: a moving entity's tree on top of the definition's)
-            const int needRef = depthTop + (ctx->nestedAnimated > 0 ? 2 : 1) * depthDef + 4;
-            const int needFast = 3 * fdep.top + fdep.maxLeafInstances + 3 * fdep.def + 6;
-            const int rows = std::max(std::max(needRef - std::min(STACK_LDS, TSTACK), needFast - TSTACK), STACK_MAX - std::min(STACK_LDS, TSTACK));
-            if (rows > 2048) return fail(-1, "BVH too deep for the traversal stacks (depth %d + %d)", depthTop, depthDef);
-            if ((e = devAlloc(ctx, &ctx->stackSpill, (size_t)rows * MAX_GRID * BLOCK))) return e;
-            ctx->spillRows = rows;
-            if ((e = devAlloc(ctx, &ctx->dbgWords, (size_t)8 + 32))) return e;   // [8..39]: -DWF_WALK_STATS builds: sixteen 64-bit phase counters (WalkStats)   // [4..7]: near-tie queue diagnostics (pushes, re-walks without a hit, -, -)
-            HIPCHK(hipMemset(ctx->dbgWords, 0, (8 + 32) * sizeof(int)));
-        }
-        if (ctx->fastOk) {
-            if ((e = devUpload(ctx, &ctx->fast.nodes, qn.data(), qn.size()))) return e;
-            if ((e = devUpload(ctx, &ctx->fast.tris, lt.data(), lt.size()))) return e;
-            if ((e = devUpload(ctx, &ctx->fast.defs, fdefs.data(), fdefs.size()))) return e;
-            if ((e = devUpload(ctx, &ctx->fast.subs, fsubs.data(), fsubs.size()))) return e;
-            // rays of a scene whose trees do not fit the caches walk long enough for one cursor fetch per 64 rays (measured: -3 % on
-            // the 10 M-triangle scene); a cache-resident scene traces so fast that the cursor's atomics would bound it (see cursorChunk)
-            const bool big = qn.size() * sizeof(QNode) + lt.size() * sizeof(LeafTri) > ((size_t)256 << 20);
-            ctx->cursorChunk = big ? 3 : 2;
-            ctx->cursorChunkShadow = big ? 1 : 2;
-            ctx->fast.instances = ctx->svHost.instances;
-            HIPCHK(hipStreamSynchronize(ctx->stream));
-        }
-        if (getenv("WF_NO_FAST")) ctx->fastOk = false;
-        // AnimatedPrimitive: the production walks' ANIM variants (triangles + simple alpha cut-outs, two-level: an animated shape entity is an
-        // instance) interpolate the transformation per ray since round 6; scenes that also hold quadrics / curves / texture-graph alpha keep the
-        // reference-order walks (WF_ANIM_FAST=0: every animated scene does)
-        ctx->animFast = d->n_animated > 0 && ctx->fastOk && ctx->genMode <= 1 && ctx->svHost.nInstances > 0 && !(getenv("WF_ANIM_FAST") && atoi(getenv("WF_ANIM_FAST")) == 0);
-        if (d->n_animated > 0 && !ctx->animFast) ctx->fastOk = false;
-        if ((e = PickWalkKernels(ctx))) return e;
-        if ((e = devAlloc(ctx, &ctx->probeCursor, (size_t)1))) return e;
-        // the walk on stream3 pushes into spill rows of its own: a column is indexed by the global thread, which both walks have
-        if (FrameOverlapScene(ctx) && (e = devAlloc(ctx, &ctx->stackSpill2, (size_t)ctx->spillRows * MAX_GRID * BLOCK))) return e;
-    }
     if ((e = devAlloc(ctx, &ctx->ws.film, (size_t)ctx->W * ctx->H * 4))) return e;
     ctx->ws.filmSpectral = nullptr;
     ctx->ws.filmGBuffer = nullptr;
     if (d->film.type == WF_FILM_GBUFFER && (e = devAlloc(ctx, &ctx->ws.filmGBuffer, (size_t)ctx->W * ctx->H))) return e;
-    if (d->film.type == WF_FILM_SPECTRAL) {
-        if (d->film.n_buckets < 1 || d->film.n_buckets > 4096 || !(d->film.lambda_max > d->film.lambda_min)) return fail(-1, "spectral film: bad bucket count / wavelength range");
-        if ((e = devAlloc(ctx, &ctx->ws.filmSpectral, (size_t)ctx->W * ctx->H * 2 * d->film.n_buckets))) return e;
-    }
+    if (d->film.type == WF_FILM_SPECTRAL && (e = devAlloc(ctx, &ctx->ws.filmSpectral, (size_t)ctx->W * ctx->H * 2 * d->film.n_buckets))) return e;
     if ((e = devAlloc(ctx, &ctx->ws.stats, (size_t)(129 + 16)))) return e;   // [129 ..]: items per material queue / the medium-sample queue
     if ((e = devAlloc(ctx, &ctx->ws.trav, (size_t)8))) return e;
     if ((e = devAlloc(ctx, &ctx->ws.counters, (size_t)CNT_COUNT * CNT_STRIDE))) return e;
-    {
-        SceneView *dev = nullptr;
-        if ((e = devAlloc(ctx, &dev, (size_t)1))) return e;
-        ctx->svHost.self = dev;  // the device copy points at itself: the address the out-of-line device functions are given
-        ctx->svHost.fatal = ctx->dbgWords ? ctx->dbgWords + 7 : nullptr;   // RaiseFatal (wf_scene.h): reported by wf_sync
-        HIPCHK(hipMemcpyAsync(dev, &ctx->svHost, sizeof(SceneView), hipMemcpyHostToDevice, ctx->stream));
-        ctx->svDev = dev;
-    }
+    SceneView *dev = nullptr;
+    if ((e = devAlloc(ctx, &dev, (size_t)1))) return e;
+    ctx->svHost.self = dev;  // the device copy points at itself: the address the out-of-line device functions are given
+    ctx->svHost.fatal = ctx->dbgWords + 7;   // RaiseFatal (wf_scene.h): reported by wf_sync
+    HIPCHK(hipMemcpyAsync(dev, &ctx->svHost, sizeof(SceneView), hipMemcpyHostToDevice, ctx->stream));
+    ctx->svDev = dev;
     ctx->fast.sv = ctx->svDev;
-    HIPCHK(hipStreamSynchronize(ctx->stream));  // sv / sobol live on the host stack
+    HIPCHK(hipStreamSynchronize(ctx->stream));  // (the copies above read host memory that the caller and this call own)
+    return 0;
+}
+int wf_scene_upload(wf_ctx *ctx, const wf_scene_desc *d) {
+    if (!ctx || !d) return fail(-1, "null argument");
+    if (int e = CheckAbi(d)) return e;   // (before the context's own state: a foreign description is reported as such)
+    if (ctx->sceneLoaded) return fail(-1, "a scene is already uploaded to this context");
+    const Switches sw = Switches::FromEnv();
+    ScenePlan plan;
+    FastTrees trees;
+    if (int e = PlanScene(d, sw, &plan, &trees)) return e;   // (nothing is allocated before the description has passed)
+    HIPCHK(hipSetDevice(ctx->device));
+    // a step that fails below takes back what this call allocated and puts the scene state back to its defaults (W, H, maxDepth and
+    // sceneBounds keep what UploadFilmAndView wrote: nothing reads them while sceneLoaded is false, and the next upload sets them)
+    struct Rollback {
+        wf_ctx *ctx;
+        size_t nAllocs;
+        bool done = false;
+        ~Rollback() {
+            if (done) return;
+            (void)hipStreamSynchronize(ctx->stream);
+            for (size_t i = nAllocs; i < ctx->allocs.size(); ++i) (void)hipFree(ctx->allocs[i]);
+            ctx->allocs.resize(nAllocs);
+            ctx->svHost = SceneView{};
+            ctx->svDev = nullptr;
+            ctx->ws = WorkState{};
+            ctx->fast = FastBVH{};
+            ctx->walk = WalkKernels{};
+            ctx->plan = ScenePlan{};
+            ctx->stackSpill = ctx->stackSpill2 = ctx->dbgWords = nullptr;
+            ctx->probeCursor = nullptr;
+        }
+    } rollback{ctx, ctx->allocs.size()};
+    ctx->plan = plan;
+    int e;
+    if ((e = UploadTables(ctx, d, sw)) || (e = UploadTraversal(ctx, trees)) || (e = UploadFilmAndView(ctx, d))) return e;
+    rollback.done = true;
     ctx->sceneLoaded = true;
+    return 0;
+}
+int wf_scene_plan_query(const wf_scene_desc *d, const char *key, int64_t *value) {
+    if (!d || !key || !value) return fail(-1, "wf_scene_plan_query: null argument");
+    ScenePlan plan;
+    FastTrees trees;
+    if (int e = PlanScene(d, Switches::FromEnv(), &plan, &trees)) return e;
+    if (!PlanValue(plan, key, value)) return fail(-1, "wf_scene_plan_query: unknown key '%s'", key);
     return 0;
 }
 
@@ -2900,20 +3103,10 @@ int wf_ctx_query(wf_ctx *ctx, const char *key, int64_t *value) {
     if (!ctx || !key || !value) return fail(-1, "wf_ctx_query: null argument");
     if (!ctx->sceneLoaded) return fail(-1, "no scene uploaded");
     const std::string k = key;
-    if (k == "fast_ok") *value = ctx->fastOk;
-    else if (k == "gen_mode") *value = ctx->genMode;
-    else if (k == "gen_tri") *value = ctx->genTri;
-    else if (k == "defer_general") *value = ctx->deferGeneral;
-    else if (k == "anim_fast") *value = ctx->animFast;
-    else if (k == "lean_shade") *value = ctx->leanShade;
-    else if (k == "rare_lights") *value = ctx->rareLights;
-    else if (k == "medium_lean") *value = ctx->mediumLean;   // k_medium_sample<true> / k_tr_segment<true>: every medium is homogeneous or a non-emissive uniform grid
-    else if (k.rfind("lean_type_", 0) == 0 && atoi(key + 10) >= 0 && atoi(key + 10) < WF_MAT_NTYPES) *value = ctx->leanType[atoi(key + 10)];
-    else if (k == "instances") *value = ctx->svHost.nInstances;
-    else if (k == "nested_animated") *value = ctx->nestedAnimated;
-    else if (k == "frame_overlap_active") *value = FrameOverlapScene(ctx) && ctx->stackSpill2 != nullptr;   // (a profiling / tracing / counting pass is serial all the same)
+    if (PlanValue(ctx->plan, key, value)) return 0;
+    if (k == "frame_overlap_active") *value = FrameOverlapActive(ctx);
     else if (k == "frame_overlap_mode") *value = ctx->frameOverlap;
-    else if (k == "skip_last_samples") *value = ctx->samplesShaded && !ctx->svHost.haveMedia && !ctx->svHost.haveSubsurface;
+    else if (k == "skip_last_samples") *value = SkipLastSamples(ctx);
     else return fail(-1, "wf_ctx_query: unknown key '%s'", key);
     return 0;
 }
@@ -2950,7 +3143,9 @@ int wf_queues_alloc(wf_ctx *ctx, int pixels_per_pass, int samples_per_pass) {
     ws.samplesPerPass = samples_per_pass;
     if (ws.stripCount < 1) { ws.stripRank = 0; ws.stripCount = 1; ws.stripHeight = 1; ws.localRows = ctx->H; }
     ctx->passSamples = 1;
-    if (const char *e = getenv("WF_PIXEL_MAJOR")) ctx->pixelMajor = atoi(e) != 0;
+    const Switches sw = Switches::FromEnv();
+    // (pixelMajor here and trWavefront below are set by their switches alone, and unset switches give wf_ctx's own defaults)
+    ctx->pixelMajor = sw.pixelMajor;
     ctx->ws.slotStride = ctx->pixelMajor ? 1 : 0;
     ctx->passStep = 1;
     int e;
@@ -2964,12 +3159,12 @@ int wf_queues_alloc(wf_ctx *ctx, int pixels_per_pass, int samples_per_pass) {
         return e;
     // pixel-only sample-index digits (wf_camera.h TopDigits): usable while the permuted index fits 32 bits
     ws.sampleTops = nullptr;
-    if (ctx->svHost.sampler.type == WF_SAMPLER_ZSOBOL && 2 * ctx->svHost.sampler.nBase4Digits <= 32 && !getenv("WF_NO_SAMPLE_TOPS") &&
+    if (ctx->svHost.sampler.type == WF_SAMPLER_ZSOBOL && 2 * ctx->svHost.sampler.nBase4Digits <= 32 && !sw.noSampleTops &&
         !ctx->svHost.haveSubsurface)  // (K12 scenes draw 10 dimensions per depth, not 7)
         if ((e = devAlloc(ctx, &ws.sampleTops, (size_t)5 * pixels_per_pass))) return e;
     if ((e = allocRayQueue(ctx, &ws.rq[0], n)) || (e = allocRayQueue(ctx, &ws.rq[1], n))) return e;
     if (ctx->svHost.haveMedia) {
-        if (getenv("WF_TR_WAVEFRONT")) ctx->trWavefront = atoi(getenv("WF_TR_WAVEFRONT"));
+        ctx->trWavefront = sw.trWavefront;
         if ((e = devAlloc(ctx, &ws.trO, n)) || (e = devAlloc(ctx, &ws.trD, n)) || (e = devAlloc(ctx, &ws.trT, n)) || (e = devAlloc(ctx, &ws.trRu, n)) ||
             (e = devAlloc(ctx, &ws.trRl, n)) || (e = devAlloc(ctx, &ws.trRng, n)) || (e = devAlloc(ctx, &ws.trQ[0], n)) || (e = devAlloc(ctx, &ws.trQ[1], n)))
             return e;
@@ -2985,7 +3180,7 @@ int wf_queues_alloc(wf_ctx *ctx, int pixels_per_pass, int samples_per_pass) {
     HIPCHK(hipMemset(ws.retraceQ64, 0xff, (size_t)n * sizeof(unsigned long long)));   // every slot "not yet written"
     if (ctx->svHost.nInstances > 0 && (e = devAlloc(ctx, &ws.hitInst, n))) return e;
     for (int m = 0; m < WF_MAT_NTYPES; ++m)
-        if ((e = devAlloc(ctx, &ws.matQ[m], ctx->matPresent[m] ? n : (size_t)1))) return e;  // workqueue.h:152-155
+        if ((e = devAlloc(ctx, &ws.matQ[m], ctx->plan.matPresent[m] ? n : (size_t)1))) return e;  // workqueue.h:152-155
     if ((e = devAlloc(ctx, &ws.sq.o, n)) || (e = devAlloc(ctx, &ws.sq.d, n)) || (e = devAlloc(ctx, &ws.sq.Ld, n)) ||
         (e = devAlloc(ctx, &ws.sq.r_u, n)) || (e = devAlloc(ctx, &ws.sq.r_l, n)))
         return e;
@@ -2993,7 +3188,7 @@ int wf_queues_alloc(wf_ctx *ctx, int pixels_per_pass, int samples_per_pass) {
     {
         // the NeeItems between the material stage's two kernels: as many 16-byte planes as the widest record of the material types present
         int planes = 0;
-        for (int m = 1; m < WF_MAT_NTYPES; ++m) if (ctx->matPresent[m]) planes = std::max(planes, NeePlanes(m));
+        for (int m = 1; m < WF_MAT_NTYPES; ++m) if (ctx->plan.matPresent[m]) planes = std::max(planes, NeePlanes(m));
         if (planes > 0 && (e = devAlloc(ctx, &ws.neeRec, n * (size_t)planes))) return e;
     }
     if ((e = devAlloc(ctx, &ws.routeCode, n))) return e;
@@ -3093,7 +3288,7 @@ int wf_intersect_closest(wf_ctx *ctx, int depth) {
     const bool anim = ctx->svHost.haveAnimated;
     if (ctx->countTraversal)
         LAUNCH("Intersect closest", (anim ? k_intersect_closest<true, true> : k_intersect_closest<true, false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1, ctx->stackSpill);
-    else if (ctx->fastOk) {
+    else if (ctx->plan.fastOk) {
         const WalkKernels &k = ctx->walk;
         // the work cursor starts at 0: zeroed by the stage's "Reset queues" launch (wf_reset_stage_queues) — a memset node of its own
         // cost a launch's latency per traversal launch (139 fillBuffer launches, 6 ms, in three renders of the spec scene, round 4);
@@ -3109,15 +3304,15 @@ int wf_intersect_closest(wf_ctx *ctx, int depth) {
             //  the pairs that involve a quadric, which only the general kernel's rays can meet)
             FastBVH triFast = ctx->fast;
             triFast.absBand = triFast.absBandTri; triFast.tieRel = triFast.tieRelTri;
-            LAUNCHT("Intersect closest", k.closest, k.grid, ctx->svHost, ctx->ws, triFast, depth & 1, ctx->spillArea(), cursor, ctx->cursorChunk, (const int *)nullptr);
-            LAUNCHT("Intersect closest: rays that met a general primitive", k.closestGen, k.gridGen, ctx->svHost, ctx->ws, ctx->fast, depth & 1, ctx->spillArea(), (int *)nullptr, ctx->cursorChunk, (const int *)ctx->ws.deferQ);
+            LAUNCHT("Intersect closest", k.closest, k.grid, ctx->svHost, ctx->ws, triFast, depth & 1, ctx->spillArea(), cursor, ctx->plan.cursorChunk, (const int *)nullptr);
+            LAUNCHT("Intersect closest: rays that met a general primitive", k.closestGen, k.gridGen, ctx->svHost, ctx->ws, ctx->fast, depth & 1, ctx->spillArea(), (int *)nullptr, ctx->plan.cursorChunk, (const int *)ctx->ws.deferQ);
         } else
-            LAUNCHT("Intersect closest", k.closest, k.grid, ctx->svHost, ctx->ws, ctx->fast, depth & 1, ctx->spillArea(), cursor, ctx->cursorChunk, (const int *)nullptr);
+            LAUNCHT("Intersect closest", k.closest, k.grid, ctx->svHost, ctx->ws, ctx->fast, depth & 1, ctx->spillArea(), cursor, ctx->plan.cursorChunk, (const int *)nullptr);
         // The near-tie re-trace of the scenes whose walk does not resolve its ties itself (genMode >= 2: quadrics, curves, texture-graph
         // alpha; RetraceInline) is a handful of long single walks: it runs on a second stream beside the routing pass (and, in the
         // fused pass, the next sample-generation launch) — they touch disjoint rays and share only the queue counters, through
         // atomics — and the main stream waits for it before anything consumes the queues.
-        const bool overlap = !RetraceInline(ctx->genMode) && ctx->profile != 1 && !ctx->traceLaunch;   // (the full per-stage profile times every launch on the main stream)
+        const bool overlap = !RetraceInline(ctx->plan.genMode) && ctx->profile != 1 && !ctx->traceLaunch;   // (the full per-stage profile times every launch on the main stream)
         if (overlap) {
             HIPCHK(hipEventRecord(ctx->evFork, ctx->stream));
             HIPCHK(hipStreamWaitEvent(ctx->stream2, ctx->evFork, 0));
@@ -3130,13 +3325,13 @@ int wf_intersect_closest(wf_ctx *ctx, int depth) {
             const int g = std::min(MAX_GRID, std::max(1, (ctx->maxQueueSize + RBLOCK - 1) / RBLOCK));
             if (anim)   // (two-level)
                 hipLaunchKernelGGL((k_route_hits<true, true>), dim3(std::min(MAX_GRID, std::max(1, (ctx->maxQueueSize + BLOCK - 1) / BLOCK))), dim3(BLOCK), 0, ctx->stream, ctx->svHost, ctx->ws, depth & 1);
-            else if (ctx->genMode > 1 || ctx->svHost.nInstances > 0) hipLaunchKernelGGL(k_route_hits<true>, dim3(g), dim3(RBLOCK), 0, ctx->stream, ctx->svHost, ctx->ws, depth & 1);
+            else if (ctx->plan.genMode > 1 || ctx->svHost.nInstances > 0) hipLaunchKernelGGL(k_route_hits<true>, dim3(g), dim3(RBLOCK), 0, ctx->stream, ctx->svHost, ctx->ws, depth & 1);
             else hipLaunchKernelGGL(k_route_hits<false>, dim3(g), dim3(RBLOCK), 0, ctx->stream, ctx->svHost, ctx->ws, depth & 1);
         }
         if (ctx->retracePending) {
             if (ctx->deferJoin) return 0;   // the fused pass joins after its sample-generation launch (JoinRetrace)
             if (int e = JoinRetrace(ctx)) return e;
-        } else if (!RetraceInline(ctx->genMode))
+        } else if (!RetraceInline(ctx->plan.genMode))
             LAUNCH("Intersect closest: near-tie re-trace", k_closest_retrace, 128, ctx->svHost, ctx->ws, depth & 1, ctx->stackSpill);
         if (ctx->svHost.haveMix) LAUNCH("Resolve MixMaterial hits", (anim ? k_resolve_mix<true> : k_resolve_mix<false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
     } else
@@ -3147,10 +3342,10 @@ int wf_intersect_closest(wf_ctx *ctx, int depth) {
 int wf_medium_sample(wf_ctx *ctx, int depth) {
     if (int e = checkReady(ctx)) return e;
     if (!ctx->svHost.haveMedia) return 0;
-    LAUNCH("Sample medium interaction", (ctx->mediumLean ? k_medium_sample<true> : k_medium_sample<false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
+    LAUNCH("Sample medium interaction", (ctx->plan.mediumLean ? k_medium_sample<true> : k_medium_sample<false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
     LAUNCH("Sample medium interaction: route surface hits", (ctx->svHost.haveAnimated ? k_medium_route<true> : k_medium_route<false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
     if (depth == ctx->maxDepth) return 0;
-    LAUNCH("Sample direct/indirect - Henyey-Greenstein", (ctx->rareLights ? k_medium_scatter<true> : k_medium_scatter<false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
+    LAUNCH("Sample direct/indirect - Henyey-Greenstein", (ctx->plan.rareLights ? k_medium_scatter<true> : k_medium_scatter<false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
     return 0;
 }
 // TraceShadowRays with media: IntersectShadowTr (wavefront/aggregate.cpp:70-88, intersect.h:165-274)
@@ -3159,7 +3354,7 @@ int wf_intersect_shadow_tr(wf_ctx *ctx, int depth) {
     if (!ctx->svHost.haveMedia) return fail(-1, "wf_intersect_shadow_tr: the scene has no media (use wf_intersect_shadow)");
     // (a scene with AnimatedPrimitives keeps the reference-order transmittance walk, which interpolates their transformations at the shadow
     //  ray's time: the transmittance wavefront's walk kernel has no ANIM variant — fuzz scene s6300008, round 6)
-    if (ctx->fastOk && !ctx->animFast && !ctx->countTraversal && RetraceInline(ctx->genMode) && (ctx->trWavefront == 1 || (ctx->trWavefront < 0 && (ctx->svHost.nInstances > 0 || ctx->mediumLean)))) {
+    if (ctx->plan.fastOk && !ctx->plan.animFast && !ctx->countTraversal && RetraceInline(ctx->plan.genMode) && (ctx->trWavefront == 1 || (ctx->trWavefront < 0 && (ctx->svHost.nInstances > 0 || ctx->plan.mediumLean)))) {
         // (round 6: also for one-level scenes whose media are all lean — k_tr_segment<true> runs at 3 waves (162 VGPRs) where the per-lane kernel is one
         //  wave of 366 + 110 registers per SIMD: cloud scene 17.3 against 18.5 ms, profiles/r06_transmittance_lean_wavefront_ab_cloud16.txt)
         // the transmittance wavefront (see k_tr_begin)
@@ -3168,12 +3363,12 @@ int wf_intersect_shadow_tr(wf_ctx *ctx, int depth) {
         for (int seg = 0; seg < WF_TR_SEGMENTS; ++seg) {
             const int cur = seg & 1;
             LAUNCHT("Intersect shadow (Tr): trace", ctx->walk.trTrace, ctx->walk.grid, ctx->svHost, ctx->ws, ctx->fast, cur, ctx->spillArea());
-            LAUNCH("Intersect shadow (Tr): segment", (ctx->mediumLean ? k_tr_segment<true> : k_tr_segment<false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, cur);
+            LAUNCH("Intersect shadow (Tr): segment", (ctx->plan.mediumLean ? k_tr_segment<true> : k_tr_segment<false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, cur);
             LAUNCH("Reset transmittance queues", k_reset, 1, ctx->ws, 1u << (CNT_TR0 + cur), -1, 0);
         }
         LAUNCH("Intersect shadow (Tr): rest", k_tr_rest, 128, ctx->svHost, ctx->ws, WF_TR_SEGMENTS & 1, ctx->stackSpill);
-    } else if (ctx->fastOk && !ctx->animFast && !ctx->countTraversal && ctx->svHost.nInstances == 0)  // (the per-lane production walk has no two-level variant)
-        LAUNCHT("Intersect shadow (Tr)", (ctx->svHost.haveAlpha || ctx->svHost.nQuadrics > 0 ? k_shadow_tr_fast<true> : ctx->mediumLean ? k_shadow_tr_fast<false, true> : k_shadow_tr_fast<false>), ctx->walk.grid,
+    } else if (ctx->plan.fastOk && !ctx->plan.animFast && !ctx->countTraversal && ctx->svHost.nInstances == 0)  // (the per-lane production walk has no two-level variant)
+        LAUNCHT("Intersect shadow (Tr)", (ctx->svHost.haveAlpha || ctx->svHost.nQuadrics > 0 ? k_shadow_tr_fast<true> : ctx->plan.mediumLean ? k_shadow_tr_fast<false, true> : k_shadow_tr_fast<false>), ctx->walk.grid,
                 ctx->svHost, ctx->ws, ctx->fast, ctx->spillArea());
     else
         LAUNCH("Intersect shadow (Tr)", (ctx->svHost.haveAnimated ? k_shadow_tr<true> : k_shadow_tr<false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, ctx->stackSpill);
@@ -3183,7 +3378,7 @@ int wf_intersect_shadow_tr(wf_ctx *ctx, int depth) {
 int wf_handle_escaped(wf_ctx *ctx, int depth) {
     if (int e = checkReady(ctx)) return e;
     if (ctx->svHost.nInfiniteLights == 0) return 0;  // escapedRayQueue == nullptr (integrator.cpp:496-497)
-    LAUNCH("Handle escaped rays", (ctx->portalLights ? k_handle_escaped<true> : k_handle_escaped<false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
+    LAUNCH("Handle escaped rays", (ctx->plan.portalLights ? k_handle_escaped<true> : k_handle_escaped<false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
     return 0;
 }
 int wf_handle_emissive(wf_ctx *ctx, int depth) {
@@ -3208,7 +3403,7 @@ static int EvalMaterial(wf_ctx *ctx, int material_type, int depth) {
         Prof prof_(ctx, names[material_type]);
         // shade variant: 0 / 1 the LEAN kernels (triangle-only scenes whose textures are all constants, image maps or bilerps: SceneLean),
         // without / with the texture footprint and bump block; 2 general; 3 general + visible surface / moving camera
-        const int v = vs ? 3 : (!ctx->leanType[material_type] ? 2 : (tex ? 1 : 0));
+        const int v = vs ? 3 : (!ctx->plan.leanType[material_type] ? 2 : (tex ? 1 : 0));
         kMatShade[material_type][v](ctx->stream, g, &ctx->svHost, &ctx->ws, cur);
     }
     {
@@ -3217,7 +3412,7 @@ static int EvalMaterial(wf_ctx *ctx, int material_type, int depth) {
                                                       "CoatedDiffuseMaterial: next-event estimation", "CoatedConductorMaterial: next-event estimation",
                                                       "SubsurfaceMaterial: next-event estimation", "HairMaterial: next-event estimation", "MeasuredMaterial: next-event estimation"};
         Prof prof_(ctx, neeNames[material_type]);
-        kMatNee[material_type][ctx->rareLights ? 1 : 0](ctx->stream, g, &ctx->svHost, &ctx->ws);
+        kMatNee[material_type][ctx->plan.rareLights ? 1 : 0](ctx->stream, g, &ctx->svHost, &ctx->ws);
     }
     return 0;
 }
@@ -3231,7 +3426,7 @@ int wf_eval_material(wf_ctx *ctx, int material_type, int depth) {
 // against 442.0 / 443.8 / 442.8 Msamples/s at K = 20, profiles/r07_thin_material_streams_ab_sm20.txt.)
 static int EvalMaterials(wf_ctx *ctx, int depth) {
     for (int m = 1; m < WF_MAT_NTYPES; ++m)
-        if (ctx->matPresent[m])
+        if (ctx->plan.matPresent[m])
             if (int e = EvalMaterial(ctx, m, depth)) return e;
     return 0;
 }
@@ -3241,9 +3436,9 @@ static int ShadowStage(wf_ctx *ctx, int depth, hipStream_t strm, int *spill) {
     const bool anim = ctx->svHost.haveAnimated;
     if (ctx->countTraversal)
         LAUNCH_ON(strm, "Intersect shadow", (anim ? k_intersect_shadow<true, true> : k_intersect_shadow<true, false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, spill);
-    else if (ctx->fastOk) {
+    else if (ctx->plan.fastOk) {
         const WalkKernels &k = ctx->walk;
-        const SpillArea area{spill, ctx->spillRows, ctx->dbgWords};   // (the debug words are shared: every update of them is an atomic)
+        const SpillArea area{spill, ctx->plan.spillRows, ctx->dbgWords};   // (the debug words are shared: every update of them is an atomic)
         int *cursor = ctx->ws.counters + CNT_CURSOR_SHADOW * CNT_STRIDE;   // (zeroed by the "Reset shadowRayQueue" launch that follows every any-hit launch)
         if (ctx->cursorDirty[1]) HIPCHK(hipMemsetAsync(cursor, 0, sizeof(int), strm));
         ctx->cursorDirty[1] = true;
@@ -3251,9 +3446,9 @@ static int ShadowStage(wf_ctx *ctx, int depth, hipStream_t strm, int *spill) {
         // depth's closest-hit rays); the kernels take the list from the WorkState they are given
         WorkState ws = ctx->ws;
         if (strm != ctx->stream && ctx->deferQShadow) ws.deferQ = ctx->deferQShadow;
-        LAUNCHT_ON(strm, "Intersect shadow", k.shadow, k.gridShadow, ctx->svHost, ws, ctx->fast, area, cursor, ctx->cursorChunkShadow, (const int *)nullptr);
+        LAUNCHT_ON(strm, "Intersect shadow", k.shadow, k.gridShadow, ctx->svHost, ws, ctx->fast, area, cursor, ctx->plan.cursorChunkShadow, (const int *)nullptr);
         if (k.shadowGen)
-            LAUNCHT_ON(strm, "Intersect shadow: rays that met a general primitive", k.shadowGen, k.gridShadowGen, ctx->svHost, ws, ctx->fast, area, (int *)nullptr, ctx->cursorChunkShadow, (const int *)ws.deferQ);
+            LAUNCHT_ON(strm, "Intersect shadow: rays that met a general primitive", k.shadowGen, k.gridShadowGen, ctx->svHost, ws, ctx->fast, area, (int *)nullptr, ctx->plan.cursorChunkShadow, (const int *)ws.deferQ);
     } else
         LAUNCH_ON(strm, "Intersect shadow", (anim ? k_intersect_shadow<false, true> : k_intersect_shadow<false, false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, spill);
     // "Reset shadowRayQueue": stats->shadowRays[depth] += size; Reset (integrator.cpp:581-585)
@@ -3320,16 +3515,15 @@ static int RenderPass(wf_ctx *ctx, int y0, int sample_index) {
     // FRAME SCHEDULING (see IssueShadowAside).  Serial, as the per-stage entry points are: the full per-stage profile (it times every launch
     // on the main stream), launch tracing, traversal counting (ws.trav, the reference-order walks on ctx->stackSpill), and the scenes
     // FrameOverlapScene leaves out.
-    const bool aside = ctx->stackSpill2 != nullptr && FrameOverlapScene(ctx) && ctx->profile != 1 && !ctx->traceLaunch && !ctx->countTraversal;
-    // (media and subsurface scenes keep the launch: their scatter stages are not this loop's material stage)
-    const bool skipLastSamples = ctx->samplesShaded && !ctx->svHost.haveMedia && !ctx->svHost.haveSubsurface;
+    const bool aside = FrameOverlapActive(ctx) && ctx->profile != 1 && !ctx->traceLaunch && !ctx->countTraversal;
+    const bool skipLastSamples = SkipLastSamples(ctx);
     if ((e = wf_reset_ray_queue(ctx, 0))) return e;
     if ((e = wf_gen_camera_rays(ctx, y0, sample_index))) return e;
     for (int depth = 0; true; ++depth) {
         if ((e = wf_reset_stage_queues(ctx, depth))) return e;
         // (GenerateRaySamples does not depend on the intersections: it is issued after the closest-hit launch so that it runs beside
         // the re-trace; the per-stage entry points keep the reference's order)
-        ctx->deferJoin = ctx->fastOk && !ctx->countTraversal && !ctx->svHost.haveMix;
+        ctx->deferJoin = ctx->plan.fastOk && !ctx->countTraversal && !ctx->svHost.haveMix;
         if ((e = wf_intersect_closest(ctx, depth))) { ctx->deferJoin = false; return e; }
         ctx->deferJoin = false;
         // no samples at the last depth: the loop leaves before the material stage, the only reader.  (Measured and dropped, round 7: at
@@ -3567,10 +3761,10 @@ int wf_trace_closest_device(wf_ctx *ctx, int n, const float *rays7, wf_hit_recor
     if (ctx->svHost.haveAnimated) return fail(-1, "%s: the scene has animated primitives — a ray needs its time (wf_trace_closest_host_t / wf_trace_any_host_t)", __func__);
     useDevice(ctx);
     if (n <= 0) return 0;
-    if (!ctx->fastOk) { LAUNCH("trace closest (device rays)", k_trace_closest, gridFor(n), ctx->svHost, n, rays7, out, ctx->stackSpill, 0); return 0; }
+    if (!ctx->plan.fastOk) { LAUNCH("trace closest (device rays)", k_trace_closest, gridFor(n), ctx->svHost, n, rays7, out, ctx->stackSpill, 0); return 0; }
     LAUNCHT("trace closest fast (device rays)", ctx->walk.traceClosest, ctx->walk.grid, ctx->svHost, ctx->fast, n, rays7, out, ctx->spillArea());
     // (the variants that do not resolve their near ties inside the walk mark them: re-traced in reference order)
-    if (!RetraceInline(ctx->genMode)) LAUNCH("trace closest (near-tie re-trace)", k_trace_closest, gridFor(n), ctx->svHost, n, rays7, out, ctx->stackSpill, 1);
+    if (!RetraceInline(ctx->plan.genMode)) LAUNCH("trace closest (near-tie re-trace)", k_trace_closest, gridFor(n), ctx->svHost, n, rays7, out, ctx->stackSpill, 1);
     return 0;
 }
 int wf_trace_any_device(wf_ctx *ctx, int n, const float *rays7, int32_t *occluded) {
@@ -3578,7 +3772,7 @@ int wf_trace_any_device(wf_ctx *ctx, int n, const float *rays7, int32_t *occlude
     if (ctx->svHost.haveAnimated) return fail(-1, "%s: the scene has animated primitives — a ray needs its time (wf_trace_closest_host_t / wf_trace_any_host_t)", __func__);
     useDevice(ctx);
     if (n <= 0) return 0;
-    if (!ctx->fastOk) { LAUNCH("trace any (device rays)", k_trace_any, gridFor(n), ctx->svHost, n, rays7, occluded, (int32_t *)nullptr, (int32_t *)nullptr, ctx->stackSpill); return 0; }
+    if (!ctx->plan.fastOk) { LAUNCH("trace any (device rays)", k_trace_any, gridFor(n), ctx->svHost, n, rays7, occluded, (int32_t *)nullptr, (int32_t *)nullptr, ctx->stackSpill); return 0; }
     LAUNCHT("trace any fast (device rays)", ctx->walk.traceAny, ctx->walk.grid, ctx->svHost, ctx->fast, n, rays7, occluded, ctx->spillArea());
     return 0;
 }
@@ -3611,23 +3805,17 @@ int wf_trace_closest_host(wf_ctx *ctx, int n, const float *o, const float *d, co
     if (ctx->svHost.haveAnimated) return fail(-1, "%s: the scene has animated primitives — a ray needs its time (wf_trace_closest_host_t / wf_trace_any_host_t)", __func__);
     useDevice(ctx);
     if (n <= 0) return 0;
-    std::vector<float> rays((size_t)n * 7);
-    for (int i = 0; i < n; ++i) {
-        for (int k = 0; k < 3; ++k) { rays[(size_t)i * 7 + k] = o[3 * i + k]; rays[(size_t)i * 7 + 3 + k] = d[3 * i + k]; }
-        rays[(size_t)i * 7 + 6] = tmax[i];
-    }
+    const std::vector<float> rays = PackRays7(o, d, tmax, n);
+    DeviceScratch tmp(ctx->stream);
     float *dr = nullptr;
     wf_hit_record *dh = nullptr;
-    HIPCHK(hipMalloc((void **)&dr, rays.size() * sizeof(float)));
-    HIPCHK(hipMalloc((void **)&dh, (size_t)n * sizeof(wf_hit_record)));
-    HIPCHK(hipMemcpyAsync(dr, rays.data(), rays.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    if (count_visits || !ctx->fastOk) {
+    int e;
+    if ((e = tmp.upload(&dr, rays.data(), rays.size())) || (e = tmp.alloc(&dh, (size_t)n))) return e;
+    if (count_visits || !ctx->plan.fastOk) {
         LAUNCH("trace closest (host rays)", k_trace_closest, gridFor(n), ctx->svHost, n, dr, dh, ctx->stackSpill, 0);
-    } else if (int e = wf_trace_closest_device(ctx, n, dr, dh)) return e;
+    } else if ((e = wf_trace_closest_device(ctx, n, dr, dh))) return e;
     HIPCHK(hipMemcpyAsync(out, dh, (size_t)n * sizeof(wf_hit_record), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    HIPCHK(hipFree(dr));
-    HIPCHK(hipFree(dh));
     return 0;
 }
 // IntersectShadowTr on caller-supplied shadow rays: a scratch WorkState over temporary device arrays (one "pixel" per ray) run through
@@ -3647,34 +3835,25 @@ static int TraceShadowTrHost(wf_ctx *ctx, const char *fn, int n, const float *o,
         hl[i] = F4{lambda[4 * i], lambda[4 * i + 1], lambda[4 * i + 2], lambda[4 * i + 3]};
     }
     WorkState ws = ctx->ws;   // counters / stats of the context, every per-item array replaced below
-    std::vector<void *> tmp;
-    auto up = [&](auto **dst, const void *src, size_t bytes) -> int {
-        void *p = nullptr;
-        HIPCHK(hipMalloc(&p, bytes));
-        tmp.push_back(p);
-        if (src) HIPCHK(hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-        else HIPCHK(hipMemsetAsync(p, 0, bytes, ctx->stream));
-        *dst = (std::remove_reference_t<decltype(**dst)> *)p;
-        return 0;
-    };
+    DeviceScratch tmp(ctx->stream);
+    const size_t N = (size_t)n;
     int e;
     int32_t *cnt = nullptr;
-    if ((e = up(&ws.sq.o, ho.data(), n * sizeof(F4))) || (e = up(&ws.sq.d, hd.data(), n * sizeof(F4))) || (e = up(&ws.sq.Ld, Ld, n * sizeof(F4))) ||
-        (e = up(&ws.sq.r_u, r_u, n * sizeof(F4))) || (e = up(&ws.sq.r_l, r_l, n * sizeof(F4))) || (e = up(&ws.sq.medium, medium, n * sizeof(int32_t))) ||
-        (e = up(&ws.lambda, hl.data(), n * sizeof(F4))) || (e = up(&ws.lambdaPdf, hp.data(), n * sizeof(F4))) || (e = up(&ws.L, nullptr, n * sizeof(F4))) ||
-        (e = up(&cnt, nullptr, (size_t)CNT_COUNT * CNT_STRIDE * sizeof(int32_t))))
+    if ((e = tmp.upload(&ws.sq.o, ho.data(), N)) || (e = tmp.upload(&ws.sq.d, hd.data(), N)) || (e = tmp.upload(&ws.sq.Ld, (const void *)Ld, N)) ||
+        (e = tmp.upload(&ws.sq.r_u, (const void *)r_u, N)) || (e = tmp.upload(&ws.sq.r_l, (const void *)r_l, N)) || (e = tmp.upload(&ws.sq.medium, medium, N)) ||
+        (e = tmp.upload(&ws.lambda, hl.data(), N)) || (e = tmp.upload(&ws.lambdaPdf, hp.data(), N)) || (e = tmp.zeroed(&ws.L, N)) ||
+        (e = tmp.zeroed(&cnt, (size_t)CNT_COUNT * CNT_STRIDE)))
         return e;
     HIPCHK(hipMemcpyAsync(cnt + CNT_SHADOW * CNT_STRIDE, &n, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     ws.counters = cnt;
     if (time) {
-        if ((e = up(&ws.pathTime, time, n * sizeof(float)))) return e;
+        if ((e = tmp.upload(&ws.pathTime, time, N))) return e;
         LAUNCH("shadow Tr (host rays, timed)", k_shadow_tr<true>, gridFor(n), ctx->svHost, ws, ctx->stackSpill);
-    } else if (ctx->fastOk && ctx->svHost.nInstances == 0) {
+    } else if (ctx->plan.fastOk && ctx->svHost.nInstances == 0) {
         LAUNCHT("shadow Tr (host rays)", (ctx->svHost.haveAlpha || ctx->svHost.nQuadrics > 0 ? k_shadow_tr_fast<true> : k_shadow_tr_fast<false>), ctx->walk.grid, ctx->svHost, ws, ctx->fast, ctx->spillArea());
     } else LAUNCH("shadow Tr (host rays)", k_shadow_tr<false>, gridFor(n), ctx->svHost, ws, ctx->stackSpill);
     HIPCHK(hipMemcpyAsync(out_L, ws.L, n * sizeof(F4), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    for (void *p : tmp) HIPCHK(hipFree(p));
     return 0;
 }
 int wf_trace_shadow_tr_host(wf_ctx *ctx, int n, const float *o, const float *d, const float *tmax, const int32_t *medium, const float *lambda,
@@ -3697,25 +3876,19 @@ static int TraceOneRandomHost(wf_ctx *ctx, int n, const float *p0, const float *
     std::vector<float> segs((size_t)n * 6);
     for (int i = 0; i < n; ++i)
         for (int k = 0; k < 3; ++k) { segs[(size_t)i * 6 + k] = p0[3 * i + k]; segs[(size_t)i * 6 + 3 + k] = p1[3 * i + k]; }
+    DeviceScratch tmp(ctx->stream);
     float *ds = nullptr, *dp = nullptr, *dt = nullptr;
     int32_t *dm = nullptr;
     wf_hit_record *dh = nullptr;
-    HIPCHK(hipMalloc((void **)&ds, segs.size() * sizeof(float)));
-    HIPCHK(hipMalloc((void **)&dm, (size_t)n * sizeof(int32_t)));
-    HIPCHK(hipMalloc((void **)&dh, (size_t)n * sizeof(wf_hit_record)));
-    HIPCHK(hipMalloc((void **)&dp, (size_t)n * sizeof(float)));
-    HIPCHK(hipMemcpyAsync(ds, segs.data(), segs.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(dm, material, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    int e;
+    if ((e = tmp.upload(&ds, segs.data(), segs.size())) || (e = tmp.upload(&dm, material, (size_t)n)) || (e = tmp.alloc(&dh, (size_t)n)) || (e = tmp.alloc(&dp, (size_t)n))) return e;
     if (time) {
-        HIPCHK(hipMalloc((void **)&dt, (size_t)n * sizeof(float)));
-        HIPCHK(hipMemcpyAsync(dt, time, (size_t)n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+        if ((e = tmp.upload(&dt, time, (size_t)n))) return e;
         LAUNCH("intersect one random (host segments, timed)", k_trace_one_random<true>, gridFor(n), ctx->svHost, n, ds, dm, (const float *)dt, dh, dp, ctx->stackSpill);
     } else LAUNCH("intersect one random (host segments)", k_trace_one_random<false>, gridFor(n), ctx->svHost, n, ds, dm, (const float *)nullptr, dh, dp, ctx->stackSpill);
     HIPCHK(hipMemcpyAsync(out, dh, (size_t)n * sizeof(wf_hit_record), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(reservoir_pdf, dp, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    HIPCHK(hipFree(ds)); HIPCHK(hipFree(dm)); HIPCHK(hipFree(dh)); HIPCHK(hipFree(dp));
-    if (dt) HIPCHK(hipFree(dt));
     return 0;
 }
 int wf_trace_one_random_host(wf_ctx *ctx, int n, const float *p0, const float *p1, const int32_t *material, wf_hit_record *out, float *reservoir_pdf) {
@@ -3730,25 +3903,19 @@ int wf_trace_any_host(wf_ctx *ctx, int n, const float *o, const float *d, const 
     if (ctx->svHost.haveAnimated) return fail(-1, "%s: the scene has animated primitives — a ray needs its time (wf_trace_closest_host_t / wf_trace_any_host_t)", __func__);
     useDevice(ctx);
     if (n <= 0) return 0;
-    std::vector<float> rays((size_t)n * 7);
-    for (int i = 0; i < n; ++i) {
-        for (int k = 0; k < 3; ++k) { rays[(size_t)i * 7 + k] = o[3 * i + k]; rays[(size_t)i * 7 + 3 + k] = d[3 * i + k]; }
-        rays[(size_t)i * 7 + 6] = tmax[i];
-    }
+    const std::vector<float> rays = PackRays7(o, d, tmax, n);
+    DeviceScratch tmp(ctx->stream);
     float *dr = nullptr;
     int32_t *dres = nullptr;
-    HIPCHK(hipMalloc((void **)&dr, rays.size() * sizeof(float)));
-    HIPCHK(hipMalloc((void **)&dres, (size_t)3 * n * sizeof(int32_t)));
-    HIPCHK(hipMemcpyAsync(dr, rays.data(), rays.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    if (nodes_visited || tris_tested || !ctx->fastOk) {
+    int e;
+    if ((e = tmp.upload(&dr, rays.data(), rays.size())) || (e = tmp.alloc(&dres, (size_t)3 * n))) return e;
+    if (nodes_visited || tris_tested || !ctx->plan.fastOk) {
         LAUNCH("trace any (host rays)", k_trace_any, gridFor(n), ctx->svHost, n, dr, dres, dres + n, dres + 2 * (size_t)n, ctx->stackSpill);
-    } else if (int e = wf_trace_any_device(ctx, n, dr, dres)) return e;
+    } else if ((e = wf_trace_any_device(ctx, n, dr, dres))) return e;
     HIPCHK(hipMemcpyAsync(occluded, dres, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     if (nodes_visited) HIPCHK(hipMemcpyAsync(nodes_visited, dres + n, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     if (tris_tested) HIPCHK(hipMemcpyAsync(tris_tested, dres + 2 * (size_t)n, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    HIPCHK(hipFree(dr));
-    HIPCHK(hipFree(dres));
     return 0;
 }
 // IntersectClosest / IntersectShadow on caller-supplied rays WITH their times (the untimed entry points would walk an animated
@@ -3758,24 +3925,18 @@ static int TraceTimed(wf_ctx *ctx, int n, const float *o, const float *d, const 
     if (!o || !d || !tmax || !time) return fail(-1, "wf_trace_*_host_t: null ray arrays");
     useDevice(ctx);
     if (n <= 0) return 0;
-    std::vector<float> rays((size_t)n * 8);
-    for (int i = 0; i < n; ++i) {
-        for (int k = 0; k < 3; ++k) { rays[(size_t)i * 7 + k] = o[3 * i + k]; rays[(size_t)i * 7 + 3 + k] = d[3 * i + k]; }
-        rays[(size_t)i * 7 + 6] = tmax[i];
-        rays[(size_t)n * 7 + i] = time[i];
-    }
+    std::vector<float> rays = PackRays7(o, d, tmax, n);
+    rays.insert(rays.end(), time, time + n);   // the n times behind the n rays
+    DeviceScratch tmp(ctx->stream);
     float *dr = nullptr;
-    void *dres = nullptr;
+    char *dres = nullptr;
     const size_t resBytes = hits ? (size_t)n * sizeof(wf_hit_record) : (size_t)n * sizeof(int32_t);
-    HIPCHK(hipMalloc((void **)&dr, rays.size() * sizeof(float)));
-    HIPCHK(hipMalloc(&dres, resBytes));
-    HIPCHK(hipMemcpyAsync(dr, rays.data(), rays.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    int e;
+    if ((e = tmp.upload(&dr, rays.data(), rays.size())) || (e = tmp.alloc(&dres, resBytes))) return e;
     if (hits) LAUNCH("trace closest (host rays with times)", k_trace_closest_timed, gridFor(n), ctx->svHost, n, dr, dr + (size_t)n * 7, (wf_hit_record *)dres, ctx->stackSpill);
     else LAUNCH("trace any (host rays with times)", k_trace_any_timed, gridFor(n), ctx->svHost, n, dr, dr + (size_t)n * 7, (int32_t *)dres, ctx->stackSpill);
     HIPCHK(hipMemcpyAsync(hits ? (void *)hits : (void *)occluded, dres, resBytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    HIPCHK(hipFree(dr));
-    HIPCHK(hipFree(dres));
     return 0;
 }
 int wf_trace_closest_host_t(wf_ctx *ctx, int n, const float *o, const float *d, const float *tmax, const float *time, wf_hit_record *out) {
@@ -3793,18 +3954,17 @@ int wf_sampler_probe(wf_ctx *ctx, int n, const int32_t *px, const int32_t *py, c
     if (ndims == 0 || ndims < -4 || ndims == -1) return fail(-1, "wf_sampler_probe: ndims %d", ndims);
     const int mode = ndims;
     ndims = mode > 0 ? mode : mode == -3 ? 30 : 2;   // floats per record (SamplerProbeRecord, wf_camera.h)
+    DeviceScratch tmp(ctx->stream);
     int32_t *din = nullptr;
     float *dout = nullptr;
-    HIPCHK(hipMalloc((void **)&din, (size_t)3 * n * sizeof(int32_t)));
-    HIPCHK(hipMalloc((void **)&dout, (size_t)n * ndims * sizeof(float)));
+    int e;
+    if ((e = tmp.alloc(&din, (size_t)3 * n)) || (e = tmp.alloc(&dout, (size_t)n * ndims))) return e;
     HIPCHK(hipMemcpyAsync(din, px, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(din + n, py, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(din + 2 * (size_t)n, sample_index, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
     LAUNCH("sampler probe", k_sampler_probe, gridFor(n), ctx->svHost, n, din, din + n, din + 2 * (size_t)n, start_dim, mode, dout);
     HIPCHK(hipMemcpyAsync(out, dout, (size_t)n * ndims * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    HIPCHK(hipFree(din));
-    HIPCHK(hipFree(dout));
     return 0;
 }
 
@@ -3836,15 +3996,13 @@ int wf_libm_probe(wf_ctx *ctx, int fn, int n, const float *in, float *out) {
     if (fn < 0 || fn > 11) return fail(-1, "wf_libm_probe: unknown function %d", fn);
     if (n <= 0) return 0;
     size_t nin = (size_t)n * (fn == 9 ? 2 : 1);
+    DeviceScratch tmp(ctx->stream);
     float *din = nullptr, *dout = nullptr;
-    HIPCHK(hipMalloc((void **)&din, nin * sizeof(float)));
-    HIPCHK(hipMalloc((void **)&dout, (size_t)n * sizeof(float)));
-    HIPCHK(hipMemcpyAsync(din, in, nin * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    int e;
+    if ((e = tmp.upload(&din, in, nin)) || (e = tmp.alloc(&dout, (size_t)n))) return e;
     LAUNCH("libm probe", k_libm_probe, gridFor(n), fn, n, din, dout);
     HIPCHK(hipMemcpyAsync(out, dout, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    HIPCHK(hipFree(din));
-    HIPCHK(hipFree(dout));
     return 0;
 }
 
@@ -3854,15 +4012,13 @@ __global__ void k_kat_probe(int n, const uint64_t *in, uint64_t *out) {
 int wf_kat_probe(wf_ctx *ctx, int n, const uint64_t *in, uint64_t *out) {
     if (!ctx) return fail(-1, "null context");
     if (n <= 0) return 0;
+    DeviceScratch tmp(ctx->stream);
     uint64_t *din = nullptr, *dout = nullptr;
-    HIPCHK(hipMalloc((void **)&din, (size_t)n * 16 * sizeof(uint64_t)));
-    HIPCHK(hipMalloc((void **)&dout, (size_t)n * 8 * sizeof(uint64_t)));
-    HIPCHK(hipMemcpyAsync(din, in, (size_t)n * 16 * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    int e;
+    if ((e = tmp.upload(&din, in, (size_t)n * 16)) || (e = tmp.alloc(&dout, (size_t)n * 8))) return e;
     LAUNCH("known-answer probe", k_kat_probe, gridFor(n), n, din, dout);
     HIPCHK(hipMemcpyAsync(out, dout, (size_t)n * 8 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    HIPCHK(hipFree(din));
-    HIPCHK(hipFree(dout));
     return 0;
 }
 

@@ -31,6 +31,12 @@ WavefrontRenderer::WavefrontRenderer(const SceneTables &tables, int device, int 
     // indices instead, so its launches stay as large as a single GPU's (as far as the render has that many sample indices).
     const int W = T.desc.film.pixel_max[0] - T.desc.film.pixel_min[0];
     Check(wf_ctx_create(device, &ctx), "wf_ctx_create");
+    // (a constructor that throws runs no destructor: a Check that fails below takes the context, and its device memory, with it)
+    struct CtxGuard {
+        wf_ctx *&ctx;
+        bool armed = true;
+        ~CtxGuard() { if (armed) { wf_ctx_destroy(ctx); ctx = nullptr; } }
+    } guard{ctx};
     Check(wf_scene_upload(ctx, &T.desc), "wf_scene_upload");
     localRows = T.desc.film.pixel_max[1] - T.desc.film.pixel_min[1];
     if (stripCount > 1) Check(wf_set_strips(ctx, stripRank, stripCount, stripHeight, &localRows), "wf_set_strips");
@@ -66,6 +72,7 @@ WavefrontRenderer::WavefrontRenderer(const SceneTables &tables, int device, int 
     Check(wf_queues_alloc(ctx, pixelsPerPass, samplesPerPass), "wf_queues_alloc");
     Check(wf_film_clear(ctx), "wf_film_clear");
     Check(wf_sync(ctx), "wf_sync");
+    guard.armed = false;
 }
 
 WavefrontRenderer::~WavefrontRenderer() {

@@ -58,7 +58,7 @@ ABI_SYMBOLS = [
     "wf_film_device_ptr", "wf_film_upload", "wf_film_spectral_download", "wf_film_gbuffer_download", "wf_film_copy_to_device", "wf_film_copy_from_device", "wf_film_gather_strips", "wf_stats_add", "wf_material_items_download", "wf_stats_download",
     "wf_profile_report", "wf_profile_enable",
     "wf_trace_closest_host", "wf_trace_any_host", "wf_sampler_probe", "wf_libm_probe", "wf_kat_probe", "wf_queue_size", "wf_queue_download",
-    "wf_counters_enable", "wf_counters_download", "wf_kernel_time_ms", "wf_debug_counters", "wf_debug_fastbvh_check", "wf_scene_check_instances", "wf_trace_closest_host_t", "wf_trace_any_host_t", "wf_ctx_query",
+    "wf_counters_enable", "wf_counters_download", "wf_kernel_time_ms", "wf_debug_counters", "wf_debug_fastbvh_check", "wf_scene_check_instances", "wf_scene_plan_query", "wf_trace_closest_host_t", "wf_trace_any_host_t", "wf_ctx_query",
     "wf_trace_closest_device", "wf_trace_any_device", "wf_device_alloc", "wf_device_free", "wf_device_upload", "wf_device_download", "wf_trace_shadow_tr_host",
     "wf_trace_shadow_tr_host_t", "wf_trace_one_random_host_t",
 ]
@@ -415,6 +415,16 @@ class Scene:
             hip.wf_last_error.restype = C.c_char_p
             raise WfError("wf_scene_check_instances: " + hip.wf_last_error().decode())
         return dict(zip(["bvh_prims", "top_level_instances", "nested_records", "nested_entries"], [int(v) for v in out]))
+
+    def plan(self, key):
+        """host-only form of query() (wf_scene_plan_query): which kernel variants an upload of this scene would choose under the current
+        environment switches.  Needs no device and no renderer."""
+        host, hip = libs()
+        v = C.c_int64(0)
+        hip.wf_scene_plan_query.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)]
+        if hip.wf_scene_plan_query(host.wfh_scene_desc(self.h), key.encode(), C.byref(v)) != 0:
+            raise WfError("wf_scene_plan_query: " + hip.wf_last_error().decode())
+        return int(v.value)
 
     def enable_profile(self, on=True):
         _, hip = libs()

@@ -257,6 +257,18 @@ def test_variant_selection_queries(wfpt):
     assert r["fast_ok"] == 1 and r["gen_mode"] >= 2 and r["defer_general"] == 1 and r["instances"] > 0, r
     assert q("instances_quadrics", ["defer_general"], WF_DEFER_GENERAL=0)["defer_general"] == 0
     assert q("animated_sss", ["fast_ok", "anim_fast"], WF_ANIM_FAST=0) == {"fast_ok": 0, "anim_fast": 0}
+    # the host-only planning step (Scene.plan, tests/test_scene_plan_host.py) gives, without a device, the answers the uploaded scene gives.
+    # Both sides read one key table over a PlanScene result, so what this pins is that the upload keeps the plan as it was made (and that
+    # the context's copy is the one queried); the values themselves are pinned above and in the CPU suite.
+    shared = ["fast_ok", "gen_mode", "gen_tri", "defer_general", "anim_fast", "lean_shade", "rare_lights", "medium_lean", "instances", "nested_animated"] + ["lean_type_%d" % t for t in range(11)]
+    for name in ["cornell64", "instances_quadrics", "media_box", "media_instances", "cloud_medium", "rgbgrid_medium", "tempgrid_medium", "animated", "animated_sss", "animated_tris",
+                 "animated_tris_alpha", "animated_interface", "animated_interface_sphere", "animated_mix", "animated_subsurface", "animated_in_definition", "animated_in_definition_general", "animated_in_definition_media",
+                 "animated_in_definition_sss"]:
+        s = wfpt.Scene(path=os.path.join(GOLDEN, name + ".pbrt"), spp=4)
+        s.create_renderer(0)
+        got, planned = {k: s.query(k) for k in shared}, {k: s.plan(k) for k in shared}
+        s.close()
+        assert got == planned, name
 
 
 @pytest.mark.parametrize("name", ["sanmiguel_like_small", "tm_like_small", "cloud_like_small"])
