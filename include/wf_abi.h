@@ -739,6 +739,25 @@ int wf_trace_any_host_t(wf_ctx *ctx, int n, const float *o, const float *d, cons
    of that device for callers without a HIP runtime of their own (uploads and downloads are synchronous). */
 int wf_trace_closest_device(wf_ctx *ctx, int n, const float *rays7, wf_hit_record *out);
 int wf_trace_any_device(wf_ctx *ctx, int n, const float *rays7, int32_t *occluded);
+/* ... with the rays' TIMES, for any scene: rays8 = n x {o[3], d[3], tMax, time} floats, a DEVICE pointer aligned to 16 bytes (a ray is
+   read as two 16-byte loads); out / occluded: device.  Which walk answers: a static scene — the walk of the two calls above (the time
+   is ignored); a scene whose AnimatedPrimitives the render walks with the production kernels ("anim_fast", wf_ctx_query) — those
+   kernels' ANIM variants, near ties resolved inside the walk at the ray's time; any other animated scene (quadrics, nested placements,
+   WF_ANIM_FAST=0) — the reference-order walk of wf_trace_*_host_t on the caller's buffers.  nodes_visited / tris_tested of the records
+   are 0 on every path.  Launched on the context's stream and NOT synchronised, like the two calls above; n <= 0 touches nothing. */
+int wf_trace_closest_device_t(wf_ctx *ctx, int n, const float *rays8, wf_hit_record *out);
+int wf_trace_any_device_t(wf_ctx *ctx, int n, const float *rays8, int32_t *occluded);
+/* WavefrontAggregate::IntersectShadowTr on DEVICE items (wf_trace_shadow_tr_host / _host_t below describe the values): rays8 as above;
+   medium[n]; lambda / Ld / r_u / r_l / out_L = n x 4 floats, read and written in place — out_L is zeroed, then written, by the
+   launches; all device pointers.  Scenes with media.  The transmittance kernel is the one the host-array call runs for the scene (with
+   the times on a scene with animated primitives, without them otherwise).  The packed ray items live in scratch the context owns,
+   grown on demand (growth may synchronise) and reused by the next call, which the in-order stream makes safe.  Not synchronised. */
+int wf_trace_shadow_tr_device(wf_ctx *ctx, int n, const float *rays8, const int32_t *medium, const float *lambda,
+                              const float *Ld, const float *r_u, const float *r_l, float *out_L);
+/* WavefrontAggregate::IntersectOneRandom on DEVICE segments (wf_trace_one_random_host / _host_t below): segs7 = n x {p0[3], p1[3], time}
+   floats; material[n]; out[n]; reservoir_pdf[n]; all device pointers.  Any scene (a static one ignores the time).  Not synchronised. */
+int wf_trace_one_random_device(wf_ctx *ctx, int n, const float *segs7, const int32_t *material,
+                               wf_hit_record *out, float *reservoir_pdf);
 int wf_device_alloc(wf_ctx *ctx, uint64_t nbytes, void **dptr);
 int wf_device_free(wf_ctx *ctx, void *dptr);
 int wf_device_upload(wf_ctx *ctx, void *dst_device, const void *src_host, uint64_t nbytes);

@@ -88,6 +88,10 @@ struct WalkKernels {
     TrTraceFn trTrace = nullptr;       // the transmittance wavefront's walk (genMode <= 1 only: null otherwise)
     TraceClosestFn traceClosest = nullptr;   // wf_trace_closest_device / wf_trace_any_device
     TraceAnyFn traceAny = nullptr;
+    // wf_trace_closest_device_t / wf_trace_any_device_t (rays8): the same variants reading eight floats per ray, or — plan.animFast — the
+    // ANIM variants the render walks the scene's AnimatedPrimitives with, at every ray's own time
+    TraceClosestFn traceClosest8 = nullptr;
+    TraceAnyFn traceAny8 = nullptr;
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -211,6 +215,16 @@ struct wf_ctx {
     bool cursorDirty[2] = {false, false};   // the closest-hit / any-hit work cursor has been used since a k_reset last zeroed it
     ScenePlan plan;              // what the uploaded scene runs: written by PlanScene, read by PickWalkKernels, the launch sites and wf_queues_alloc
     WalkKernels walk;
+    // The scratch of wf_trace_shadow_tr_device: the packed shadow-queue items of the call (k_pack_shadow_items) and its counter block.
+    // Owned by the context and grown geometrically (GrowTrScratch: the only place a call may synchronise or allocate), freed in
+    // DestroyCtx.  The next call overwrites it without waiting: every launch that reads it is on the context's in-order stream, ahead
+    // of the pack kernel that rewrites it.
+    struct TrScratch {
+        F4 *o = nullptr, *d = nullptr, *lambdaPdf = nullptr;
+        float *pathTime = nullptr;
+        int32_t *counters = nullptr;
+        size_t capacity = 0;   // items
+    } trScratch;
     int32_t *probeCursor = nullptr;
     int W = 0, H = 0;
     int maxDepth = 5;
@@ -1206,18 +1220,20 @@ __global__ void __launch_bounds__(BLOCK) k_intersect_one_random(const SceneView 
     LdsStack st{stackSpill + gtid, stride, 0};
     for (int i = gtid; i < n; i += stride) KIntersectOneRandom<ANIM>(sv, ws, i, st);
 }
-// IntersectOneRandom on caller-supplied probe segments (the boundary adapter's path): segs = p0.xyz p1.xyz per item
-// ANIM: walked at times[i] (wf_trace_one_random_host_t); otherwise at time 0 on a static scene
+// IntersectOneRandom on caller-supplied probe segments (the boundary adapter's path): segs = p0.xyz p1.xyz at the head of every
+// segStride floats (6: the packed host arrays; 7: the caller's device segments {p0, p1, time}, wf_trace_one_random_device)
+// ANIM: walked at times[timeStride * i] (the host call's array of times, or the seventh float of the device segments); otherwise at
+// time 0 on a static scene
 template <bool ANIM>
-__global__ void __launch_bounds__(BLOCK) k_trace_one_random(const SceneView sv, int n, const float *segs, const int32_t *material, const float *times, wf_hit_record *out,
-                                                            float *pdf, int *stackSpill) {
+__global__ void __launch_bounds__(BLOCK) k_trace_one_random(const SceneView sv, int n, const float *segs, int segStride, const int32_t *material, const float *times,
+                                                            int timeStride, wf_hit_record *out, float *pdf, int *stackSpill) {
     const int gtid = blockIdx.x * BLOCK + threadIdx.x, stride = gridDim.x * BLOCK;
     LdsStack st{stackSpill + gtid, stride, 0};
     for (int i = gtid; i < n; i += stride) {
-        const float *s = segs + (size_t)6 * i;
+        const float *s = segs + (size_t)segStride * i;
         ClosestHit ch;
         SurfIntr si;
-        float p = IntersectOneRandom<ANIM>(sv, V3{s[0], s[1], s[2]}, V3{s[3], s[4], s[5]}, material[i], st, &ch, &si, ANIM ? times[i] : 0.f);
+        float p = IntersectOneRandom<ANIM>(sv, V3{s[0], s[1], s[2]}, V3{s[3], s[4], s[5]}, material[i], st, &ch, &si, ANIM ? times[(size_t)timeStride * i] : 0.f);
         wf_hit_record h{};
         h.prim = p != 0 ? ch.prim : -1;
         if (p != 0) { h.t = ch.h.t; h.b0 = ch.h.b0; h.b1 = ch.h.b1; h.b2 = ch.h.b2; h.instance = ch.inst; } else h.instance = -1;
@@ -1255,17 +1271,31 @@ __global__ void __launch_bounds__(TBLOCK, TWavesFor(GenBase(GEN), INST ? WF_TWAV
         }, cursor, chunk);
 }
 
+// A ray of the stand-alone walks.  STRIDE 7: {o[3], d[3], tMax} (wf_trace_*_device).  STRIDE 8: {o[3], d[3], tMax, time}, aligned to 16
+// bytes and read as two 16-byte loads (wf_trace_*_device_t); the ANIM variants (GenAnim) leave the time where the instance entries of
+// the walk read it, as k_shadow_fast does — a static scene's variants ignore it.
+template <int GEN, int STRIDE>
+__device__ inline void FetchTraceRay(const float *rays, int i, V3 *o, V3 *d, float *tMax) {
+    static_assert(STRIDE == 7 || STRIDE == 8, "rays7 or rays8");
+    static_assert(STRIDE == 8 || !GenAnim(GEN), "a ray of an animated scene needs its time");
+    if constexpr (STRIDE == 8) {
+        const F4 *r = reinterpret_cast<const F4 *>(rays) + (size_t)2 * i;
+        const F4 a = r[0], b = r[1];
+        *o = V3{a.x, a.y, a.z}; *d = V3{a.w, b.x, b.y}; *tMax = b.z;
+        if constexpr (GenAnim(GEN)) g_time[threadIdx.x] = b.w;
+    } else {
+        const float *r = rays + (size_t)7 * i;
+        *o = V3{r[0], r[1], r[2]}; *d = V3{r[3], r[4], r[5]}; *tMax = r[6];
+    }
+}
 // GENERAL: the scene has alpha-tested triangles or quadrics (the variant the render uses then)
-template <int GEN, bool INST>
+template <int GEN, bool INST, int STRIDE = 7>
 __global__ void __launch_bounds__(TBLOCK) k_trace_closest_fast(const SceneView sv, FastBVH bvh, int n, const float *rays, wf_hit_record *out, SpillArea sp) {
     const int gtid = blockIdx.x * TBLOCK + threadIdx.x, stride = gridDim.x * TBLOCK;
     LdsStackT st{sp.base + gtid, stride, 0, 0, sp.rows, sp.dbg};
     TraceQueue<false, GEN, INST>(
         sv, bvh, n, st,
-        [&](int i, V3 *o, V3 *d, float *tMax) {
-            const float *r = rays + (size_t)7 * i;
-            *o = V3{r[0], r[1], r[2]}; *d = V3{r[3], r[4], r[5]}; *tMax = r[6];
-        },
+        [&](int i, V3 *o, V3 *d, float *tMax) { FetchTraceRay<GEN, STRIDE>(rays, i, o, d, tMax); },
         [&](int i, bool valid, const RayWalk &w) {
             if (!valid) return;
             wf_hit_record h;
@@ -1277,16 +1307,13 @@ __global__ void __launch_bounds__(TBLOCK) k_trace_closest_fast(const SceneView s
             out[i] = h;
         });
 }
-template <int GEN, bool INST>
+template <int GEN, bool INST, int STRIDE = 7>
 __global__ void __launch_bounds__(TBLOCK) k_trace_any_fast(const SceneView sv, FastBVH bvh, int n, const float *rays, int32_t *occluded, SpillArea sp) {
     const int gtid = blockIdx.x * TBLOCK + threadIdx.x, stride = gridDim.x * TBLOCK;
     LdsStackT st{sp.base + gtid, stride, 0, 0, sp.rows, sp.dbg};
     TraceQueue<true, GEN, INST>(
         sv, bvh, n, st,
-        [&](int i, V3 *o, V3 *d, float *tMax) {
-            const float *r = rays + (size_t)7 * i;
-            *o = V3{r[0], r[1], r[2]}; *d = V3{r[3], r[4], r[5]}; *tMax = r[6];
-        },
+        [&](int i, V3 *o, V3 *d, float *tMax) { FetchTraceRay<GEN, STRIDE>(rays, i, o, d, tMax); },
         [&](int i, bool valid, const RayWalk &w) { if (valid) occluded[i] = w.prim >= 0; });
 }
 
@@ -1536,56 +1563,79 @@ __global__ void __launch_bounds__(BLOCK) k_update_film_pm(const SceneView sv, Wo
     }
 }
 
-// stand-alone traversal for parity tests / counters: rays as packed {o[3], d[3], tMax}
-// onlyMarked: the re-trace pass after k_trace_closest_fast — only the records it marked as near-ties (nodes_visited == -1)
-__global__ void __launch_bounds__(BLOCK) k_trace_closest(const SceneView sv, int n, const float *rays, wf_hit_record *out, int *stackSpill, int onlyMarked) {
+// stand-alone traversal for parity tests / counters: rays as {o[3], d[3], tMax} at the head of every rayStride floats (7: packed;
+// 8: the rays8 of wf_trace_*_device_t on a static scene, whose eighth float — the time — is not read)
+// mode & TRACE_ONLY_MARKED: the re-trace pass after k_trace_closest_fast — only the records it marked as near-ties (nodes_visited == -1)
+// mode & TRACE_NO_COUNTS: nodes_visited / tris_tested = 0 (the records of the device-buffer calls with times carry none, on any walk)
+constexpr int TRACE_ONLY_MARKED = 1, TRACE_NO_COUNTS = 2;
+__global__ void __launch_bounds__(BLOCK) k_trace_closest(const SceneView sv, int n, const float *rays, int rayStride, wf_hit_record *out, int *stackSpill, int mode) {
     const int gtid = blockIdx.x * BLOCK + threadIdx.x, stride = gridDim.x * BLOCK;
     LdsStack st{stackSpill + gtid, stride, 0};
+    const bool onlyMarked = (mode & TRACE_ONLY_MARKED) != 0, counts = mode == 0;
     for (int i = gtid; i < n; i += stride) {
         if (onlyMarked && out[i].nodes_visited != -1) continue;
-        const float *r = rays + (size_t)7 * i;
+        const float *r = rays + (size_t)rayStride * i;
         ClosestHit ch;
         st.n = 0;
         bool found = BVHIntersectClosest(sv, V3{r[0], r[1], r[2]}, V3{r[3], r[4], r[5]}, r[6], st, &ch);
         wf_hit_record h;
         h.prim = found ? ch.prim : -1;
         h.t = found ? ch.h.t : 0; h.b0 = found ? ch.h.b0 : 0; h.b1 = found ? ch.h.b1 : 0; h.b2 = found ? ch.h.b2 : 0;
-        h.nodes_visited = onlyMarked ? 0 : ch.nodesVisited; h.tris_tested = onlyMarked ? 0 : ch.trisTested; h.instance = found ? ch.inst : -1;
+        h.nodes_visited = counts ? ch.nodesVisited : 0; h.tris_tested = counts ? ch.trisTested : 0; h.instance = found ? ch.inst : -1;
         out[i] = h;
     }
 }
 // ... and at the rays' own TIMES (AnimatedPrimitive, cpu/primitive.cpp:132-158: the reference's WavefrontAggregate reads ray.time): the
-// reference-order walks with the per-ray interpolation of the animated transformations (wf_trace_*_host_t)
-__global__ void __launch_bounds__(BLOCK) k_trace_closest_timed(const SceneView sv, int n, const float *rays, const float *times, wf_hit_record *out, int *stackSpill) {
+// reference-order walks with the per-ray interpolation of the animated transformations.  Ray i at rays + rayStride i, its time at
+// times[timeStride i]: (7, 1) the host call's packed rays with the n times behind them (wf_trace_*_host_t), (8, 8) the caller's rays8
+// with times = rays8 + 7 (wf_trace_*_device_t on the animated scenes the production walk does not take).  counts = 0: no visit counts
+__global__ void __launch_bounds__(BLOCK) k_trace_closest_timed(const SceneView sv, int n, const float *rays, int rayStride, const float *times, int timeStride,
+                                                               wf_hit_record *out, int *stackSpill, int counts) {
     const int gtid = blockIdx.x * BLOCK + threadIdx.x, stride = gridDim.x * BLOCK;
     LdsStack st{stackSpill + gtid, stride, 0};
     for (int i = gtid; i < n; i += stride) {
-        const float *r = rays + (size_t)7 * i;
+        const float *r = rays + (size_t)rayStride * i;
         ClosestHit ch;
         st.n = 0;
-        bool found = BVHIntersectClosest<true>(sv, V3{r[0], r[1], r[2]}, V3{r[3], r[4], r[5]}, r[6], st, &ch, times[i]);
+        bool found = BVHIntersectClosest<true>(sv, V3{r[0], r[1], r[2]}, V3{r[3], r[4], r[5]}, r[6], st, &ch, times[(size_t)timeStride * i]);
         wf_hit_record h;
         h.prim = found ? ch.prim : -1;
         h.t = found ? ch.h.t : 0; h.b0 = found ? ch.h.b0 : 0; h.b1 = found ? ch.h.b1 : 0; h.b2 = found ? ch.h.b2 : 0;
-        h.nodes_visited = ch.nodesVisited; h.tris_tested = ch.trisTested; h.instance = found ? ch.inst : -1;
+        h.nodes_visited = counts ? ch.nodesVisited : 0; h.tris_tested = counts ? ch.trisTested : 0; h.instance = found ? ch.inst : -1;
         out[i] = h;
     }
 }
-__global__ void __launch_bounds__(BLOCK) k_trace_any_timed(const SceneView sv, int n, const float *rays, const float *times, int32_t *occluded, int *stackSpill) {
+__global__ void __launch_bounds__(BLOCK) k_trace_any_timed(const SceneView sv, int n, const float *rays, int rayStride, const float *times, int timeStride,
+                                                           int32_t *occluded, int *stackSpill) {
     const int gtid = blockIdx.x * BLOCK + threadIdx.x, stride = gridDim.x * BLOCK;
     LdsStack st{stackSpill + gtid, stride, 0};
     for (int i = gtid; i < n; i += stride) {
-        const float *r = rays + (size_t)7 * i;
+        const float *r = rays + (size_t)rayStride * i;
         int v = 0, t = 0;
         st.n = 0;
-        occluded[i] = BVHIntersectAny<true>(sv, V3{r[0], r[1], r[2]}, V3{r[3], r[4], r[5]}, r[6], st, &v, &t, times[i]);
+        occluded[i] = BVHIntersectAny<true>(sv, V3{r[0], r[1], r[2]}, V3{r[3], r[4], r[5]}, r[6], st, &v, &t, times[(size_t)timeStride * i]);
     }
 }
-__global__ void __launch_bounds__(BLOCK) k_trace_any(const SceneView sv, int n, const float *rays, int32_t *occluded, int32_t *nodes, int32_t *tris, int *stackSpill) {
+// IntersectShadowTr on the caller's DEVICE items (wf_trace_shadow_tr_device): the per-item arrays of the scratch WorkState that the
+// transmittance kernels read and the caller does not supply — the shadow queue's (o, tMax) and (d, pixelIndex = i), the wavelengths' pdf
+// (1), the item's path time (animated scenes: pathTime != nullptr) — the zeroed result, and the counter block with CNT_SHADOW = n
+__global__ void __launch_bounds__(BLOCK) k_pack_shadow_items(int n, const float *rays8, F4 *o, F4 *d, F4 *lambdaPdf, float *pathTime, F4 *L, int32_t *counters) {
+    if (blockIdx.x == 0 && threadIdx.x < CNT_COUNT) counters[threadIdx.x * CNT_STRIDE] = threadIdx.x == CNT_SHADOW ? n : 0;
+    for (int i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) {
+        const F4 *r = reinterpret_cast<const F4 *>(rays8) + (size_t)2 * i;
+        const F4 a = r[0], b = r[1];
+        o[i] = F4{a.x, a.y, a.z, b.z};
+        d[i] = F4{a.w, b.x, b.y, BitsToFloat((uint32_t)i)};
+        lambdaPdf[i] = F4{1, 1, 1, 1};
+        if (pathTime) pathTime[i] = b.w;
+        L[i] = F4{0, 0, 0, 0};
+    }
+}
+__global__ void __launch_bounds__(BLOCK) k_trace_any(const SceneView sv, int n, const float *rays, int rayStride, int32_t *occluded, int32_t *nodes, int32_t *tris, int *stackSpill) {
     const int gtid = blockIdx.x * BLOCK + threadIdx.x, stride = gridDim.x * BLOCK;
     LdsStack st{stackSpill + gtid, stride, 0};
     for (int i = gtid; i < n; i += stride) {
-        const float *r = rays + (size_t)7 * i;
+        const float *r = rays + (size_t)rayStride * i;
         int v = 0, t = 0;
         st.n = 0;
         bool occ = BVHIntersectAny(sv, V3{r[0], r[1], r[2]}, V3{r[3], r[4], r[5]}, r[6], st, &v, &t);
@@ -2425,6 +2475,8 @@ struct ShadowWalk { using Fn = ShadowWalkFn; template <int G, bool I> static Fn 
 struct TrTraceWalk { using Fn = TrTraceFn; template <int G, bool I> static Fn of() { return k_tr_trace<G, I>; } };
 struct TraceClosestWalk { using Fn = TraceClosestFn; template <int G, bool I> static Fn of() { return k_trace_closest_fast<G, I>; } };
 struct TraceAnyWalk { using Fn = TraceAnyFn; template <int G, bool I> static Fn of() { return k_trace_any_fast<G, I>; } };
+struct TraceClosestWalk8 { using Fn = TraceClosestFn; template <int G, bool I> static Fn of() { return k_trace_closest_fast<G, I, 8>; } };   // (rays8)
+struct TraceAnyWalk8 { using Fn = TraceAnyFn; template <int G, bool I> static Fn of() { return k_trace_any_fast<G, I, 8>; } };
 // K<G, inst> for the G of the pack that equals genx; null if there is none.  The packs handed in are the variants the library holds —
 // a pair that appears nowhere here is not compiled.  The ANIM variants (GenAnim) exist two-level only: an animated shape is an instance.
 template <typename K, bool INST, int G>
@@ -2453,8 +2505,15 @@ static int PickWalkKernels(wf_ctx *ctx) {
     }
     k.traceClosest = PickWalk<TraceClosestWalk>(gen, inst, std::integer_sequence<int, 0, 1, 2, 3>{});
     k.traceAny = PickWalk<TraceAnyWalk>(gen, inst, std::integer_sequence<int, 0, 1, 2, 3>{});
+    {
+        // the timed boundary calls: a static scene's rays through the variants above, an animFast scene's (genMode <= 1: near ties are
+        // resolved inside the walk — RetraceInline — at the ray's time) through the ANIM variants of the render's walks
+        using TimedWalks = std::integer_sequence<int, 0, 1, 2, 3, GenX(0, false, true), GenX(1, false, true)>;
+        k.traceClosest8 = PickWalk<TraceClosestWalk8>(GenX(gen, false, ctx->plan.animFast), inst, TimedWalks{});
+        k.traceAny8 = PickWalk<TraceAnyWalk8>(GenX(gen, false, ctx->plan.animFast), inst, TimedWalks{});
+    }
     if (RetraceInline(gen)) k.trTrace = PickWalk<TrTraceWalk>(gen, inst, std::integer_sequence<int, 0, 1>{});   // (resolves its near ties inside the walk)
-    if (!k.closest || !k.shadow || !k.traceClosest || !k.traceAny || (ctx->plan.deferGeneral && (!k.closestGen || !k.shadowGen)) || (RetraceInline(gen) && !k.trTrace))
+    if (!k.closest || !k.shadow || !k.traceClosest || !k.traceAny || !k.traceClosest8 || !k.traceAny8 || (ctx->plan.deferGeneral && (!k.closestGen || !k.shadowGen)) || (RetraceInline(gen) && !k.trTrace))
         return fail(-1, "no walk kernel for this scene (genMode %d, genTri %d, two-class %d, animated %d, instances %d)", gen, ctx->plan.genTri, (int)ctx->plan.deferGeneral, (int)ctx->plan.animFast, (int)inst);
     // resident workgroups of the queue walks (closest-hit and shadow differ in registers)
     hipDeviceProp_t prop;
@@ -2772,6 +2831,8 @@ static void DestroyCtx(wf_ctx *ctx) {
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     if (ctx->stream3) (void)hipStreamSynchronize(ctx->stream3);
     for (void *p : ctx->allocs) (void)hipFree(p);
+    for (void *p : {(void *)ctx->trScratch.o, (void *)ctx->trScratch.d, (void *)ctx->trScratch.lambdaPdf, (void *)ctx->trScratch.pathTime, (void *)ctx->trScratch.counters})
+        if (p) (void)hipFree(p);
     for (auto &e : ctx->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     for (auto e : ctx->eventPool) (void)hipEventDestroy(e);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -3758,22 +3819,134 @@ int wf_counters_download(wf_ctx *ctx, wf_traversal_counters *out) {
 
 int wf_trace_closest_device(wf_ctx *ctx, int n, const float *rays7, wf_hit_record *out) {
     if (!ctx || !ctx->sceneLoaded) return fail(-1, "no scene uploaded");
-    if (ctx->svHost.haveAnimated) return fail(-1, "%s: the scene has animated primitives — a ray needs its time (wf_trace_closest_host_t / wf_trace_any_host_t)", __func__);
+    if (ctx->svHost.haveAnimated) return fail(-1, "%s: the scene has animated primitives — a ray needs its time (wf_trace_closest_device_t / wf_trace_any_device_t)", __func__);
     useDevice(ctx);
     if (n <= 0) return 0;
-    if (!ctx->plan.fastOk) { LAUNCH("trace closest (device rays)", k_trace_closest, gridFor(n), ctx->svHost, n, rays7, out, ctx->stackSpill, 0); return 0; }
+    if (!ctx->plan.fastOk) { LAUNCH("trace closest (device rays)", k_trace_closest, gridFor(n), ctx->svHost, n, rays7, 7, out, ctx->stackSpill, 0); return 0; }
     LAUNCHT("trace closest fast (device rays)", ctx->walk.traceClosest, ctx->walk.grid, ctx->svHost, ctx->fast, n, rays7, out, ctx->spillArea());
     // (the variants that do not resolve their near ties inside the walk mark them: re-traced in reference order)
-    if (!RetraceInline(ctx->plan.genMode)) LAUNCH("trace closest (near-tie re-trace)", k_trace_closest, gridFor(n), ctx->svHost, n, rays7, out, ctx->stackSpill, 1);
+    if (!RetraceInline(ctx->plan.genMode)) LAUNCH("trace closest (near-tie re-trace)", k_trace_closest, gridFor(n), ctx->svHost, n, rays7, 7, out, ctx->stackSpill, TRACE_ONLY_MARKED);
     return 0;
 }
 int wf_trace_any_device(wf_ctx *ctx, int n, const float *rays7, int32_t *occluded) {
     if (!ctx || !ctx->sceneLoaded) return fail(-1, "no scene uploaded");
-    if (ctx->svHost.haveAnimated) return fail(-1, "%s: the scene has animated primitives — a ray needs its time (wf_trace_closest_host_t / wf_trace_any_host_t)", __func__);
+    if (ctx->svHost.haveAnimated) return fail(-1, "%s: the scene has animated primitives — a ray needs its time (wf_trace_closest_device_t / wf_trace_any_device_t)", __func__);
     useDevice(ctx);
     if (n <= 0) return 0;
-    if (!ctx->plan.fastOk) { LAUNCH("trace any (device rays)", k_trace_any, gridFor(n), ctx->svHost, n, rays7, occluded, (int32_t *)nullptr, (int32_t *)nullptr, ctx->stackSpill); return 0; }
+    if (!ctx->plan.fastOk) { LAUNCH("trace any (device rays)", k_trace_any, gridFor(n), ctx->svHost, n, rays7, 7, occluded, (int32_t *)nullptr, (int32_t *)nullptr, ctx->stackSpill); return 0; }
     LAUNCHT("trace any fast (device rays)", ctx->walk.traceAny, ctx->walk.grid, ctx->svHost, ctx->fast, n, rays7, occluded, ctx->spillArea());
+    return 0;
+}
+// The transmittance launch of a boundary call over its scratch WorkState `ws` of n items — wf_trace_shadow_tr_host / _host_t and
+// wf_trace_shadow_tr_device choose their kernel HERE, so that the device-buffer call runs what the host-array call of the same
+// timed-ness runs.  timed: the items carry times (ws.pathTime) and the reference-order walk's ANIM variant, the render's kernel for
+// scenes with animated primitives, interpolates at them; otherwise the render's per-lane production walk where it has one (one-level
+// scenes), else the reference-order walk.
+static int LaunchBoundaryTr(wf_ctx *ctx, const WorkState &ws, int n, bool timed, const char *nameTimed, const char *nameUntimed) {
+    if (timed) {
+        LAUNCH(nameTimed, k_shadow_tr<true>, gridFor(n), ctx->svHost, ws, ctx->stackSpill);
+    } else if (ctx->plan.fastOk && ctx->svHost.nInstances == 0) {
+        LAUNCHT(nameUntimed, (ctx->svHost.haveAlpha || ctx->svHost.nQuadrics > 0 ? k_shadow_tr_fast<true> : k_shadow_tr_fast<false>), ctx->walk.grid, ctx->svHost, ws, ctx->fast, ctx->spillArea());
+    } else LAUNCH(nameUntimed, k_shadow_tr<false>, gridFor(n), ctx->svHost, ws, ctx->stackSpill);
+    return 0;
+}
+// The two calls above with the rays' TIMES (rays8), on any scene: the walk is chosen by what the scene is.
+//   static                  the walks of the untimed calls, reading eight floats per ray (the time is ignored)
+//   plan.animFast           the production walks' ANIM variants (walk.traceClosest8 / traceAny8)
+//   any other animated one  the reference-order walks of wf_trace_*_host_t, on the caller's buffers
+// The records carry no visit counts on any of them.
+static bool Aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
+static int TraceDeviceTimed(wf_ctx *ctx, const char *fn, int n, const float *rays8, wf_hit_record *hits, int32_t *occluded) {
+    if (!ctx || !ctx->sceneLoaded) return fail(-1, "%s: no scene uploaded", fn);
+    if (n <= 0) return 0;
+    if (!rays8) return fail(-1, "%s: null rays8", fn);
+    if (!hits && !occluded) return fail(-1, "%s: null output buffer", fn);
+    if (!Aligned16(rays8)) return fail(-1, "%s: rays8 is not aligned to 16 bytes (a ray is read as two 16-byte loads)", fn);
+    useDevice(ctx);
+    const float *times = rays8 + 7;
+    if (ctx->svHost.haveAnimated && !ctx->plan.animFast) {
+        if (hits) LAUNCH("trace closest (device rays, timed)", k_trace_closest_timed, gridFor(n), ctx->svHost, n, rays8, 8, times, 8, hits, ctx->stackSpill, 0);
+        else LAUNCH("trace any (device rays, timed)", k_trace_any_timed, gridFor(n), ctx->svHost, n, rays8, 8, times, 8, occluded, ctx->stackSpill);
+    } else if (ctx->svHost.haveAnimated) {
+        if (hits) LAUNCHT("trace closest fast (device rays, timed)", ctx->walk.traceClosest8, ctx->walk.grid, ctx->svHost, ctx->fast, n, rays8, hits, ctx->spillArea());
+        else LAUNCHT("trace any fast (device rays, timed)", ctx->walk.traceAny8, ctx->walk.grid, ctx->svHost, ctx->fast, n, rays8, occluded, ctx->spillArea());
+    } else if (!ctx->plan.fastOk) {
+        if (hits) LAUNCH("trace closest (device rays, static)", k_trace_closest, gridFor(n), ctx->svHost, n, rays8, 8, hits, ctx->stackSpill, TRACE_NO_COUNTS);
+        else LAUNCH("trace any (device rays, static)", k_trace_any, gridFor(n), ctx->svHost, n, rays8, 8, occluded, (int32_t *)nullptr, (int32_t *)nullptr, ctx->stackSpill);
+    } else if (hits) {
+        LAUNCHT("trace closest fast (device rays, static)", ctx->walk.traceClosest8, ctx->walk.grid, ctx->svHost, ctx->fast, n, rays8, hits, ctx->spillArea());
+        if (!RetraceInline(ctx->plan.genMode)) LAUNCH("trace closest (near-tie re-trace)", k_trace_closest, gridFor(n), ctx->svHost, n, rays8, 8, hits, ctx->stackSpill, TRACE_ONLY_MARKED);
+    } else LAUNCHT("trace any fast (device rays, static)", ctx->walk.traceAny8, ctx->walk.grid, ctx->svHost, ctx->fast, n, rays8, occluded, ctx->spillArea());
+    return 0;
+}
+int wf_trace_closest_device_t(wf_ctx *ctx, int n, const float *rays8, wf_hit_record *out) {
+    if (ctx && n > 0 && !out) return fail(-1, "wf_trace_closest_device_t: null out");
+    return TraceDeviceTimed(ctx, "wf_trace_closest_device_t", n, rays8, out, nullptr);
+}
+int wf_trace_any_device_t(wf_ctx *ctx, int n, const float *rays8, int32_t *occluded) {
+    if (ctx && n > 0 && !occluded) return fail(-1, "wf_trace_any_device_t: null occluded");
+    return TraceDeviceTimed(ctx, "wf_trace_any_device_t", n, rays8, nullptr, occluded);
+}
+// room for n items in ctx->trScratch.  Growth waits for the launches that still read the old arrays; a call that fits allocates and
+// waits for nothing.
+static int GrowTrScratch(wf_ctx *ctx, size_t n) {
+    wf_ctx::TrScratch &t = ctx->trScratch;
+    if (!t.counters) {
+        HIPCHK(hipMalloc((void **)&t.counters, (size_t)CNT_COUNT * CNT_STRIDE * sizeof(int32_t)));
+        HIPCHK(hipMemsetAsync(t.counters, 0, (size_t)CNT_COUNT * CNT_STRIDE * sizeof(int32_t), ctx->stream));
+    }
+    if (n <= t.capacity) return 0;
+    const size_t cap = std::max(n, 2 * t.capacity);
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    for (void *p : {(void *)t.o, (void *)t.d, (void *)t.lambdaPdf, (void *)t.pathTime}) if (p) HIPCHK(hipFree(p));
+    t.o = t.d = t.lambdaPdf = nullptr;
+    t.pathTime = nullptr;
+    t.capacity = 0;
+    HIPCHK(hipMalloc((void **)&t.o, cap * sizeof(F4)));
+    HIPCHK(hipMalloc((void **)&t.d, cap * sizeof(F4)));
+    HIPCHK(hipMalloc((void **)&t.lambdaPdf, cap * sizeof(F4)));
+    HIPCHK(hipMalloc((void **)&t.pathTime, cap * sizeof(float)));
+    t.capacity = cap;
+    return 0;
+}
+// IntersectShadowTr on the caller's device items: TraceShadowTrHost's scratch WorkState, with the caller's arrays in place of the
+// uploaded copies and the rest packed on the device into the context's scratch
+int wf_trace_shadow_tr_device(wf_ctx *ctx, int n, const float *rays8, const int32_t *medium, const float *lambda, const float *Ld, const float *r_u,
+                              const float *r_l, float *out_L) {
+    const char *fn = "wf_trace_shadow_tr_device";
+    if (!ctx || !ctx->sceneLoaded) return fail(-1, "%s: no scene uploaded", fn);
+    if (!ctx->svHost.haveMedia) return fail(-1, "%s: the scene has no media", fn);
+    if (n <= 0) return 0;
+    if (!rays8 || !medium || !lambda || !Ld || !r_u || !r_l) return fail(-1, "%s: null input array", fn);
+    if (!out_L) return fail(-1, "%s: null out_L", fn);
+    if (!Aligned16(rays8)) return fail(-1, "%s: rays8 is not aligned to 16 bytes (a ray is read as two 16-byte loads)", fn);
+    if (!Aligned16(lambda) || !Aligned16(Ld) || !Aligned16(r_u) || !Aligned16(r_l) || !Aligned16(out_L))
+        return fail(-1, "%s: lambda / Ld / r_u / r_l / out_L are read and written four floats at a time: not aligned to 16 bytes", fn);
+    useDevice(ctx);
+    if (int e = GrowTrScratch(ctx, (size_t)n)) return e;
+    const wf_ctx::TrScratch &t = ctx->trScratch;
+    const bool timed = ctx->svHost.haveAnimated;   // (a static scene's items need no times: the untimed host-array call's kernel)
+    WorkState ws = ctx->ws;   // counters / stats of the context, every per-item array replaced below (the kernels only read the caller's inputs)
+    ws.sq.o = t.o; ws.sq.d = t.d; ws.lambdaPdf = t.lambdaPdf;
+    ws.sq.Ld = (F4 *)Ld; ws.sq.r_u = (F4 *)r_u; ws.sq.r_l = (F4 *)r_l; ws.sq.medium = (int32_t *)medium;
+    ws.lambda = (F4 *)lambda;
+    ws.L = (F4 *)out_L;
+    ws.counters = t.counters;
+    if (timed) ws.pathTime = t.pathTime;
+    LAUNCH("shadow Tr (device rays): pack items", k_pack_shadow_items, gridFor(n), n, rays8, t.o, t.d, t.lambdaPdf, timed ? t.pathTime : (float *)nullptr, (F4 *)out_L, t.counters);
+    return LaunchBoundaryTr(ctx, ws, n, timed, "shadow Tr (device rays, timed)", "shadow Tr (device rays)");
+}
+// IntersectOneRandom on the caller's device segments {p0, p1, time}: the kernel of the host-array calls, at the segments' times on a
+// scene with animated primitives
+int wf_trace_one_random_device(wf_ctx *ctx, int n, const float *segs7, const int32_t *material, wf_hit_record *out, float *reservoir_pdf) {
+    const char *fn = "wf_trace_one_random_device";
+    if (!ctx || !ctx->sceneLoaded) return fail(-1, "%s: no scene uploaded", fn);
+    if (n <= 0) return 0;
+    if (!segs7 || !material) return fail(-1, "%s: null input array", fn);
+    if (!out || !reservoir_pdf) return fail(-1, "%s: null output buffer", fn);
+    useDevice(ctx);
+    if (ctx->svHost.haveAnimated) LAUNCH("intersect one random (device segments, timed)", k_trace_one_random<true>, gridFor(n), ctx->svHost, n, segs7, 7, material, segs7 + 6, 7, out, reservoir_pdf, ctx->stackSpill);
+    else LAUNCH("intersect one random (device segments)", k_trace_one_random<false>, gridFor(n), ctx->svHost, n, segs7, 7, material, (const float *)nullptr, 0, out, reservoir_pdf, ctx->stackSpill);
     return 0;
 }
 int wf_device_alloc(wf_ctx *ctx, uint64_t nbytes, void **dptr) {
@@ -3812,7 +3985,7 @@ int wf_trace_closest_host(wf_ctx *ctx, int n, const float *o, const float *d, co
     int e;
     if ((e = tmp.upload(&dr, rays.data(), rays.size())) || (e = tmp.alloc(&dh, (size_t)n))) return e;
     if (count_visits || !ctx->plan.fastOk) {
-        LAUNCH("trace closest (host rays)", k_trace_closest, gridFor(n), ctx->svHost, n, dr, dh, ctx->stackSpill, 0);
+        LAUNCH("trace closest (host rays)", k_trace_closest, gridFor(n), ctx->svHost, n, dr, 7, dh, ctx->stackSpill, 0);
     } else if ((e = wf_trace_closest_device(ctx, n, dr, dh))) return e;
     HIPCHK(hipMemcpyAsync(out, dh, (size_t)n * sizeof(wf_hit_record), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -3846,12 +4019,8 @@ static int TraceShadowTrHost(wf_ctx *ctx, const char *fn, int n, const float *o,
         return e;
     HIPCHK(hipMemcpyAsync(cnt + CNT_SHADOW * CNT_STRIDE, &n, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     ws.counters = cnt;
-    if (time) {
-        if ((e = tmp.upload(&ws.pathTime, time, N))) return e;
-        LAUNCH("shadow Tr (host rays, timed)", k_shadow_tr<true>, gridFor(n), ctx->svHost, ws, ctx->stackSpill);
-    } else if (ctx->plan.fastOk && ctx->svHost.nInstances == 0) {
-        LAUNCHT("shadow Tr (host rays)", (ctx->svHost.haveAlpha || ctx->svHost.nQuadrics > 0 ? k_shadow_tr_fast<true> : k_shadow_tr_fast<false>), ctx->walk.grid, ctx->svHost, ws, ctx->fast, ctx->spillArea());
-    } else LAUNCH("shadow Tr (host rays)", k_shadow_tr<false>, gridFor(n), ctx->svHost, ws, ctx->stackSpill);
+    if (time && (e = tmp.upload(&ws.pathTime, time, N))) return e;
+    if ((e = LaunchBoundaryTr(ctx, ws, n, time != nullptr, "shadow Tr (host rays, timed)", "shadow Tr (host rays)"))) return e;
     HIPCHK(hipMemcpyAsync(out_L, ws.L, n * sizeof(F4), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return 0;
@@ -3884,8 +4053,8 @@ static int TraceOneRandomHost(wf_ctx *ctx, int n, const float *p0, const float *
     if ((e = tmp.upload(&ds, segs.data(), segs.size())) || (e = tmp.upload(&dm, material, (size_t)n)) || (e = tmp.alloc(&dh, (size_t)n)) || (e = tmp.alloc(&dp, (size_t)n))) return e;
     if (time) {
         if ((e = tmp.upload(&dt, time, (size_t)n))) return e;
-        LAUNCH("intersect one random (host segments, timed)", k_trace_one_random<true>, gridFor(n), ctx->svHost, n, ds, dm, (const float *)dt, dh, dp, ctx->stackSpill);
-    } else LAUNCH("intersect one random (host segments)", k_trace_one_random<false>, gridFor(n), ctx->svHost, n, ds, dm, (const float *)nullptr, dh, dp, ctx->stackSpill);
+        LAUNCH("intersect one random (host segments, timed)", k_trace_one_random<true>, gridFor(n), ctx->svHost, n, ds, 6, dm, (const float *)dt, 1, dh, dp, ctx->stackSpill);
+    } else LAUNCH("intersect one random (host segments)", k_trace_one_random<false>, gridFor(n), ctx->svHost, n, ds, 6, dm, (const float *)nullptr, 0, dh, dp, ctx->stackSpill);
     HIPCHK(hipMemcpyAsync(out, dh, (size_t)n * sizeof(wf_hit_record), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(reservoir_pdf, dp, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -3910,7 +4079,7 @@ int wf_trace_any_host(wf_ctx *ctx, int n, const float *o, const float *d, const 
     int e;
     if ((e = tmp.upload(&dr, rays.data(), rays.size())) || (e = tmp.alloc(&dres, (size_t)3 * n))) return e;
     if (nodes_visited || tris_tested || !ctx->plan.fastOk) {
-        LAUNCH("trace any (host rays)", k_trace_any, gridFor(n), ctx->svHost, n, dr, dres, dres + n, dres + 2 * (size_t)n, ctx->stackSpill);
+        LAUNCH("trace any (host rays)", k_trace_any, gridFor(n), ctx->svHost, n, dr, 7, dres, dres + n, dres + 2 * (size_t)n, ctx->stackSpill);
     } else if ((e = wf_trace_any_device(ctx, n, dr, dres))) return e;
     HIPCHK(hipMemcpyAsync(occluded, dres, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     if (nodes_visited) HIPCHK(hipMemcpyAsync(nodes_visited, dres + n, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -3933,8 +4102,8 @@ static int TraceTimed(wf_ctx *ctx, int n, const float *o, const float *d, const 
     const size_t resBytes = hits ? (size_t)n * sizeof(wf_hit_record) : (size_t)n * sizeof(int32_t);
     int e;
     if ((e = tmp.upload(&dr, rays.data(), rays.size())) || (e = tmp.alloc(&dres, resBytes))) return e;
-    if (hits) LAUNCH("trace closest (host rays with times)", k_trace_closest_timed, gridFor(n), ctx->svHost, n, dr, dr + (size_t)n * 7, (wf_hit_record *)dres, ctx->stackSpill);
-    else LAUNCH("trace any (host rays with times)", k_trace_any_timed, gridFor(n), ctx->svHost, n, dr, dr + (size_t)n * 7, (int32_t *)dres, ctx->stackSpill);
+    if (hits) LAUNCH("trace closest (host rays with times)", k_trace_closest_timed, gridFor(n), ctx->svHost, n, dr, 7, dr + (size_t)n * 7, 1, (wf_hit_record *)dres, ctx->stackSpill, 1);
+    else LAUNCH("trace any (host rays with times)", k_trace_any_timed, gridFor(n), ctx->svHost, n, dr, 7, dr + (size_t)n * 7, 1, (int32_t *)dres, ctx->stackSpill);
     HIPCHK(hipMemcpyAsync(hits ? (void *)hits : (void *)occluded, dres, resBytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return 0;

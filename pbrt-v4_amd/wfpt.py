@@ -39,6 +39,18 @@ class HitRecord(C.Structure):
                 ("nodes_visited", C.c_int32), ("tris_tested", C.c_int32), ("instance", C.c_int32)]
 
 
+# wf_hit_record as a numpy structured dtype (eight 32-bit words)
+HIT_DTYPE = np.dtype([("prim", "<i4"), ("t", "<f4"), ("b0", "<f4"), ("b1", "<f4"), ("b2", "<f4"),
+                      ("nodes_visited", "<i4"), ("tris_tested", "<i4"), ("instance", "<i4")])
+
+
+def hit_records(words):
+    """The int32 [n, 8] tensor of record words that the device-buffer calls return (Scene.trace_device, Scene.trace_one_random_device),
+    downloaded and viewed as wf_hit_record fields: a numpy structured array of n records (HIT_DTYPE)."""
+    a = np.ascontiguousarray(words.detach().cpu().numpy(), dtype=np.int32).reshape(-1, 8)
+    return a.view(HIT_DTYPE).reshape(-1).copy()
+
+
 class TraversalCounters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in (
         "closest_rays", "closest_nodes", "closest_tris", "closest_hits",
@@ -61,6 +73,7 @@ ABI_SYMBOLS = [
     "wf_counters_enable", "wf_counters_download", "wf_kernel_time_ms", "wf_debug_counters", "wf_debug_fastbvh_check", "wf_scene_check_instances", "wf_scene_plan_query", "wf_trace_closest_host_t", "wf_trace_any_host_t", "wf_ctx_query",
     "wf_trace_closest_device", "wf_trace_any_device", "wf_device_alloc", "wf_device_free", "wf_device_upload", "wf_device_download", "wf_trace_shadow_tr_host",
     "wf_trace_shadow_tr_host_t", "wf_trace_one_random_host_t",
+    "wf_trace_closest_device_t", "wf_trace_any_device_t", "wf_trace_shadow_tr_device", "wf_trace_one_random_device",
 ]
 HOST_SYMBOLS = [
     "wfh_init", "wfh_last_error", "wfh_scene_load", "wfh_scene_load_string", "wfh_scene_free", "wfh_scene_desc", "wfh_scene_info",
@@ -326,6 +339,83 @@ class Scene:
                                                   pdf.ctypes.data), "wf_trace_one_random_host_t")
         return np.frombuffer(out, dtype=np.dtype([("prim", "<i4"), ("t", "<f4"), ("b0", "<f4"), ("b1", "<f4"), ("b2", "<f4"),
                                                   ("nodes_visited", "<i4"), ("tris_tested", "<i4"), ("instance", "<i4")])).copy(), pdf
+
+    # ---- the device-buffer boundary (what a GPU-resident integrator binds): torch tensors in, torch tensors out, no host round trip ----
+    def _device_call(self, what, fn, argtypes, tensors, *args):
+        """Launch one device-buffer entry point on the context's stream (wf_stream), ordered after torch's current stream, and order
+        torch's current stream after it: tensors that torch ops produced just before the call, and ops that consume the results just
+        after it, need no synchronisation by the caller."""
+        import torch
+        _, hip = libs()
+        dev = tensors[0].device
+        for t in tensors:
+            if not (t.is_cuda and t.device == dev and t.is_contiguous()):
+                raise WfError("%s: the arguments are contiguous tensors on the context's device" % what)
+        fn.argtypes = argtypes
+        cur = torch.cuda.current_stream(dev)
+        ext = torch.cuda.ExternalStream(hip.wf_stream(self.ctx), device=dev)
+        ext.wait_stream(cur)
+        rc = fn(self.ctx, *args)
+        cur.wait_stream(ext)
+        _check(rc, what)
+
+    @staticmethod
+    def _as(t, dtype, cols, what):
+        import torch
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or (cols and (t.dim() != 2 or t.shape[1] != cols)) or (not cols and t.dim() != 1):
+            raise WfError("%s: expected a %s tensor of shape [n%s]" % (what, dtype, ", %d" % cols if cols else ""))
+        return t
+
+    def trace_device(self, rays8, any_hit=False, out=None):
+        """wf_trace_closest_device_t / wf_trace_any_device_t: rays8 = float32 [n, 8] rows {o, d, tMax, time} on the device.  Returns the
+        hit records as an int32 [n, 8] tensor of their words (hit_records() views a downloaded copy by field), or — any_hit — the
+        int32 [n] occlusion flags.  Any scene: a static one ignores the times.  out: a tensor to write into instead of a new one."""
+        import torch
+        _, hip = libs()
+        self._as(rays8, torch.float32, 8, "trace_device rays8")
+        n = rays8.shape[0]
+        if out is None:
+            out = torch.empty((n,) if any_hit else (n, 8), dtype=torch.int32, device=rays8.device)
+        else:
+            self._as(out, torch.int32, 0 if any_hit else 8, "trace_device out")
+            if out.shape[0] < n:
+                raise WfError("trace_device: out holds fewer than n results")
+        f = hip.wf_trace_any_device_t if any_hit else hip.wf_trace_closest_device_t
+        self._device_call(f.__name__, f, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p], [rays8, out], n, rays8.data_ptr(), out.data_ptr())
+        return out
+
+    def trace_shadow_tr_device(self, rays8, medium, lambda_, Ld, r_u, r_l):
+        """wf_trace_shadow_tr_device: IntersectShadowTr on device items of a scene with media — rays8 float32 [n, 8], medium int32 [n],
+        lambda_ / Ld / r_u / r_l float32 [n, 4].  Returns the float32 [n, 4] radiance each ray adds to its pixel."""
+        import torch
+        _, hip = libs()
+        self._as(rays8, torch.float32, 8, "trace_shadow_tr_device rays8")
+        self._as(medium, torch.int32, 0, "trace_shadow_tr_device medium")
+        for t in (lambda_, Ld, r_u, r_l):
+            self._as(t, torch.float32, 4, "trace_shadow_tr_device lambda_ / Ld / r_u / r_l")
+        n = rays8.shape[0]
+        if any(t.shape[0] != n for t in (medium, lambda_, Ld, r_u, r_l)):
+            raise WfError("trace_shadow_tr_device: the arrays hold different numbers of items")
+        out = torch.empty((n, 4), dtype=torch.float32, device=rays8.device)
+        ts = [rays8, medium, lambda_, Ld, r_u, r_l, out]
+        self._device_call("wf_trace_shadow_tr_device", hip.wf_trace_shadow_tr_device, [C.c_void_p, C.c_int] + [C.c_void_p] * 7, ts, n, *[t.data_ptr() for t in ts])
+        return out
+
+    def trace_one_random_device(self, segs7, material):
+        """wf_trace_one_random_device: IntersectOneRandom on device probe segments — segs7 float32 [n, 7] rows {p0, p1, time}, material
+        int32 [n].  Returns (hit records as an int32 [n, 8] tensor, reservoir pdfs as a float32 [n] tensor)."""
+        import torch
+        _, hip = libs()
+        self._as(segs7, torch.float32, 7, "trace_one_random_device segs7")
+        self._as(material, torch.int32, 0, "trace_one_random_device material")
+        n = segs7.shape[0]
+        if material.shape[0] != n:
+            raise WfError("trace_one_random_device: the arrays hold different numbers of items")
+        out = torch.empty((n, 8), dtype=torch.int32, device=segs7.device)
+        pdf = torch.empty((n,), dtype=torch.float32, device=segs7.device)
+        ts = [segs7, material, out, pdf]
+        self._device_call("wf_trace_one_random_device", hip.wf_trace_one_random_device, [C.c_void_p, C.c_int] + [C.c_void_p] * 4, ts, n, *[t.data_ptr() for t in ts])
+        return out, pdf
 
     def bounds(self):
         """WavefrontAggregate::Bounds() in rendering space: (pMin[3], pMax[3])"""
