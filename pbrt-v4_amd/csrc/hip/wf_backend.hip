@@ -12,20 +12,19 @@
 // per-lane HBM column) — no private-memory (scratch) arrays anywhere in the hot loop.
 // Queue pushes are wave-aggregated (wf_kernels.h: QueueAlloc): one atomic per wave per destination queue.
 //
+// The library's host-only part — the environment switches, the scene's plan, the builder of the production traversal layout and its
+// self-check — is plain C++ beside this unit: wf_plan.h, wf_plan.cpp, wf_fastbvh_build.cpp.  This unit keeps the context, the kernels,
+// PickWalkKernels, the uploads, the render pass and the boundary calls.
+//
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (the only fused operations are the explicit
 // fma calls of the restated arithmetic, as in the reference's CPU build).
 #include <hip/hip_runtime.h>
-#include <array>
-
 #include <climits>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <algorithm>
-#include <atomic>
 #include <map>
 #include <string>
-#include <thread>
 #include <type_traits>
 #include <utility>
 #include <vector>
@@ -39,19 +38,13 @@
 #include "../common/wf_kat.h"
 #pragma clang attribute pop
 #include "wf_traverse.h"
+#include "wf_plan.h"
 
 using namespace wf;
+using namespace wf::planning;
 
 // ---------------------------------------------------------------------------------------------
-// errors
-static thread_local char g_err[512] = "";
-static int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code ? code : -1;
-}
+// errors: fail() of wf_plan.h sets the text of wf_last_error
 #define HIPCHK(call)                                                                                        \
     do {                                                                                                    \
         hipError_t e_ = (call);                                                                             \
@@ -60,8 +53,6 @@ static int fail(int code, const char *fmt, ...) {
 
 // ---------------------------------------------------------------------------------------------
 constexpr int BLOCK = 256;
-constexpr int STACK_LDS = 24;   // LDS stack entries per lane: 24 x 4 B x 256 lanes = 24 KiB per workgroup
-constexpr int STACK_MAX = 64;   // nodesToVisit[64], cpu/aggregates.cpp:538
 constexpr int MAX_GRID = 256 * 8;  // 256 CUs x up to 8 resident 256-thread workgroups
 
 struct SpillArea { int *base; int rows; int *dbg; };   // the context's stackSpill rows + the debug words (kernel argument of the production traversal)
@@ -94,90 +85,6 @@ struct WalkKernels {
     TraceAnyFn traceAny8 = nullptr;
 };
 
-// ---------------------------------------------------------------------------------------------
-// The environment switches of context creation, scene upload and queue allocation, read in one place.  Each of those three calls takes a
-// fresh copy when it runs (the tests set switches between calls); the code they steer sees values, not the environment.
-struct Switches {
-    bool shadeTris = true;        // WF_SHADE_TRIS=0: the indexed vertex tables only (wf_scene.h ShadeTri)
-    bool gridCorners = true;      // WF_GRID_CORNERS=0: no corner-packed copies of the density grids
-    double gridCornersGB = 32.0;  // WF_GRID_CORNERS_GB: tables beyond this many gigabytes in all are left out
-    bool mediumLean = true;       // WF_MEDIUM_LEAN=0
-    bool leanShade = true;        // WF_LEAN_SHADE=0
-    bool leanPerType = true;      // WF_LEAN_PER_TYPE=0
-    int deferGeneral = -1;        // WF_DEFER_GENERAL=1 | 0 forces / forbids the two-class traversal; -1 (unset): by the scene's counts
-    bool noFast = false;          // WF_NO_FAST (set to anything): the reference-order walks only
-    bool animFast = true;         // WF_ANIM_FAST=0
-    bool pixelMajor = true;       // WF_PIXEL_MAJOR=0: items of a pass ordered sample by sample
-    bool noSampleTops = false;    // WF_NO_SAMPLE_TOPS (set to anything)
-    int trWavefront = -1;         // WF_TR_WAVEFRONT (wf_ctx::trWavefront)
-    int frameOverlap = 1;         // WF_FRAME_OVERLAP: 0 | 1 | 2 (wf_ctx::frameOverlap)
-    bool samplesShaded = true;    // WF_SAMPLES_SHADED=0
-    bool traceLaunch = false;     // WF_TRACE_LAUNCH (set to anything)
-    bool scratchPrime = true;     // WF_SCRATCH_PRIME=0
-    static Switches FromEnv() {
-        auto isSet = [](const char *name) { return getenv(name) != nullptr; };
-        auto on = [](const char *name) { const char *e = getenv(name); return !(e && atoi(e) == 0); };   // on unless set to 0
-        auto number = [](const char *name, int unset) { const char *e = getenv(name); return e ? atoi(e) : unset; };
-        Switches s;
-        s.shadeTris = on("WF_SHADE_TRIS");
-        s.gridCorners = on("WF_GRID_CORNERS");
-        if (const char *e = getenv("WF_GRID_CORNERS_GB")) s.gridCornersGB = atof(e);
-        s.mediumLean = on("WF_MEDIUM_LEAN");
-        s.leanShade = on("WF_LEAN_SHADE");
-        s.leanPerType = on("WF_LEAN_PER_TYPE");
-        if (isSet("WF_DEFER_GENERAL")) s.deferGeneral = number("WF_DEFER_GENERAL", 0) != 0;
-        s.noFast = isSet("WF_NO_FAST");
-        s.animFast = on("WF_ANIM_FAST");
-        s.pixelMajor = on("WF_PIXEL_MAJOR");
-        s.noSampleTops = isSet("WF_NO_SAMPLE_TOPS");
-        s.trWavefront = number("WF_TR_WAVEFRONT", -1);
-        s.frameOverlap = std::min(2, std::max(0, number("WF_FRAME_OVERLAP", 1)));
-        s.samplesShaded = on("WF_SAMPLES_SHADED");
-        s.traceLaunch = isSet("WF_TRACE_LAUNCH");
-        s.scratchPrime = on("WF_SCRATCH_PRIME");
-        return s;
-    }
-};
-
-// Everything decided about a scene: a pure function of the description and the switches (PlanScene), made before anything is uploaded.
-// wf_ctx::plan is the one copy; wf_scene_plan_query gives the same answers without a context.
-struct ScenePlan {
-    // what the description holds (the upload copies these into SceneView)
-    int64_t nBvhPrims = 0;       // entries of bvh_prims the trees index (wf_scene_check_instances)
-    int nInstances = 0;
-    int nestedAnimated = 0;      // records of `instances` that are nested placements (animated shapes inside instance definitions); such scenes keep the reference-order walks
-    bool haveAlpha = false, texNeedsFootprint = false, haveMix = false, haveSubsurface = false, haveQuadricAlpha = false, haveCurves = false, haveAnimated = false;
-    int matTypeMask = 0;
-    bool matPresent[WF_MAT_NTYPES] = {};
-    // the stage kernels' variants
-    bool mediumLean = false;     // every medium is homogeneous or a non-emissive uniform grid: k_medium_sample<true>
-    bool portalLights = false;   // the scene has a portal infinite light (k_handle_escaped<RARE>)
-    bool leanShade = false;      // the scene qualifies for the lean shade kernels (SceneLean)
-    // ... per MATERIAL TYPE since round 6: a type none of whose materials sits on a quadric / patch / curve keeps its lean shade kernel
-    // when such shapes appear elsewhere in the scene (their hits are items of other types' queues)
-    bool leanType[WF_MAT_NTYPES] = {};
-    bool rareLights = false;     // the scene has a light type only the VARIANT 2 material kernels sample (portal infinite lights)
-    // the walk kernels' variants (PickWalkKernels turns these into template instantiations)
-    int genMode = 0;             // general-primitive strength of the traversal kernels: 0 triangles only, 1 simple alpha, 2 anything but curves and alpha on quadrics, 3 anything (see GeneralPrims)
-    bool deferGeneral = false;   // TWO-CLASS TRAVERSAL (see WalkKernels)
-    int genTri = 0;
-    bool fastBuilt = false;      // BuildFastBVH gave a production layout (FastTrees): it is uploaded, in use or not
-    bool fastOk = false;         // ... and the scene's walks use it; false (leaf sizes > 16, nested placements, WF_NO_FAST, ...): the reference-order kernels only
-    bool animFast = false;       // the scene's AnimatedPrimitives are walked by the production kernels' ANIM variants (round 6; genMode <= 1 only)
-    int cursorChunk = 2;         // 64-ray batches a closest-hit wave takes per cursor fetch (chosen from the tree size)
-    int cursorChunkShadow = 2;   // ... an any-hit wave (round 6, with the descent scheduling, 10 M-triangle scene: closest-hit 27.7 ms at 1, 26.7 at 3, 27.0 at 4, 27.4 at 8, 29.9 at 16;
-                                 // any-hit 12.15 at 1, 12.16 at 3, 12.4 at 4, 13.0 at 8: profiles/r06_cursor_chunk_ab_sm16.txt)
-                                 // (-3 %), but on a 30 k-triangle scene one fetch per 64 rays is 83 atomics/us on one counter: the kernel's bound
-    int spillRows = 0;           // rows of wf_ctx::stackSpill behind the LDS stack entries, from the trees' depths
-};
-// The production traversal layout as BuildFastBVH leaves it on the host: what the upload copies once PlanScene has succeeded.
-struct FastTrees {
-    std::vector<QNode> nodes;
-    std::vector<LeafTri> tris;
-    std::vector<FastDef> defs;
-    std::vector<SubEntry> subs;
-    FastBVH header{};
-};
 
 struct wf_ctx {
     int device = 0;
@@ -1737,737 +1644,6 @@ static int checkReady(wf_ctx *ctx) {
     return 0;
 }
 
-// Reference LinearBVHNode arrays (depth-first: left child = i + 1, right child = offset) -> QNode (breadth-first
-// numbering per tree, quantised child boxes on the tree's own grid) + LeafTri (vertices in leaf order).  The top-level
-// tree comes first; every instance definition's tree follows with its own grid (FastDef).  See wf_traverse.h.
-struct FastDepths { int top = 0, def = 0, maxLeafInstances = 0; };   // levels of the four-wide trees (top level / deepest definition), most instances in one leaf
-// ---- the top-level tree of a two-level scene, rebuilt over RE-BRAIDED instances (round 6; SubEntry in wf_traverse.h) ----
-// One primitive of the builder: a top-level triangle / quadric (its LeafTri record of the scene's leaf order) or an instance entry.
-struct TopPrim {
-    float b[6];
-    int kind;   // 0: the LeafTri record `idx` of the reference's leaf order; 1: instance entry `idx` (FastBVH::subs)
-    int idx;
-};
-// Binned SAH (16 bins on the axis of the largest centroid extent, the reference's cost model: cpu/aggregates.cpp:270-370 — this tree is
-// the production walk's own, nothing is pinned to it), written as reference-layout nodes (depth first: left child = i + 1, right child =
-// offset) so that the four-wide collapse and the quantisation below take it like a reference tree.  A leaf holds at most four LeafTri
-// records; an instance entry is always a leaf of its own, referenced by the node itself (offset = INST_FIRST + entry: the walk pops
-// the entry without a LeafTri fetch).  `order` receives the primitives in leaf order.
-struct TopTreeBuilder {
-    std::vector<TopPrim> &P;
-    std::vector<wf_bvh_node> &out;
-    int leafBase;   // LeafTri index of P[0] in the new leaf order
-    static double Area(const float b[6]) {
-        const double dx = (double)b[3] - b[0], dy = (double)b[4] - b[1], dz = (double)b[5] - b[2];
-        return dx * dy + dy * dz + dz * dx;
-    }
-    int Build(int lo, int hi) {
-        const int me = (int)out.size();
-        out.emplace_back();
-        float bb[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY}, cb[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
-        bool anyEntry = false;
-        for (int i = lo; i < hi; ++i) {
-            const TopPrim &p = P[i];
-            anyEntry = anyEntry || p.kind == 1;
-            for (int a = 0; a < 3; ++a) {
-                bb[a] = std::min(bb[a], p.b[a]); bb[3 + a] = std::max(bb[3 + a], p.b[3 + a]);
-                const float c = 0.5f * p.b[a] + 0.5f * p.b[3 + a];
-                cb[a] = std::min(cb[a], c); cb[3 + a] = std::max(cb[3 + a], c);
-            }
-        }
-        const int count = hi - lo;
-        auto makeLeaf = [&]() {
-            wf_bvh_node &nd = out[me];
-            for (int a = 0; a < 3; ++a) { nd.bmin[a] = bb[a]; nd.bmax[a] = bb[3 + a]; }
-            nd.axis = 0; nd.pad = 0;
-            nd.nprims = (uint16_t)count;
-            nd.offset = (count == 1 && P[lo].kind == 1) ? INST_FIRST + P[lo].idx : leafBase + lo;
-            return me;
-        };
-        if (count == 1) return makeLeaf();
-        int axis = 0;
-        for (int a = 1; a < 3; ++a) if (cb[3 + a] - cb[a] > cb[3 + axis] - cb[axis]) axis = a;
-        int mid = (lo + hi) / 2;
-        const float cmin = cb[axis], cext = cb[3 + axis] - cb[axis];
-        bool split = false;
-        if (cext > 0) {
-            constexpr int NB = 16;
-            int cnt[NB] = {};
-            float bbox[NB][6];
-            for (int k = 0; k < NB; ++k) for (int a = 0; a < 3; ++a) { bbox[k][a] = INFINITY; bbox[k][3 + a] = -INFINITY; }
-            auto binOf = [&](const TopPrim &p) {
-                const float c = 0.5f * p.b[axis] + 0.5f * p.b[3 + axis];
-                int k = (int)(NB * ((c - cmin) / cext));
-                return k < 0 ? 0 : (k >= NB ? NB - 1 : k);
-            };
-            for (int i = lo; i < hi; ++i) {
-                const int k = binOf(P[i]);
-                ++cnt[k];
-                for (int a = 0; a < 3; ++a) { bbox[k][a] = std::min(bbox[k][a], P[i].b[a]); bbox[k][3 + a] = std::max(bbox[k][3 + a], P[i].b[3 + a]); }
-            }
-            double costR[NB] = {};
-            {
-                float r[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
-                int c = 0;
-                for (int k = NB - 1; k >= 1; --k) {
-                    if (cnt[k]) for (int a = 0; a < 3; ++a) { r[a] = std::min(r[a], bbox[k][a]); r[3 + a] = std::max(r[3 + a], bbox[k][3 + a]); }
-                    c += cnt[k];
-                    costR[k] = c ? c * Area(r) : 0;
-                }
-            }
-            float l[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
-            int c = 0, best = -1;
-            double bestCost = 0;
-            for (int k = 0; k + 1 < NB; ++k) {
-                if (cnt[k]) for (int a = 0; a < 3; ++a) { l[a] = std::min(l[a], bbox[k][a]); l[3 + a] = std::max(l[3 + a], bbox[k][3 + a]); }
-                c += cnt[k];
-                if (c == 0 || c == count) continue;
-                const double cost = c * Area(l) + costR[k + 1];
-                if (best < 0 || cost < bestCost) { best = k; bestCost = cost; }
-            }
-            if (best >= 0) {
-                const double area = Area(bb);
-                const double minCost = 0.5 + (area > 0 ? bestCost / area : 0);
-                if (count <= 4 && !anyEntry && !(minCost < count)) return makeLeaf();
-                TopPrim *m = std::partition(P.data() + lo, P.data() + hi, [&](const TopPrim &p) { return binOf(p) <= best; });
-                mid = (int)(m - P.data());
-                split = mid > lo && mid < hi;
-            }
-        }
-        if (!split) {
-            // coincident centroids: up to four records share a leaf, more (or any instance entry) are dealt half and half
-            if (count <= 4 && !anyEntry) return makeLeaf();
-            mid = (lo + hi) / 2;
-        }
-        Build(lo, mid);
-        const int right = Build(mid, hi);
-        wf_bvh_node &nd = out[me];
-        for (int a = 0; a < 3; ++a) { nd.bmin[a] = bb[a]; nd.bmax[a] = bb[3 + a]; }
-        nd.axis = (uint8_t)axis; nd.pad = 0;
-        nd.nprims = 0;
-        nd.offset = right;
-        return me;
-    }
-};
-
-// Nested placements (wf_abi.h wf_instance) exist in scenes with animated primitives only; without any, the two words that describe them are
-// never read (callers that predate them may have left them unset).
-static int NestedPlacements(const wf_scene_desc *d) {
-    int n = 0;
-    if (d->n_animated > 0)
-        for (int i = 0; i < d->n_instances; ++i) n += d->instances[i].outer_plus1 != 0;
-    return n;
-}
-// Entries of bvh_prims: what the leaves of the trees index.  Every triangle / quadric once, every top-level instance once, and every nested
-// placement ONCE PER DEFINITION (its records in `instances` repeat per use, its entry in the definition's leaves does not) — so this is
-// n_triangles + n_quadrics + n_instances only while no definition with a nested placement is used more than once.
-static int64_t BvhPrimCount(const wf_scene_desc *d) {
-    int64_t n = 0;
-    for (int i = 0; i < d->n_bvh_nodes; ++i)
-        if (d->bvh_nodes[i].nprims > 0) n = std::max(n, (int64_t)d->bvh_nodes[i].offset + d->bvh_nodes[i].nprims);
-    return n;
-}
-int wf_scene_check_instances(const wf_scene_desc *d, int64_t out[4]) {
-    if (!d) return fail(-1, "wf_scene_check_instances: null argument");
-    const int nGeom = d->n_triangles + d->n_quadrics, nI = d->n_instances, nD = d->n_instance_defs;
-    const int64_t nPrims = BvhPrimCount(d);
-    for (int i = 0; i < d->n_bvh_nodes; ++i) {
-        const wf_bvh_node &n = d->bvh_nodes[i];
-        if (n.offset < 0 || (n.nprims == 0 && n.offset >= d->n_bvh_nodes)) return fail(-1, "bvh_nodes[%d]: offset %d out of range", i, n.offset);
-    }
-    const int64_t nTop = nI > 0 ? d->n_top_prims : nPrims;
-    if (nTop < 0 || nTop > nPrims) return fail(-1, "n_top_prims %d outside bvh_prims (%lld entries)", d->n_top_prims, (long long)nPrims);
-    const bool anim = d->n_animated > 0;   // (the nested-placement words are read in such scenes only)
-    int64_t nNestedRecords = 0, nNestedEntries = 0;
-    // per definition: its range of bvh_prims, and how many nested placements its leaves name (entries nGeom + 0 .. nGeom + c - 1)
-    std::vector<int> defNested((size_t)std::max(nD, 0), 0);
-    for (int k = 0; k < nD; ++k) {
-        const wf_instance_def &def = d->instance_defs[k];
-        if (def.n_prims < 0 || def.first_prim < 0 || (int64_t)def.first_prim + def.n_prims > nPrims) return fail(-1, "instance_defs[%d]: bvh_prims range %d + %d outside the %lld entries", k, def.first_prim, def.n_prims, (long long)nPrims);
-        if (def.bvh_root >= d->n_bvh_nodes) return fail(-1, "instance_defs[%d]: bvh_root %d out of range", k, def.bvh_root);
-        int c = 0, hi = -1;
-        for (int j = def.first_prim; j < def.first_prim + def.n_prims; ++j) {
-            const int t = d->bvh_prims[j];
-            if (t < 0) return fail(-1, "bvh_prims[%d] = %d", j, t);
-            if (t >= nGeom) { ++c; hi = std::max(hi, t - nGeom); }
-        }
-        if (c > 0 && !anim) return fail(-1, "instance_defs[%d] names an instance in its leaves: only a scene with animated primitives can hold nested placements", k);
-        if (hi >= c) return fail(-1, "instance_defs[%d]: nested placement %d named, %d present", k, hi, c);
-        defNested[k] = c;
-        nNestedEntries += c;
-    }
-    for (int64_t j = 0; j < nTop; ++j) {
-        const int t = d->bvh_prims[j];
-        if (t < 0 || t >= nGeom + nI) return fail(-1, "bvh_prims[%lld] = %d outside the primitives and instances", (long long)j, t);
-        if (anim && t >= nGeom && d->instances[t - nGeom].outer_plus1 != 0) return fail(-1, "bvh_prims[%lld]: a nested placement's record among the top-level primitives", (long long)j);
-    }
-    for (int i = 0; i < nI; ++i) {
-        const wf_instance &in = d->instances[i];
-        if (in.def < 0 || in.def >= nD) return fail(-1, "instances[%d]: def %d out of range", i, in.def);
-        if (in.anim_plus1 < 0 || in.anim_plus1 > d->n_animated) return fail(-1, "instances[%d]: anim_plus1 %d out of range", i, in.anim_plus1);
-        if (!anim) continue;
-        if (in.outer_plus1 != 0) {
-            // a nested placement: animated, holds none itself, and belongs to the group of the use it names
-            ++nNestedRecords;
-            const int o = in.outer_plus1 - 1;
-            if (o < 0 || o >= nI || d->instances[o].outer_plus1 != 0) return fail(-1, "instances[%d]: outer_plus1 %d does not name a use of a definition", i, in.outer_plus1);
-            const int first = d->instances[o].nested_first, c = defNested[d->instances[o].def];
-            if (first <= 0 || i < first || i >= first + c) return fail(-1, "instances[%d]: not among the %d nested records of instances[%d] (nested_first %d)", i, c, o, first);
-            if (in.anim_plus1 == 0 || in.nested_first != 0 || defNested[in.def] != 0) return fail(-1, "instances[%d]: a nested placement is an animated primitive around a definition without nested placements", i);
-        } else {
-            const int c = defNested[in.def];
-            if (c == 0) continue;   // (nested_first is not read)
-            if (in.nested_first <= 0 || (int64_t)in.nested_first + c > nI) return fail(-1, "instances[%d]: nested_first %d + %d nested placements outside instances", i, in.nested_first, c);
-            for (int k = 0; k < c; ++k)
-                if (d->instances[in.nested_first + k].outer_plus1 != i + 1) return fail(-1, "instances[%d]: record %d is not nested placement %d of this use", i, in.nested_first + k, k);
-        }
-    }
-    if (out) { out[0] = nPrims; out[1] = nI - nNestedRecords; out[2] = nNestedRecords; out[3] = nNestedEntries; }
-    return 0;
-}
-static bool BuildFastBVH(const wf_scene_desc *d, std::vector<QNode> *nodes, std::vector<LeafTri> *tris, std::vector<FastDef> *defs, std::vector<SubEntry> *subs,
-                         FastBVH *out, FastDepths *depths) {
-    const wf_bvh_node *L = d->bvh_nodes;   // (rebound to the extended array once the re-braided top-level tree has been appended)
-    int n = d->n_bvh_nodes;
-    const int nRef = n;                    // nodes of the reference's trees
-    const int nGeom = d->n_triangles + d->n_quadrics;
-    const int nPrims = (int)BvhPrimCount(d);    // entries of bvh_prims: every triangle / quadric once, every instance once (no nested placements here: below)
-    if (n == 0 || (size_t)nPrims >= (size_t)INST_FIRST || d->n_instances >= INST_FIRST) return false;
-    for (int i = 0; i < n; ++i)
-        if (L[i].nprims > 16) return false;
-    // nested placements (animated shapes inside instance definitions, wf_abi.h wf_instance) have no entry form in the production tree: such
-    // scenes keep the reference-order walks, which take the third level from BVHIntersectClosestDef / BVHIntersectAnyDef<ANIM>
-    if (NestedPlacements(d) > 0) return false;
-    tris->resize((size_t)nPrims);
-    for (int k = 0; k < nPrims; ++k) {
-        int t = d->bvh_prims[k];
-        if (t >= nGeom) {
-            // an object instance: c.z == 4, entered by the INST kernel variants
-            LeafTri lt;
-            lt.a = F4{0, 0, 0, 0};
-            lt.b = F4{0, 0, 0, 0};
-            lt.c = F4{0, BitsToFloat((uint32_t)(t - nGeom)), 4.f, BitsToFloat(0u)};
-            (*tris)[k] = lt;
-            continue;
-        }
-        if (t >= d->n_triangles) {
-            // a sphere: c.z == 3, tested by the general-primitive kernel variants from wf_quadric (object space)
-            const wf_mesh &mesh = d->meshes[d->tri_mesh[t]];
-            uint32_t route = mesh.material >= 0 ? (uint32_t)d->materials[mesh.material].type | (mesh.first_light >= 0 ? 16u : 0u) : 32u;
-            LeafTri lt;
-            lt.a = F4{0, 0, 0, 0};
-            lt.b = F4{0, 0, 0, 0};
-            lt.c = F4{0, BitsToFloat((uint32_t)t), 3.f, BitsToFloat(route)};
-            (*tris)[k] = lt;
-            continue;
-        }
-        const int32_t *v = d->tri_indices + 3 * (size_t)t;
-        const float *p0 = d->P + 3 * (size_t)v[0], *p1 = d->P + 3 * (size_t)v[1], *p2 = d->P + 3 * (size_t)v[2];
-        LeafTri lt;
-        lt.a = F4{p0[0], p0[1], p0[2], p1[0]};
-        lt.b = F4{p1[1], p1[2], p2[0], p2[1]};
-        // IntersectTriangle's first test (shapes.cpp:172-173), hoisted to build time
-        V3 q0{p0[0], p0[1], p0[2]}, q1{p1[0], p1[1], p1[2]}, q2{p2[0], p2[1], p2[2]};
-        bool degenerate = LengthSquared(Cross(q2 - q0, q1 - q0)) == 0;
-        // routing code of EnqueueWorkAfterIntersection (intersect.h:48-156), so that the traversal kernel needs no
-        // per-hit mesh / material gathers: material type | emissive << 4 | interface << 5
-        const wf_mesh &mesh = d->meshes[d->tri_mesh[t]];
-        uint32_t route = 0;
-        if (mesh.material >= 0) route = (uint32_t)d->materials[mesh.material].type | (mesh.first_light >= 0 ? 16u : 0u);
-        else route = 32u;
-        // c.z: 0 = test, 1 = degenerate (never hit), 2 = test, then the mesh's alpha texture decides (ALPHA kernel variants)
-        lt.c = F4{p2[2], BitsToFloat((uint32_t)t), degenerate ? 1.f : mesh.alpha_tex >= 0 ? 2.f : 0.f, BitsToFloat(route)};
-        (*tris)[k] = lt;
-    }
-    nodes->clear();
-    bool gridOk = true;
-    std::vector<int> bfsIndex(n, -1);
-    // Subtree collapse: the production tree need not mirror the reference's leaves — a reference subtree holding at most
-    // `collapse` primitives (contiguous in bvh_prims: leaf order is depth-first) becomes ONE leaf here.  The walk then tests
-    // a superset of the triangles the reference tests, which changes no result (the exact triangle test decides, near-ties
-    // are re-traced in reference order) and removes the bottom levels of dependent node fetches: instance definitions are
-    // built with one primitive per leaf (maxPrimsInNode = 1, scene.cpp:1539).
-    int collapse = 1;
-    if (const char *e = getenv("WF_LEAF_COLLAPSE")) collapse = std::min(16, std::max(1, atoi(e)));
-    std::vector<int> subFirst(n), subCount(n);
-    auto fillSubRanges = [&](int from, int to) {   // nodes [from, to): a complete set of depth-first trees
-        for (int i = to - 1; i >= from; --i) {
-            if (L[i].nprims > 0) { subFirst[i] = L[i].offset; subCount[i] = L[i].nprims; }
-            else { subFirst[i] = subFirst[i + 1]; subCount[i] = subCount[i + 1] + subCount[L[i].offset]; }
-        }
-    };
-    fillSubRanges(0, n);
-    auto leafLike = [&](int i) { return L[i].nprims > 0 || subCount[i] <= collapse; };
-    // TIGHT INSTANCE BOXES (round 5).  The reference bounds an instance by the box of the eight transformed corners of its definition's
-    // box (TransformedPrimitive::Bounds) — for a rotated definition up to three times the surface area of the box of the transformed
-    // GEOMETRY — and the spec scene's rays entered eight instances each, three of four visits without a single primitive test.  The
-    // production walk only has to visit a superset of what can be hit, so its top-level tree carries, for an instance of an all-triangle
-    // definition, the box of the definition's transformed vertices (widened by 2^-18 of the magnitudes involved: the transform's rounding
-    // and the instance-space ray's), clipped to the reference's box, and interior boxes re-united bottom-up.  Topology, leaves and the
-    // reference-layout nodes (counting kernels, near-tie re-walk, CPU checker) are untouched: same hits, fewer entries.  WF_TIGHT_INSTANCES=0: off.
-    // WF_BRAID = most entries one instance is opened into (round 6, SubEntry in wf_traverse.h; 0: one entry per instance in the reference's
-    // own top-level tree, as in round 5)
-    int braidMax = 2;   // (measured on the spec scene, profiles/r06_rebraid_ab_sm16.txt: 2 is the optimum — DESIGN 4.1)
-    if (const char *e = getenv("WF_BRAID")) braidMax = std::min(256, std::max(0, atoi(e)));
-    const bool braid = braidMax > 0 && d->n_instances > 0 && d->n_top_bvh_nodes > 0 && L[0].nprims == 0;
-    std::vector<wf_bvh_node> tightTop;
-    if (!braid && d->n_instances > 0 && d->n_top_bvh_nodes > 0 && !(getenv("WF_TIGHT_INSTANCES") && atoi(getenv("WF_TIGHT_INSTANCES")) == 0)) {
-        const int nTop = d->n_top_bvh_nodes;
-        std::vector<std::vector<int32_t>> defVerts((size_t)d->n_instance_defs);
-        std::vector<char> defGeneral((size_t)d->n_instance_defs, 0);
-        for (int k = 0; k < d->n_instance_defs; ++k) {
-            const wf_instance_def &def = d->instance_defs[k];
-            std::vector<int32_t> &v = defVerts[k];
-            for (int j = def.first_prim; j < def.first_prim + def.n_prims; ++j) {
-                const int t = d->bvh_prims[j];
-                if (t >= d->n_triangles) { defGeneral[k] = 1; break; }
-                const int32_t *ix = d->tri_indices + 3 * (size_t)t;
-                v.push_back(ix[0]); v.push_back(ix[1]); v.push_back(ix[2]);
-            }
-            std::sort(v.begin(), v.end());
-            v.erase(std::unique(v.begin(), v.end()), v.end());
-            if (v.empty()) defGeneral[k] = 1;
-        }
-        std::vector<std::array<float, 6>> ib((size_t)d->n_instances);
-        std::vector<char> ibOk((size_t)d->n_instances, 0);
-        // (the pad also carries 2^-19 of the SCENE's magnitude, like the re-braided entries' boxes below: the instance-space ray the
-        //  reference decides hits with carries the rounding of the render-space origin and of the distance travelled — ADVICE r5)
-        double sceneMagT = 0;
-        for (int a = 0; a < 3; ++a) sceneMagT = std::max(sceneMagT, std::max(std::fabs((double)L[0].bmin[a]), std::fabs((double)L[0].bmax[a])) + ((double)L[0].bmax[a] - L[0].bmin[a]));
-        for (int i = 0; i < d->n_instances; ++i) {
-            const wf_instance &in = d->instances[i];
-            if (defGeneral[in.def] || in.anim_plus1 != 0) continue;   // (an AnimatedPrimitive keeps the reference's motion bounds)
-            const float(*m)[4] = in.render_from_instance.m;
-            if (m[3][0] != 0 || m[3][1] != 0 || m[3][2] != 0 || m[3][3] != 1) continue;
-            double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300}, mag = 0;
-            for (int32_t vi : defVerts[in.def]) {
-                const float *pp = d->P + 3 * (size_t)vi;
-                for (int a = 0; a < 3; ++a) {
-                    const double c = (double)m[a][0] * pp[0] + (double)m[a][1] * pp[1] + (double)m[a][2] * pp[2] + (double)m[a][3];
-                    lo[a] = std::min(lo[a], c); hi[a] = std::max(hi[a], c);
-                    mag = std::max(mag, std::fabs((double)m[a][0] * pp[0]) + std::fabs((double)m[a][1] * pp[1]) + std::fabs((double)m[a][2] * pp[2]) + std::fabs((double)m[a][3]));
-                }
-            }
-            bool finite = true;
-            for (int a = 0; a < 3; ++a) {
-                const double pad = 0x1p-18 * (mag + (hi[a] - lo[a])) + 0x1p-19 * sceneMagT + 1e-30;
-                ib[i][a] = (float)(lo[a] - pad); ib[i][3 + a] = (float)(hi[a] + pad);
-                if (!((double)ib[i][a] <= lo[a] - 0.5 * pad)) ib[i][a] = NextFloatDown(ib[i][a]);
-                if (!((double)ib[i][3 + a] >= hi[a] + 0.5 * pad)) ib[i][3 + a] = NextFloatUp(ib[i][3 + a]);
-                finite = finite && std::isfinite(ib[i][a]) && std::isfinite(ib[i][3 + a]);
-            }
-            ibOk[i] = finite;
-        }
-        tightTop.assign(L, L + nTop);
-        for (int i = nTop - 1; i >= 0; --i) {
-            wf_bvh_node &t = tightTop[i];
-            float b[6];
-            bool have = false, keep = false;
-            if (L[i].nprims > 0) {
-                for (int j = L[i].offset; j < L[i].offset + L[i].nprims && !keep; ++j) {
-                    const int pr = d->bvh_prims[j];
-                    if (pr < nGeom || !ibOk[pr - nGeom]) { keep = true; break; }   // a triangle / quadric or an instance left alone: the reference's box stands
-                    const std::array<float, 6> &q = ib[pr - nGeom];
-                    if (!have) { for (int a = 0; a < 6; ++a) b[a] = q[a]; have = true; }
-                    else for (int a = 0; a < 3; ++a) { b[a] = std::min(b[a], q[a]); b[3 + a] = std::max(b[3 + a], q[3 + a]); }
-                }
-            } else {
-                const wf_bvh_node &c0 = tightTop[i + 1], &c1 = tightTop[L[i].offset];
-                for (int a = 0; a < 3; ++a) { b[a] = std::min(c0.bmin[a], c1.bmin[a]); b[3 + a] = std::max(c0.bmax[a], c1.bmax[a]); }
-                have = true;
-            }
-            if (keep || !have) continue;
-            for (int a = 0; a < 3; ++a) {   // clipped to the reference's box (the geometry lies in both)
-                t.bmin[a] = std::max(L[i].bmin[a], b[a]);
-                t.bmax[a] = std::min(L[i].bmax[a], b[3 + a]);
-                if (!(t.bmin[a] <= t.bmax[a])) { t.bmin[a] = L[i].bmin[a]; t.bmax[a] = L[i].bmax[a]; }
-            }
-        }
-    }
-    // the boxes the production tree is packed from: the tightened ones for the top-level tree, the reference's everywhere else
-    auto BoxOf = [&](int i) -> const wf_bvh_node & { return (!tightTop.empty() && i < (int)tightTop.size()) ? tightTop[i] : L[i]; };
-    // one tree: linear nodes [root, ...) reachable from root; grid written to base / cell; returns the root's QNode index
-    int lastTreeDepth = 0;   // levels of the four-wide tree buildTree made last (a single leaf-like root: 1)
-    std::vector<std::array<int, 4>> qKids;   // per QNode: the reference-layout nodes its four children stand for (-1: empty slot)
-    auto buildTree = [&](int root, float baseOut[3], float cellOut[3]) -> int {
-        lastTreeDepth = 1;
-        // Quantisation grid over the root bounds.  A plane is the REAL number base + q * cell (the device never forms
-        // it as a float: WalkSetRay folds base and cell into per-ray fma constants).  Every stored plane lies at least
-        // `margin` outside the float box it bounds; margin = 2^-20 of the largest coordinate magnitude, which covers the
-        // rounding of (base - o) and of the box's own float planes in the reference's slab test.
-        double margin[3];
-        for (int a = 0; a < 3; ++a) {
-            double lo = L[root].bmin[a], hi = L[root].bmax[a];
-            double ext = hi - lo;
-            margin[a] = 0x1p-20 * (std::max(std::fabs(lo), std::fabs(hi)) + ext) + 1e-37;
-            float base = (float)(lo - 2 * margin[a]);
-            while ((double)base > lo - 2 * margin[a]) base = NextFloatDown(base);
-            float cell = (float)((hi + 2 * margin[a] - (double)base) / 65535.0);
-            if (!(cell > 0)) cell = 1e-30f;
-            cell = NextFloatUp(NextFloatUp(cell));
-            baseOut[a] = base;
-            cellOut[a] = cell;
-        }
-        auto plane = [&](int q, int a) { return (double)baseOut[a] + (double)q * (double)cellOut[a]; };
-        auto qlo = [&](float v, int a) {
-            double target = (double)v - margin[a];
-            int q = (int)std::floor((target - baseOut[a]) / cellOut[a]);
-            q = std::min(std::max(q, 0), 65535);
-            while (q > 0 && plane(q, a) > target) --q;
-            if (plane(q, a) > target) gridOk = false;
-            return (uint32_t)q;
-        };
-        auto qhi = [&](float v, int a) {
-            double target = (double)v + margin[a];
-            int q = (int)std::ceil((target - baseOut[a]) / cellOut[a]);
-            q = std::min(std::max(q, 0), 65535);
-            while (q < 65535 && plane(q, a) < target) ++q;
-            if (plane(q, a) < target) gridOk = false;
-            return (uint32_t)q;
-        };
-        auto leafRef = [&](int i) { return (int)~(((unsigned)subFirst[i] << 4) | (unsigned)(subCount[i] - 1)); };
-        const int qBase = (int)nodes->size();
-        auto emptyBox = [&](uint32_t q[12], int slot) { for (int a = 0; a < 3; ++a) q[slot * 3 + a] = 0x0000ffffu; };
-        auto area = [&](int i) {
-            const wf_bvh_node &bx = BoxOf(i);
-            double dx = (double)bx.bmax[0] - bx.bmin[0], dy = (double)bx.bmax[1] - bx.bmin[1], dz = (double)bx.bmax[2] - bx.bmin[2];
-            return dx * dy + dy * dz + dz * dx;
-        };
-        auto packBox = [&](const wf_bvh_node &b, uint32_t q[12], int slot) {
-            for (int a = 0; a < 3; ++a) q[slot * 3 + a] = qlo(b.bmin[a], a) | (qhi(b.bmax[a], a) << 16);
-        };
-        if (leafLike(root)) {
-            QNode qn{};
-            packBox(BoxOf(root), qn.q, 0);
-            qn.child[0] = leafRef(root);
-            for (int c = 1; c < 4; ++c) { emptyBox(qn.q, c); qn.child[c] = NODE_NONE; }
-            nodes->push_back(qn);
-            qKids.push_back({root, -1, -1, -1});
-            return qBase;
-        }
-        // four-way collapse of the binary tree: a node's children are its two binary children, the largest interior ones
-        // replaced by their own children until there are four (or only leaves are left); breadth-first numbering
-        std::vector<int> order;
-        order.push_back(root);
-        bfsIndex[root] = qBase;
-        std::vector<std::array<int, 4>> kidsOf;
-        std::vector<int> level{1};
-        for (size_t h = 0; h < order.size(); ++h) {
-            int i = order[h];
-            lastTreeDepth = std::max(lastTreeDepth, level[h] + 1);   // + 1: the leaves hanging off this node
-            std::array<int, 4> kids = {i + 1, (int)L[i].offset, -1, -1};
-            int nk = 2;
-            while (nk < 4) {
-                int best = -1;
-                for (int k = 0; k < nk; ++k)
-                    if (!leafLike(kids[k]) && (best < 0 || area(kids[k]) > area(kids[best]))) best = k;
-                if (best < 0) break;
-                int c = kids[best];
-                kids[best] = c + 1;
-                kids[nk++] = L[c].offset;
-            }
-            for (int k = 0; k < nk; ++k)
-                if (!leafLike(kids[k])) { bfsIndex[kids[k]] = qBase + (int)order.size(); order.push_back(kids[k]); level.push_back(level[h] + 1); }
-            kidsOf.push_back(kids);
-        }
-        nodes->resize((size_t)qBase + order.size());
-        qKids.insert(qKids.end(), kidsOf.begin(), kidsOf.end());
-        for (size_t h = 0; h < order.size(); ++h) {
-            QNode qn{};
-            for (int c = 0; c < 4; ++c) {
-                int k = kidsOf[h][c];
-                if (k < 0) { emptyBox(qn.q, c); qn.child[c] = NODE_NONE; continue; }
-                packBox(BoxOf(k), qn.q, c);
-                qn.child[c] = !leafLike(k) ? bfsIndex[k] : leafRef(k);
-            }
-            (*nodes)[(size_t)qBase + h] = qn;
-        }
-        return qBase;
-    };
-    // the definitions' trees first (the entries of the re-braided top-level tree name their nodes), then the top-level tree; afterwards
-    // the top-level tree is moved to the FRONT of the array: the walk starts at node 0
-    for (int i = 0; i < nRef; ++i)
-        if (leafLike(i)) {
-            int ni = 0;
-            for (int k = 0; k < subCount[i]; ++k) ni += d->bvh_prims[subFirst[i] + k] >= nGeom;
-            depths->maxLeafInstances = std::max(depths->maxLeafInstances, ni);
-        }
-    defs->clear();
-    for (int k = 0; k < d->n_instance_defs; ++k) {
-        FastDef fd{};
-        fd.root = d->instance_defs[k].bvh_root >= 0 ? buildTree(d->instance_defs[k].bvh_root, fd.base, fd.cell) : -1;
-        if (d->instance_defs[k].bvh_root >= 0) depths->def = std::max(depths->def, lastTreeDepth);
-        defs->push_back(fd);
-    }
-    const int nDefQ = (int)nodes->size();
-    subs->clear();
-    std::vector<wf_bvh_node> Lx;
-    int topRoot = 0;
-    if (braid) {
-        // ---- partial re-braiding: the entries of every instance
-        const int nTop = d->n_top_bvh_nodes;
-        std::vector<char> defGeneral((size_t)d->n_instance_defs, 0);
-        for (int k = 0; k < d->n_instance_defs; ++k) {
-            const wf_instance_def &def = d->instance_defs[k];
-            if (def.bvh_root < 0 || def.n_prims <= 0) { defGeneral[k] = 1; continue; }
-            for (int j = def.first_prim; j < def.first_prim + def.n_prims; ++j)
-                if (d->bvh_prims[j] >= d->n_triangles) { defGeneral[k] = 1; break; }
-        }
-        double sceneMag = 0;
-        for (int a = 0; a < 3; ++a) sceneMag = std::max(sceneMag, std::max(std::fabs((double)L[0].bmin[a]), std::fabs((double)L[0].bmax[a])) + ((double)L[0].bmax[a] - L[0].bmin[a]));
-        struct Entry { int bnode; float b[6]; };
-        std::vector<std::vector<Entry>> entriesOf((size_t)d->n_instances);
-        // the box of a definition's subtree under an instance's transformation: its triangles' transformed vertices (double arithmetic),
-        // widened by 2^-18 of the magnitudes involved plus 2^-19 of the SCENE's (the instance-space ray the reference decides hits with
-        // carries the rounding of the render-space ray's origin and of the distance travelled — ADVICE r5: not of the instance's own
-        // coordinates only)
-        auto subtreeBox = [&](const wf_instance &in, int bnode, float b[6]) {
-            const float(*m)[4] = in.render_from_instance.m;
-            double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300}, mag = 0;
-            for (int j = subFirst[bnode]; j < subFirst[bnode] + subCount[bnode]; ++j) {
-                const LeafTri &lt = (*tris)[j];
-                const float v[3][3] = {{lt.a.x, lt.a.y, lt.a.z}, {lt.a.w, lt.b.x, lt.b.y}, {lt.b.z, lt.b.w, lt.c.x}};
-                for (int q = 0; q < 3; ++q)
-                    for (int a = 0; a < 3; ++a) {
-                        const double t0 = (double)m[a][0] * v[q][0], t1 = (double)m[a][1] * v[q][1], t2 = (double)m[a][2] * v[q][2];
-                        const double c = t0 + t1 + t2 + (double)m[a][3];
-                        lo[a] = std::min(lo[a], c); hi[a] = std::max(hi[a], c);
-                        mag = std::max(mag, std::fabs(t0) + std::fabs(t1) + std::fabs(t2) + std::fabs((double)m[a][3]));
-                    }
-            }
-            bool finite = true;
-            for (int a = 0; a < 3; ++a) {
-                const double pad = 0x1p-18 * (mag + (hi[a] - lo[a])) + 0x1p-19 * sceneMag + 1e-30;
-                b[a] = (float)(lo[a] - pad); b[3 + a] = (float)(hi[a] + pad);
-                if (!((double)b[a] <= lo[a] - 0.5 * pad)) b[a] = NextFloatDown(b[a]);
-                if (!((double)b[3 + a] >= hi[a] + 0.5 * pad)) b[3 + a] = NextFloatUp(b[3 + a]);
-                finite = finite && std::isfinite(b[a]) && std::isfinite(b[3 + a]);
-            }
-            return finite;
-        };
-        auto refOf = [&](int bnode) { return leafLike(bnode) ? (int)~(((unsigned)subFirst[bnode] << 4) | (unsigned)(subCount[bnode] - 1)) : bfsIndex[bnode]; };
-        double minFrac = 1.0 / 64;   // an entry smaller than this fraction of the instance's own box is not opened further
-        if (const char *e = getenv("WF_BRAID_MIN_FRAC")) minFrac = atof(e);
-        auto openInstance = [&](int i) {
-            const wf_instance &in = d->instances[i];
-            std::vector<Entry> &es = entriesOf[i];
-            if (in.def < 0 || in.def >= d->n_instance_defs || defGeneral[in.def]) return;
-            if (in.anim_plus1 != 0) return;   // an AnimatedPrimitive: one entry under the reference's motion bounds (its leaf's box)
-            const float(*m)[4] = in.render_from_instance.m;
-            if (m[3][0] != 0 || m[3][1] != 0 || m[3][2] != 0 || m[3][3] != 1) return;
-            Entry root;
-            root.bnode = d->instance_defs[in.def].bvh_root;
-            if (!subtreeBox(in, root.bnode, root.b)) return;
-            const double rootArea = TopTreeBuilder::Area(root.b);
-            es.push_back(root);
-            while ((int)es.size() < braidMax) {
-                int best = -1;
-                double bestArea = minFrac * rootArea;
-                for (int k = 0; k < (int)es.size(); ++k) {
-                    if (leafLike(es[k].bnode)) continue;
-                    const double ar = TopTreeBuilder::Area(es[k].b);
-                    if (ar > bestArea) { best = k; bestArea = ar; }
-                }
-                if (best < 0) break;
-                const std::array<int, 4> &kids = qKids[(size_t)bfsIndex[es[best].bnode]];
-                int nk = 0;
-                for (int c = 0; c < 4; ++c) nk += kids[c] >= 0;
-                if ((int)es.size() - 1 + nk > braidMax) break;
-                Entry ch[4];
-                bool ok = true;
-                int w = 0;
-                for (int c = 0; c < 4 && ok; ++c)
-                    if (kids[c] >= 0) { ch[w].bnode = kids[c]; ok = subtreeBox(in, kids[c], ch[w].b); ++w; }
-                if (!ok) break;
-                es[best] = ch[0];
-                for (int c = 1; c < w; ++c) es.push_back(ch[c]);
-            }
-        };
-        {
-            unsigned nThreads = std::max(1u, std::min(32u, std::thread::hardware_concurrency()));
-            if ((unsigned)d->n_instances < 4 * nThreads) nThreads = 1;
-            std::atomic<int> next{0};
-            auto worker = [&]() { for (int i; (i = next.fetch_add(1)) < d->n_instances;) openInstance(i); };
-            std::vector<std::thread> pool;
-            for (unsigned t = 1; t < nThreads; ++t) pool.emplace_back(worker);
-            worker();
-            for (std::thread &t : pool) t.join();
-        }
-        // ---- the primitives of the new top-level tree, in the reference's leaf order (deterministic)
-        std::vector<TopPrim> P;
-        P.reserve((size_t)subCount[0] + (size_t)d->n_instances * 4);
-        for (int i = 0; i < nTop; ++i) {
-            if (L[i].nprims == 0) continue;
-            for (int j = L[i].offset; j < L[i].offset + L[i].nprims; ++j) {
-                const int t = d->bvh_prims[j];
-                TopPrim p;
-                if (t < d->n_triangles) {
-                    const LeafTri &lt = (*tris)[j];
-                    const float v[3][3] = {{lt.a.x, lt.a.y, lt.a.z}, {lt.a.w, lt.b.x, lt.b.y}, {lt.b.z, lt.b.w, lt.c.x}};
-                    for (int a = 0; a < 3; ++a) { p.b[a] = std::min(v[0][a], std::min(v[1][a], v[2][a])); p.b[3 + a] = std::max(v[0][a], std::max(v[1][a], v[2][a])); }
-                    p.kind = 0; p.idx = j;
-                    P.push_back(p);
-                } else if (t < nGeom) {   // a quadric / patch / curve: the reference's leaf box bounds it
-                    for (int a = 0; a < 3; ++a) { p.b[a] = L[i].bmin[a]; p.b[3 + a] = L[i].bmax[a]; }
-                    p.kind = 0; p.idx = j;
-                    P.push_back(p);
-                } else {
-                    const int ii = t - nGeom;
-                    const wf_instance &in = d->instances[ii];
-                    if (entriesOf[ii].empty()) {   // left alone (general primitives inside, a projective matrix): one entry at the definition's root, the reference's leaf box
-                        for (int a = 0; a < 3; ++a) { p.b[a] = L[i].bmin[a]; p.b[3 + a] = L[i].bmax[a]; }
-                        p.kind = 1; p.idx = (int)subs->size();
-                        const int root = (in.def >= 0 && in.def < d->n_instance_defs) ? d->instance_defs[in.def].bvh_root : -1;
-                        subs->push_back(SubEntry{ii, root >= 0 ? refOf(root) : NODE_NONE});
-                        P.push_back(p);
-                    } else
-                        for (const Entry &e : entriesOf[ii]) {
-                            for (int a = 0; a < 6; ++a) p.b[a] = e.b[a];
-                            p.kind = 1; p.idx = (int)subs->size();
-                            subs->push_back(SubEntry{ii, refOf(e.bnode)});
-                            P.push_back(p);
-                        }
-                }
-            }
-        }
-        if (P.empty() || subs->size() >= (size_t)INST_FIRST) return false;
-        // ---- the tree, as reference-layout nodes behind the reference's own
-        const int leafBase = (int)tris->size();
-        Lx.assign(L, L + n);
-        TopTreeBuilder tb{P, Lx, leafBase};
-        // (node indices of the builder are positions in Lx: it appends)
-        topRoot = tb.Build(0, (int)P.size());
-        tris->resize((size_t)leafBase + P.size());
-        for (size_t k = 0; k < P.size(); ++k) {
-            if (P[k].kind == 0) (*tris)[(size_t)leafBase + k] = (*tris)[(size_t)P[k].idx];
-            else (*tris)[(size_t)leafBase + k].c = F4{0, BitsToFloat((uint32_t)P[k].idx), 4.f, BitsToFloat(0u)};   // (never read: an entry is a leaf of its own)
-        }
-        if (tris->size() >= (size_t)INST_FIRST) return false;
-        L = Lx.data();
-        n = (int)Lx.size();
-        subFirst.resize(n); subCount.resize(n); bfsIndex.resize(n, -1);
-        fillSubRanges(nRef, n);
-        if (const char *e = getenv("WF_BRAID_VERBOSE")) if (atoi(e)) fprintf(stderr, "[wf] re-braided top-level tree: %d instances -> %zu entries, %zu primitives, %d nodes\n", d->n_instances, subs->size(), P.size(), n - nRef);
-    } else {
-        // one entry per instance, at its definition's root
-        for (int i = 0; i < d->n_instances; ++i) {
-            const int def = d->instances[i].def;
-            const int root = (def >= 0 && def < d->n_instance_defs) ? d->instance_defs[def].bvh_root : -1;
-            subs->push_back(SubEntry{i, root < 0 ? NODE_NONE : (leafLike(root) ? (int)~(((unsigned)subFirst[root] << 4) | (unsigned)(subCount[root] - 1)) : bfsIndex[root])});
-        }
-    }
-    buildTree(topRoot, out->base, out->cell);
-    depths->top = lastTreeDepth;
-    {
-        // the top-level tree to the front
-        const int nAll = (int)nodes->size(), nTopQ = nAll - nDefQ;
-        auto remap = [&](int r) { return r < 0 ? r : (r >= nDefQ ? r - nDefQ : r + nTopQ); };
-        std::vector<QNode> moved((size_t)nAll);
-        for (int i = 0; i < nAll; ++i) {
-            QNode qn = (*nodes)[(size_t)i];
-            for (int c = 0; c < 4; ++c) qn.child[c] = remap(qn.child[c]);
-            moved[(size_t)remap(i)] = qn;
-        }
-        nodes->swap(moved);
-        for (FastDef &fd : *defs) fd.root = fd.root < 0 ? 0 : remap(fd.root);
-        for (SubEntry &se : *subs) se.node = remap(se.node);
-    }
-    {
-        double ext = 0;
-        for (int a = 0; a < 3; ++a) ext = std::max(ext, std::max(std::fabs((double)L[0].bmin[a]), std::fabs((double)L[0].bmax[a])) + ((double)L[0].bmax[a] - L[0].bmin[a]));
-        const double band = d->n_quadrics > 0 ? 0x1p-10 : 0x1p-20;   // (FastBVH::tieRel: quadric hits are accepted by interval bounds)
-        out->absBand = (float)(band * ext);
-        out->tieRel = (float)(1 + band);
-        out->absBandTri = (float)(0x1p-20 * ext);   // the band of a triangle / triangle pair (wf_traverse.h, WalkAccept<PAIRS>)
-        out->tieRelTri = (float)(1 + 0x1p-20);
-        out->firstGeneral = d->n_quadrics > 0 ? d->n_triangles : INT_MAX;
-    }
-    if (!gridOk) return false;
-    out->nNodes = (int)nodes->size();
-    return true;
-}
-
-// ---- host-only self-check of the production layout (wf_debug_fastbvh_check; CPU suite) ----------------------------------------------
-// Walks the QNode / LeafTri / SubEntry arrays on the HOST with random rays, in double arithmetic and without pruning by distance, and
-// checks that every triangle a ray really hits (brute force over the top-level triangles and every (instance, triangle) pair, in the
-// instance's space) is among the triangles the walk tests — the one property the production tree owes (wf_traverse.h: "a superset of
-// visited nodes, the exact triangle test decides").  No device is needed: BuildFastBVH is host code.
-namespace {
-struct CheckWalk {
-    const std::vector<QNode> &nodes;
-    const std::vector<LeafTri> &tris;
-    const std::vector<FastDef> &defs;
-    const std::vector<SubEntry> &subs;
-    const wf_scene_desc *d;
-    const FastBVH &top;
-    std::vector<std::pair<int, int>> tested;   // (triangle id, instance or -1)
-    long long nodesVisited = 0, entries = 0;
-    static bool Slab(const float base[3], const float cell[3], const uint32_t q[3], const double o[3], const double dir[3]) {
-        double t0 = 0, t1 = 1e300;
-        for (int a = 0; a < 3; ++a) {
-            const double lo = (double)base[a] + (double)(q[a] & 0xffffu) * (double)cell[a], hi = (double)base[a] + (double)(q[a] >> 16) * (double)cell[a];
-            if (lo > hi) return false;   // an empty slot
-            if (dir[a] == 0) { if (o[a] < lo || o[a] > hi) return false; continue; }
-            double tn = (lo - o[a]) / dir[a], tf = (hi - o[a]) / dir[a];
-            if (tn > tf) std::swap(tn, tf);
-            t0 = std::max(t0, tn); t1 = std::min(t1, tf);
-        }
-        return t0 <= t1;
-    }
-    void Leaf(int ref, int inst, const double o[3], const double dir[3]) {
-        const unsigned r = ~(unsigned)ref;
-        const int first = (int)(r >> 4), count = (int)(r & 15u) + 1;
-        if (first >= INST_FIRST) { Enter(first - INST_FIRST, o, dir); return; }
-        for (int i = 0; i < count; ++i) {
-            const LeafTri &lt = tris[(size_t)first + i];
-            if (lt.c.z == 4.f) { if (inst < 0) Enter((int)FloatToBits(lt.c.y), o, dir); continue; }
-            tested.push_back({(int)FloatToBits(lt.c.y), inst});
-        }
-    }
-    void Tree(int ref, const float base[3], const float cell[3], int inst, const double o[3], const double dir[3]) {
-        std::vector<int> st{ref};
-        while (!st.empty()) {
-            const int r = st.back();
-            st.pop_back();
-            if (r == NODE_NONE) continue;
-            if (r < 0) { Leaf(r, inst, o, dir); continue; }
-            ++nodesVisited;
-            const QNode &qn = nodes[(size_t)r];
-            for (int c = 0; c < 4; ++c)
-                if (qn.child[c] != NODE_NONE && Slab(base, cell, qn.q + 3 * c, o, dir)) st.push_back(qn.child[c]);
-        }
-    }
-    void Enter(int entry, const double oW[3], const double dW[3]) {
-        ++entries;
-        const SubEntry se = subs[(size_t)entry];
-        if (se.node == NODE_NONE) return;
-        const wf_instance &in = d->instances[se.inst];
-        const float(*mi)[4] = in.render_from_instance.mInv;
-        double o[3], dir[3];
-        for (int a = 0; a < 3; ++a) {
-            o[a] = (double)mi[a][0] * oW[0] + (double)mi[a][1] * oW[1] + (double)mi[a][2] * oW[2] + (double)mi[a][3];
-            dir[a] = (double)mi[a][0] * dW[0] + (double)mi[a][1] * dW[1] + (double)mi[a][2] * dW[2];
-        }
-        const FastDef &fd = defs[(size_t)in.def];
-        Tree(se.node, fd.base, fd.cell, se.inst, o, dir);
-    }
-};
-// does the ray hit the triangle well inside (barycentrics > eps, in front of the origin)?  Moeller-Trumbore in double arithmetic
-bool HitsClearly(const double o[3], const double dir[3], const float *p0, const float *p1, const float *p2) {
-    double e1[3], e2[3], pv[3], tv[3], qv[3];
-    for (int a = 0; a < 3; ++a) { e1[a] = (double)p1[a] - p0[a]; e2[a] = (double)p2[a] - p0[a]; tv[a] = o[a] - p0[a]; }
-    pv[0] = dir[1] * e2[2] - dir[2] * e2[1]; pv[1] = dir[2] * e2[0] - dir[0] * e2[2]; pv[2] = dir[0] * e2[1] - dir[1] * e2[0];
-    const double det = e1[0] * pv[0] + e1[1] * pv[1] + e1[2] * pv[2];
-    const double scale = std::sqrt((e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]) * (e2[0] * e2[0] + e2[1] * e2[1] + e2[2] * e2[2]) * (dir[0] * dir[0] + dir[1] * dir[1] + dir[2] * dir[2]));
-    if (!(std::fabs(det) > 1e-9 * scale)) return false;
-    const double u = (tv[0] * pv[0] + tv[1] * pv[1] + tv[2] * pv[2]) / det;
-    qv[0] = tv[1] * e1[2] - tv[2] * e1[1]; qv[1] = tv[2] * e1[0] - tv[0] * e1[2]; qv[2] = tv[0] * e1[1] - tv[1] * e1[0];
-    const double v = (dir[0] * qv[0] + dir[1] * qv[1] + dir[2] * qv[2]) / det;
-    const double t = (e2[0] * qv[0] + e2[1] * qv[1] + e2[2] * qv[2]) / det;
-    return u > 1e-4 && v > 1e-4 && u + v < 1 - 1e-4 && t > 1e-6;
-}
-}  // namespace
-
 // ---- the scene's walk kernels (WalkKernels) --------------------------------------------------------------------------------------
 // the walk kernel templates as types, so that one function maps run-time values onto their instantiations
 struct ClosestWalk { using Fn = ClosestWalkFn; template <int G, bool I> static Fn of() { return k_closest_fast<G, I>; } };
@@ -2532,287 +1708,9 @@ static int PickWalkKernels(wf_ctx *ctx) {
     return 0;
 }
 
-// ---- the scene's plan (ScenePlan) ------------------------------------------------------------------------------------------------
-// PlanScene, in its order: check the description, classify it, build the production trees, decide the walks.  Host code without a HIP
-// call: wf_scene_upload runs it before it allocates anything (a rejected description leaves the context as it was), and
-// wf_scene_plan_query runs it without a context.
-
-// Every array the five interpolants of measured material i point to must lie inside table_data (the kernels index them unchecked)
-static int CheckMeasuredTable(const wf_scene_desc *d, int i) {
-    const int64_t nT = d->n_table_floats, h = d->materials[i].measured_table;
-    if (h < 0 || h + WF_MEASURED_HEADER_WORDS > nT) return fail(-1, "measured material %d: header outside table_data", i);
-    auto word = [&](int64_t k) { int32_t v; memcpy(&v, &d->table_data[h + k], 4); return (int64_t)v; };
-    static const int nParams[5] = {0, 0, 2, 2, 3};
-    static const bool hasCdf[5] = {false, false, true, true, false};
-    for (int k = 0; k < 5; ++k) {
-        const int64_t b = 16 + 16 * k, sx = word(b), sy = word(b + 1);
-        if (sx < 2 || sy < 2 || sx > (1 << 20) || sy > (1 << 20)) return fail(-1, "measured material %d: interpolant %d has size %lld x %lld", i, k, (long long)sx, (long long)sy);
-        int64_t slices = 1;
-        for (int p = nParams[k] - 1; p >= 0; --p) {
-            const int64_t ps = word(b + 2 + p), st = word(b + 5 + p), po = word(b + 8 + p);
-            if (ps < 1 || ps > (1 << 20) || po < 0 || po + ps > nT || st != (ps > 1 ? slices : 0)) return fail(-1, "measured material %d: interpolant %d, parameter %d invalid", i, k, p);
-            slices *= ps;
-            if (slices > nT) return fail(-1, "measured material %d: interpolant %d larger than table_data", i, k);
-        }
-        const int64_t dataOff = word(b + 11), margOff = word(b + 12), condOff = word(b + 13);
-        if (dataOff < 0 || dataOff + slices * sx * sy > nT) return fail(-1, "measured material %d: interpolant %d data outside table_data", i, k);
-        if (hasCdf[k] && (margOff < 0 || margOff + slices * sy > nT || condOff < 0 || condOff + slices * sx * sy > nT))
-            return fail(-1, "measured material %d: interpolant %d cdf outside table_data", i, k);
-    }
-    return 0;
-}
-// Step 1: everything that rejects a description, before anything indexes through its tables (on the host or on the device).
-// counts: wf_scene_check_instances' out.
-static int CheckAbi(const wf_scene_desc *d) {
-    return d->abi_version == WF_ABI_VERSION ? 0 : fail(-1, "ABI version mismatch: desc %d, library %d", d->abi_version, WF_ABI_VERSION);
-}
-static int CheckScene(const wf_scene_desc *d, int64_t counts[4]) {
-    if (int e = CheckAbi(d)) return e;
-    if (d->sampler.type == WF_SAMPLER_SOBOL && (!d->sobol_matrices || !d->vdc_sobol || !d->vdc_sobol_inv)) return fail(-1, "the Sobol sampler needs the sobol_matrices / vdc_sobol tables");
-    if (int e = wf_scene_check_instances(d, counts)) return e;
-    if (d->sampler.type < WF_SAMPLER_ZSOBOL || d->sampler.type > WF_SAMPLER_SOBOL) return fail(-1, "unknown sampler type %d", d->sampler.type);
-    if (d->sampler.type == WF_SAMPLER_HALTON && (!d->halton_primes || (d->sampler.randomize == WF_RAND_PERMUTE_DIGITS && (!d->halton_perm_offsets || !d->halton_perms))))
-        return fail(-1, "Halton sampler without its prime / digit-permutation tables");
-    for (int i = 0; i < d->n_materials; ++i) {
-        const wf_material &m = d->materials[i];
-        if (m.type == WF_MAT_MIX) {
-            if (m.mix[0] < 0 || m.mix[0] >= d->n_materials || m.mix[1] < 0 || m.mix[1] >= d->n_materials || m.mix[0] >= i || m.mix[1] >= i)
-                return fail(-1, "mix material %d must name two earlier materials", i);
-            continue;
-        }
-        if (m.type < 0 || m.type >= WF_MAT_NTYPES) return fail(-1, "material %d has unknown type %d", i, m.type);
-        if (m.type == WF_MAT_SUBSURFACE && (m.sss_table < 0 || (size_t)m.sss_table + BSSRDF_TABLE_FLOATS > (size_t)d->n_table_floats))
-            return fail(-1, "subsurface material %d: BSSRDF table outside table_data", i);
-        if (m.type == WF_MAT_MEASURED)
-            if (int e = CheckMeasuredTable(d, i)) return e;
-    }
-    if (d->film.type == WF_FILM_SPECTRAL && (d->film.n_buckets < 1 || d->film.n_buckets > 4096 || !(d->film.lambda_max > d->film.lambda_min)))
-        return fail(-1, "spectral film: bad bucket count / wavelength range");
-    return 0;
-}
-// Step 2: what the scene holds, and which variants of the stage and walk kernels that asks for.
-static void ClassifyScene(const wf_scene_desc *d, const Switches &sw, ScenePlan *plan) {
-    plan->nInstances = d->n_instances;
-    plan->nestedAnimated = NestedPlacements(d);
-    plan->haveAnimated = d->n_animated > 0;
-    for (int i = 0; i < d->n_meshes; ++i)
-        if (d->meshes[i].alpha_tex >= 0) plan->haveAlpha = true;
-    for (int i = 0; i < d->n_textures; ++i)
-        if (d->textures[i].type >= WF_TEX_FLOAT_IMAGE) plan->texNeedsFootprint = true;
-    for (int i = 0; i < d->n_materials; ++i)
-        if (d->materials[i].displacement >= 0 || d->materials[i].normalmap >= 0) plan->texNeedsFootprint = true;
-    // the lean delta-tracking kernel (k_medium_sample<true>): no procedural cloud, NanoVDB, RGB grid or emissive grid in the scene (WF_MEDIUM_LEAN=0: off)
-    plan->mediumLean = d->n_media > 0 && sw.mediumLean;
-    for (int m = 0; m < d->n_media; ++m)
-        if (!(d->media[m].type == WF_MEDIUM_HOMOGENEOUS || (d->media[m].type == WF_MEDIUM_GRID && !d->media[m].is_emissive))) plan->mediumLean = false;
-    // the lean shade kernels (wf_scene.h "LEAN DEVICE VARIANTS"): no quadrics / patches / curves, every texture a constant, an image map or a
-    // bilerp (WF_LEAN_SHADE=0 turns them off)
-    bool simpleTextures = true;
-    for (int i = 0; i < d->n_textures && simpleTextures; ++i)
-        if (!wf::IsSimpleFloatTexture(d->textures[i].type) && !wf::IsSimpleSpectrumTexture(d->textures[i].type)) simpleTextures = false;
-    plan->leanShade = d->n_quadrics == 0 && d->n_animated == 0 && sw.leanShade && simpleTextures;
-    {
-        // the material types met on shapes that are not triangles (through MixMaterials, whose hits join the queue of the chosen material's type)
-        bool onGeneral[WF_MAT_NTYPES] = {};
-        std::vector<int> todo;
-        for (int i = 0; i < d->n_quadrics; ++i) {
-            const int m = d->meshes[d->quadrics[i].mesh].material;
-            if (m >= 0 && m < d->n_materials) todo.push_back(m);
-        }
-        std::vector<char> seen((size_t)std::max(d->n_materials, 1), 0);
-        while (!todo.empty()) {
-            const int m = todo.back();
-            todo.pop_back();
-            if (m < 0 || m >= d->n_materials || seen[m]) continue;
-            seen[m] = 1;
-            const int t = d->materials[m].type;
-            if (t == WF_MAT_MIX) { todo.push_back(d->materials[m].mix[0]); todo.push_back(d->materials[m].mix[1]); }
-            else if (t >= 0 && t < WF_MAT_NTYPES) onGeneral[t] = true;
-        }
-        const bool wanted = sw.leanShade && sw.leanPerType;
-        for (int t = 0; t < WF_MAT_NTYPES; ++t) plan->leanType[t] = plan->leanShade || (wanted && simpleTextures && d->n_animated == 0 && !onGeneral[t]);
-    }
-    // ... and, since round 5, emitters that are not triangles (sphere / disk / cylinder / patch / curve lights: an out-of-line sampler of
-    // 214 VGPRs) and emitters with an alpha texture (the texture-graph evaluator): LightSampleLi<RARE>, AreaLightL<ALPHA> (wf_lights.h)
-    for (int i = 0; i < d->n_lights; ++i) {
-        const wf_light &l = d->lights[i];
-        if (l.type == WF_LIGHT_PORTAL_INFINITE) plan->rareLights = plan->portalLights = true;
-        if (l.type == WF_LIGHT_DIFFUSE_AREA && (l.tri >= d->n_triangles || l.alpha_tex_plus1 != 0)) plan->rareLights = true;
-    }
-    for (int i = 0; i < d->n_quadrics; ++i) {
-        if (d->meshes[d->quadrics[i].mesh].alpha_tex >= 0) plan->haveQuadricAlpha = true;
-        if (d->quadrics[i].type == WF_QUADRIC_CURVE) plan->haveCurves = true;
-    }
-    for (int i = 0; i < d->n_materials; ++i) {
-        const int t = d->materials[i].type;
-        if (t == WF_MAT_MIX) { plan->haveMix = true; continue; }
-        plan->matPresent[t] = true;
-        plan->matTypeMask |= 1 << t;
-        if (t == WF_MAT_SUBSURFACE) plan->haveSubsurface = true;
-    }
-    if (d->n_quadrics > 0) plan->genMode = (plan->haveCurves || plan->haveQuadricAlpha) ? 3 : 2;
-    int alphaGen = 0;   // what the TRIANGLES of the scene ask of the walk: 0 nothing, 1 simple alpha cut-outs, 2 texture-graph alpha
-    for (int i = 0; i < d->n_meshes && alphaGen < 2; ++i)
-        if (d->meshes[i].alpha_tex >= 0) {
-            const int tt = d->textures[d->meshes[i].alpha_tex].type;
-            // the inline test looks an image map up without a footprint (MIPFilterFloatZeroP): uv-mapped, not EWA-filtered
-            const wf_texture &at = d->textures[d->meshes[i].alpha_tex];
-            const bool lean = tt == WF_TEX_FLOAT_CONSTANT || (at.mapping == WF_TEXMAP_UV && (tt != WF_TEX_FLOAT_IMAGE || d->tex_images[at.i0].filter != WF_MIP_EWA));
-            alphaGen = std::max(alphaGen, ((tt == WF_TEX_FLOAT_CONSTANT || tt == WF_TEX_FLOAT_IMAGE || tt == WF_TEX_FLOAT_BILERP) && lean) ? 1 : 2);
-        }
-    plan->genMode = std::max(plan->genMode, alphaGen);
-    // TWO-CLASS TRAVERSAL: the scene's quadrics / patches / curves are few beside its triangles, and the triangles themselves need no
-    // more than the simple alpha test — the triangle kernels walk first, the general kernels only the rays handed over
-    // (WF_DEFER_GENERAL=1 | 0 forces / forbids it for any scene with such shapes)
-    plan->genTri = std::min(alphaGen, 1);
-    if (d->n_quadrics > 0 && alphaGen <= 1 && plan->genMode >= 2) {
-        const bool few = (int64_t)d->n_quadrics * 16 <= (int64_t)d->n_triangles;
-        plan->deferGeneral = sw.deferGeneral >= 0 ? sw.deferGeneral != 0 : few;
-    }
-}
-// levels of the reference's binary tree under `root`
-static int RefTreeDepth(const wf_scene_desc *d, int root) {
-    int best = 0;
-    if (root < 0 || root >= d->n_bvh_nodes) return best;
-    std::vector<std::pair<int, int>> st{{root, 1}};
-    while (!st.empty()) {
-        auto [i, dep] = st.back();
-        st.pop_back();
-        best = std::max(best, dep);
-        if (d->bvh_nodes[i].nprims == 0) { st.push_back({i + 1, dep + 1}); st.push_back({d->bvh_nodes[i].offset, dep + 1}); }
-    }
-    return best;
-}
-static int PlanScene(const wf_scene_desc *d, const Switches &sw, ScenePlan *plan, FastTrees *trees) {
-    *plan = ScenePlan{};
-    int64_t counts[4];
-    if (int e = CheckScene(d, counts)) return e;
-    plan->nBvhPrims = counts[0];
-    ClassifyScene(d, sw, plan);
-    // Step 3: the production trees, and the traversal stacks behind them.
-    FastDepths fdep;
-    plan->fastBuilt = BuildFastBVH(d, &trees->nodes, &trees->tris, &trees->defs, &trees->subs, &trees->header, &fdep);
-    {
-        // LDS entries per lane + rows of `stackSpill` behind them, sized from the trees' ACTUAL depths: the
-        // reference-order walk pushes one sibling per level of the reference's binary trees (top level, then an instance
-        // definition's on top); the four-wide production walk up to three per level of ITS collapsed trees (BuildFastBVH records
-        // their depths: the greedy largest-area collapse does not halve the depth of an unbalanced tree), one entry per instance
-        // of a leaf, and the two instance markers.  A push past the rows is dropped and flagged (LdsStackT, wf_sync).
-        int depthTop = d->n_bvh_nodes > 0 ? RefTreeDepth(d, 0) : 0, depthDef = 0;
-        for (int k = 0; k < d->n_instance_defs; ++k) depthDef = std::max(depthDef, RefTreeDepth(d, d->instance_defs[k].bvh_root));
-        // (a definition with nested placements carries a third level: a moving entity's tree on top of the definition's)
-        const int needRef = depthTop + (plan->nestedAnimated > 0 ? 2 : 1) * depthDef + 4;
-        const int needFast = 3 * fdep.top + fdep.maxLeafInstances + 3 * fdep.def + 6;
-        plan->spillRows = std::max(std::max(needRef - std::min(STACK_LDS, TSTACK), needFast - TSTACK), STACK_MAX - std::min(STACK_LDS, TSTACK));
-        if (plan->spillRows > 2048) return fail(-1, "BVH too deep for the traversal stacks (depth %d + %d)", depthTop, depthDef);
-    }
-    // Step 4: which walks use the trees.
-    plan->fastOk = plan->fastBuilt && !sw.noFast;
-    if (plan->fastBuilt) {
-        // rays of a scene whose trees do not fit the caches walk long enough for one cursor fetch per 64 rays (measured: -3 % on
-        // the 10 M-triangle scene); a cache-resident scene traces so fast that the cursor's atomics would bound it (see cursorChunk)
-        const bool big = trees->nodes.size() * sizeof(QNode) + trees->tris.size() * sizeof(LeafTri) > ((size_t)256 << 20);
-        plan->cursorChunk = big ? 3 : 2;
-        plan->cursorChunkShadow = big ? 1 : 2;
-    }
-    // AnimatedPrimitive: the production walks' ANIM variants (triangles + simple alpha cut-outs, two-level: an animated shape entity is an
-    // instance) interpolate the transformation per ray since round 6; scenes that also hold quadrics / curves / texture-graph alpha keep the
-    // reference-order walks (WF_ANIM_FAST=0: every animated scene does)
-    plan->animFast = d->n_animated > 0 && plan->fastOk && plan->genMode <= 1 && plan->nInstances > 0 && sw.animFast;
-    if (d->n_animated > 0 && !plan->animFast) plan->fastOk = false;
-    return 0;
-}
-// The answers of wf_ctx_query / wf_scene_plan_query that the plan alone gives; false: not one of its keys.
-static bool PlanValue(const ScenePlan &plan, const char *key, int64_t *value) {
-    const std::string k = key;
-    if (k == "fast_ok") *value = plan.fastOk;
-    else if (k == "gen_mode") *value = plan.genMode;
-    else if (k == "gen_tri") *value = plan.genTri;
-    else if (k == "defer_general") *value = plan.deferGeneral;
-    else if (k == "anim_fast") *value = plan.animFast;
-    else if (k == "lean_shade") *value = plan.leanShade;
-    else if (k == "rare_lights") *value = plan.rareLights;
-    else if (k == "medium_lean") *value = plan.mediumLean;   // k_medium_sample<true> / k_tr_segment<true>: every medium is homogeneous or a non-emissive uniform grid
-    else if (k.rfind("lean_type_", 0) == 0 && atoi(key + 10) >= 0 && atoi(key + 10) < WF_MAT_NTYPES) *value = plan.leanType[atoi(key + 10)];
-    else if (k == "instances") *value = plan.nInstances;
-    else if (k == "nested_animated") *value = plan.nestedAnimated;
-    else return false;
-    return true;
-}
-
 extern "C" {
 
-const char *wf_last_error(void) { return g_err; }
 int wf_abi_version(void) { return WF_ABI_VERSION; }
-
-int wf_debug_fastbvh_check(const wf_scene_desc *d, int n_rays, uint64_t seed, int64_t out[8]) {
-    if (!d || !out || n_rays < 0) return fail(-1, "wf_debug_fastbvh_check: bad arguments");
-    FastTrees trees;
-    FastDepths fdep;
-    for (int k = 0; k < 8; ++k) out[k] = 0;
-    if (!BuildFastBVH(d, &trees.nodes, &trees.tris, &trees.defs, &trees.subs, &trees.header, &fdep)) return fail(-1, "wf_debug_fastbvh_check: the scene has no production layout");
-    out[0] = (int64_t)trees.nodes.size(); out[1] = (int64_t)trees.tris.size(); out[2] = (int64_t)trees.subs.size(); out[3] = fdep.top;
-    // structure: every child reference names a node / a leaf run / an entry inside the arrays
-    for (size_t i = 0; i < trees.nodes.size(); ++i)
-        for (int c = 0; c < 4; ++c) {
-            const int r = trees.nodes[i].child[c];
-            if (r == NODE_NONE) continue;
-            if (r >= 0) { if ((size_t)r >= trees.nodes.size()) return fail(-1, "wf_debug_fastbvh_check: node %zu child %d out of range", i, c); continue; }
-            const unsigned u = ~(unsigned)r;
-            const size_t first = u >> 4, count = (u & 15u) + 1;
-            if (first >= (size_t)INST_FIRST ? first - INST_FIRST >= trees.subs.size() : first + count > trees.tris.size()) return fail(-1, "wf_debug_fastbvh_check: node %zu child %d: leaf run out of range", i, c);
-        }
-    for (const SubEntry &se : trees.subs)
-        if (se.inst < 0 || se.inst >= d->n_instances || (se.node >= 0 && (size_t)se.node >= trees.nodes.size())) return fail(-1, "wf_debug_fastbvh_check: entry out of range");
-    // coverage with random rays through the scene's box
-    uint64_t rng = seed * 0x9E3779B97F4A7C15ull + 0xD1B54A32D192ED03ull;
-    auto rnd = [&]() { rng ^= rng << 13; rng ^= rng >> 7; rng ^= rng << 17; return (double)(rng >> 11) * (1.0 / 9007199254740992.0); };
-    const wf_bvh_node &root = d->bvh_nodes[0];
-    CheckWalk cw{trees.nodes, trees.tris, trees.defs, trees.subs, d, trees.header, {}};
-    const int nGeom = d->n_triangles + d->n_quadrics;
-    for (int r = 0; r < n_rays; ++r) {
-        double o[3], dir[3], tgt[3];
-        for (int a = 0; a < 3; ++a) {
-            const double lo = root.bmin[a], hi = root.bmax[a], ext = hi - lo;
-            o[a] = lo - 0.1 * ext + 1.2 * ext * rnd();
-            tgt[a] = lo + ext * rnd();
-            dir[a] = tgt[a] - o[a];
-        }
-        cw.tested.clear();
-        cw.Tree(0, trees.header.base, trees.header.cell, -1, o, dir);
-        std::sort(cw.tested.begin(), cw.tested.end());
-        out[6] += (int64_t)cw.tested.size();
-        auto check = [&](int tri, int inst, const double oo[3], const double dd[3]) {
-            const int32_t *v = d->tri_indices + 3 * (size_t)tri;
-            if (!HitsClearly(oo, dd, d->P + 3 * (size_t)v[0], d->P + 3 * (size_t)v[1], d->P + 3 * (size_t)v[2])) return;
-            ++out[4];
-            if (!std::binary_search(cw.tested.begin(), cw.tested.end(), std::make_pair(tri, inst))) ++out[5];
-        };
-        // the top-level primitives and, per instance, its definition's
-        int nTopPrims = 0;
-        for (int i = 0; i < (d->n_top_bvh_nodes > 0 ? d->n_top_bvh_nodes : d->n_bvh_nodes); ++i) nTopPrims += d->bvh_nodes[i].nprims;
-        for (int j = 0; j < nTopPrims; ++j) {
-            const int t = d->bvh_prims[j];
-            if (t < d->n_triangles) { check(t, -1, o, dir); continue; }
-            if (t < nGeom) continue;
-            const int ii = t - nGeom;
-            const wf_instance &in = d->instances[ii];
-            if (in.def < 0 || in.def >= d->n_instance_defs) continue;
-            const float(*mi)[4] = in.render_from_instance.mInv;
-            double oI[3], dI[3];
-            for (int a = 0; a < 3; ++a) {
-                oI[a] = (double)mi[a][0] * o[0] + (double)mi[a][1] * o[1] + (double)mi[a][2] * o[2] + (double)mi[a][3];
-                dI[a] = (double)mi[a][0] * dir[0] + (double)mi[a][1] * dir[1] + (double)mi[a][2] * dir[2];
-            }
-            const wf_instance_def &def = d->instance_defs[in.def];
-            for (int k = def.first_prim; k < def.first_prim + def.n_prims; ++k)
-                if (d->bvh_prims[k] < d->n_triangles) check(d->bvh_prims[k], ii, oI, dI);
-        }
-    }
-    out[7] = cw.entries;
-    out[3] = cw.nodesVisited;
-    return 0;
-}
 
 // The stream's scratch (private segment) grows whenever a kernel needs more per lane than any kernel before it; on about a third of the
 // pool's boxes every such growth costs the launch that triggers it 20-30 ms (round 4: the first frame of a process took 200 ms instead of
@@ -3151,15 +2049,6 @@ int wf_scene_upload(wf_ctx *ctx, const wf_scene_desc *d) {
     ctx->sceneLoaded = true;
     return 0;
 }
-int wf_scene_plan_query(const wf_scene_desc *d, const char *key, int64_t *value) {
-    if (!d || !key || !value) return fail(-1, "wf_scene_plan_query: null argument");
-    ScenePlan plan;
-    FastTrees trees;
-    if (int e = PlanScene(d, Switches::FromEnv(), &plan, &trees)) return e;
-    if (!PlanValue(plan, key, value)) return fail(-1, "wf_scene_plan_query: unknown key '%s'", key);
-    return 0;
-}
-
 int wf_ctx_query(wf_ctx *ctx, const char *key, int64_t *value) {
     if (!ctx || !key || !value) return fail(-1, "wf_ctx_query: null argument");
     if (!ctx->sceneLoaded) return fail(-1, "no scene uploaded");

@@ -1,0 +1,123 @@
+// wf_plan.h — what libwfhip.so decides about a scene on the host before anything is uploaded: the environment switches (Switches), the
+// scene's plan (ScenePlan, PlanScene) and the production traversal layout as it is built (FastTrees, BuildFastBVH).  The definitions are
+// plain C++ without a HIP call — wf_plan.cpp, wf_fastbvh_build.cpp — so they are compiled once, not per pass of the kernel unit, and a
+// stand-alone host program can link them (tools/plan_dump.cpp).  wf_backend.hip includes this for what the upload and the queries use.
+#pragma once
+#include <cstdint>
+#include <cstdlib>
+#include <algorithm>
+#include <vector>
+#include "../common/wf_fastbvh.h"
+
+// (hidden: these names are shared by the library's units, not exported from it)
+namespace wf { namespace planning __attribute__((visibility("hidden"))) {
+
+// the message of wf_last_error (per thread); returns `code`, or -1 for 0
+int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+
+// The environment switches of context creation, scene upload (tree building included) and queue allocation, read in one place.  Each of those three calls takes a
+// fresh copy when it runs (the tests set switches between calls); the code they steer sees values, not the environment.
+struct Switches {
+    bool shadeTris = true;        // WF_SHADE_TRIS=0: the indexed vertex tables only (wf_scene.h ShadeTri)
+    bool gridCorners = true;      // WF_GRID_CORNERS=0: no corner-packed copies of the density grids
+    double gridCornersGB = 32.0;  // WF_GRID_CORNERS_GB: tables beyond this many gigabytes in all are left out
+    bool mediumLean = true;       // WF_MEDIUM_LEAN=0
+    bool leanShade = true;        // WF_LEAN_SHADE=0
+    bool leanPerType = true;      // WF_LEAN_PER_TYPE=0
+    int deferGeneral = -1;        // WF_DEFER_GENERAL=1 | 0 forces / forbids the two-class traversal; -1 (unset): by the scene's counts
+    bool noFast = false;          // WF_NO_FAST (set to anything): the reference-order walks only
+    bool animFast = true;         // WF_ANIM_FAST=0
+    bool pixelMajor = true;       // WF_PIXEL_MAJOR=0: items of a pass ordered sample by sample
+    bool noSampleTops = false;    // WF_NO_SAMPLE_TOPS (set to anything)
+    int trWavefront = -1;         // WF_TR_WAVEFRONT (wf_ctx::trWavefront)
+    int frameOverlap = 1;         // WF_FRAME_OVERLAP: 0 | 1 | 2 (wf_ctx::frameOverlap)
+    bool samplesShaded = true;    // WF_SAMPLES_SHADED=0
+    bool traceLaunch = false;     // WF_TRACE_LAUNCH (set to anything)
+    bool scratchPrime = true;     // WF_SCRATCH_PRIME=0
+    // the tree builder's (BuildFastBVH)
+    int leafCollapse = 1;         // WF_LEAF_COLLAPSE: 1..16 primitives a reference subtree may hold to become one leaf
+    int braidMax = 2;             // WF_BRAID: 0..256, most entries one instance is opened into (measured on the spec scene, profiles/r06_rebraid_ab_sm16.txt: 2 is the optimum — DESIGN 4.1)
+    bool tightInstances = true;   // WF_TIGHT_INSTANCES=0
+    double braidMinFrac = 1.0 / 64;   // WF_BRAID_MIN_FRAC: an entry smaller than this fraction of the instance's own box is not opened further
+    bool braidVerbose = false;    // WF_BRAID_VERBOSE=1: one line on stderr per re-braided tree
+    static Switches FromEnv() {
+        auto isSet = [](const char *name) { return getenv(name) != nullptr; };
+        auto on = [](const char *name) { const char *e = getenv(name); return !(e && atoi(e) == 0); };   // on unless set to 0
+        auto number = [](const char *name, int unset) { const char *e = getenv(name); return e ? atoi(e) : unset; };
+        Switches s;
+        s.shadeTris = on("WF_SHADE_TRIS");
+        s.gridCorners = on("WF_GRID_CORNERS");
+        if (const char *e = getenv("WF_GRID_CORNERS_GB")) s.gridCornersGB = atof(e);
+        s.mediumLean = on("WF_MEDIUM_LEAN");
+        s.leanShade = on("WF_LEAN_SHADE");
+        s.leanPerType = on("WF_LEAN_PER_TYPE");
+        if (isSet("WF_DEFER_GENERAL")) s.deferGeneral = number("WF_DEFER_GENERAL", 0) != 0;
+        s.noFast = isSet("WF_NO_FAST");
+        s.animFast = on("WF_ANIM_FAST");
+        s.pixelMajor = on("WF_PIXEL_MAJOR");
+        s.noSampleTops = isSet("WF_NO_SAMPLE_TOPS");
+        s.trWavefront = number("WF_TR_WAVEFRONT", -1);
+        s.frameOverlap = std::min(2, std::max(0, number("WF_FRAME_OVERLAP", 1)));
+        s.samplesShaded = on("WF_SAMPLES_SHADED");
+        s.traceLaunch = isSet("WF_TRACE_LAUNCH");
+        s.scratchPrime = on("WF_SCRATCH_PRIME");
+        s.leafCollapse = std::min(16, std::max(1, number("WF_LEAF_COLLAPSE", 1)));
+        s.braidMax = std::min(256, std::max(0, number("WF_BRAID", 2)));
+        s.tightInstances = on("WF_TIGHT_INSTANCES");
+        if (const char *e = getenv("WF_BRAID_MIN_FRAC")) s.braidMinFrac = atof(e);
+        s.braidVerbose = number("WF_BRAID_VERBOSE", 0) != 0;
+        return s;
+    }
+};
+
+// Everything decided about a scene: a pure function of the description and the switches (PlanScene), made before anything is uploaded.
+// wf_ctx::plan is the one copy; wf_scene_plan_query gives the same answers without a context.
+struct ScenePlan {
+    // what the description holds (the upload copies these into SceneView)
+    int64_t nBvhPrims = 0;       // entries of bvh_prims the trees index (wf_scene_check_instances)
+    int nInstances = 0;
+    int nestedAnimated = 0;      // records of `instances` that are nested placements (animated shapes inside instance definitions); such scenes keep the reference-order walks
+    bool haveAlpha = false, texNeedsFootprint = false, haveMix = false, haveSubsurface = false, haveQuadricAlpha = false, haveCurves = false, haveAnimated = false;
+    int matTypeMask = 0;
+    bool matPresent[WF_MAT_NTYPES] = {};
+    // the stage kernels' variants
+    bool mediumLean = false;     // every medium is homogeneous or a non-emissive uniform grid: k_medium_sample<true>
+    bool portalLights = false;   // the scene has a portal infinite light (k_handle_escaped<RARE>)
+    bool leanShade = false;      // the scene qualifies for the lean shade kernels (SceneLean)
+    // ... per MATERIAL TYPE since round 6: a type none of whose materials sits on a quadric / patch / curve keeps its lean shade kernel
+    // when such shapes appear elsewhere in the scene (their hits are items of other types' queues)
+    bool leanType[WF_MAT_NTYPES] = {};
+    bool rareLights = false;     // the scene has a light type only the VARIANT 2 material kernels sample (portal infinite lights)
+    // the walk kernels' variants (PickWalkKernels turns these into template instantiations)
+    int genMode = 0;             // general-primitive strength of the traversal kernels: 0 triangles only, 1 simple alpha, 2 anything but curves and alpha on quadrics, 3 anything (see GeneralPrims)
+    bool deferGeneral = false;   // TWO-CLASS TRAVERSAL (see WalkKernels)
+    int genTri = 0;
+    bool fastBuilt = false;      // BuildFastBVH gave a production layout (FastTrees): it is uploaded, in use or not
+    bool fastOk = false;         // ... and the scene's walks use it; false (leaf sizes > 16, nested placements, WF_NO_FAST, ...): the reference-order kernels only
+    bool animFast = false;       // the scene's AnimatedPrimitives are walked by the production kernels' ANIM variants (round 6; genMode <= 1 only)
+    int cursorChunk = 2;         // 64-ray batches a closest-hit wave takes per cursor fetch (chosen from the tree size)
+    int cursorChunkShadow = 2;   // ... an any-hit wave (round 6, with the descent scheduling, 10 M-triangle scene: closest-hit 27.7 ms at 1, 26.7 at 3, 27.0 at 4, 27.4 at 8, 29.9 at 16;
+                                 // any-hit 12.15 at 1, 12.16 at 3, 12.4 at 4, 13.0 at 8: profiles/r06_cursor_chunk_ab_sm16.txt)
+                                 // (-3 %), but on a 30 k-triangle scene one fetch per 64 rays is 83 atomics/us on one counter: the kernel's bound
+    int spillRows = 0;           // rows of wf_ctx::stackSpill behind the LDS stack entries, from the trees' depths
+};
+// The production traversal layout as BuildFastBVH leaves it on the host: what the upload copies once PlanScene has succeeded.
+struct FastTrees {
+    std::vector<QNode> nodes;
+    std::vector<LeafTri> tris;
+    std::vector<FastDef> defs;
+    std::vector<SubEntry> subs;
+    FastBVH header{};
+};
+struct FastDepths { int top = 0, def = 0, maxLeafInstances = 0; };   // levels of the four-wide trees (top level / deepest definition), most instances in one leaf
+
+int NestedPlacements(const wf_scene_desc *d);   // records of `instances` that are nested placements
+int64_t BvhPrimCount(const wf_scene_desc *d);   // entries of bvh_prims the trees index
+// wf_fastbvh_build.cpp; false: the scene has no production layout (leaves over 16 primitives, nested placements, ...)
+bool BuildFastBVH(const wf_scene_desc *d, const Switches &sw, FastTrees *trees, FastDepths *depths);
+// wf_plan.cpp
+int CheckAbi(const wf_scene_desc *d);
+int PlanScene(const wf_scene_desc *d, const Switches &sw, ScenePlan *plan, FastTrees *trees);
+bool PlanValue(const ScenePlan &plan, const char *key, int64_t *value);
+
+}}  // namespace wf::planning

@@ -1,6 +1,6 @@
 """The production traversal layout, checked on the HOST (no GPU): wf_debug_fastbvh_check (include/wf_abi.h) builds the QNode / LeafTri /
 instance-entry arrays wf_scene_upload would upload — since round 6 with the top-level tree rebuilt over partially re-braided instances
-(wf_traverse.h, SubEntry) — and walks them with random rays in double arithmetic.  The property the tree owes: every triangle a ray
+(wf_fastbvh.h, SubEntry) — and walks them with random rays in double arithmetic.  The property the tree owes: every triangle a ray
 really hits (brute force over the top-level triangles and every (instance, triangle) pair) is among the triangles the walk tests.
 The hits themselves are decided by the exact triangle test on the device and pinned bit for bit by the GPU suite's goldens."""
 import os

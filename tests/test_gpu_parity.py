@@ -199,7 +199,7 @@ def test_two_class_traversal_and_rebraided_instances(wfpt, tmp_path, monkeypatch
     """Round 6's two structural options of the production walk, FORCED on scenes their heuristics would leave alone, stay bit-identical with the
     reference's render: the two-class traversal (WF_DEFER_GENERAL=1: the triangle kernels walk every ray and hand the rays that meet a quadric /
     patch / curve leaf to a second launch of the general kernels — wf_backend.hip) and instances opened into several entries of the
-    top-level tree (WF_BRAID=8: partial re-braiding, wf_traverse.h SubEntry; 0 = one entry per instance in the reference's own tree)."""
+    top-level tree (WF_BRAID=8: partial re-braiding, wf_fastbvh.h SubEntry; 0 = one entry per instance in the reference's own tree)."""
     monkeypatch.setenv("WF_DEFER_GENERAL", "1")
     monkeypatch.setenv("WF_BRAID", str(braid))
     _check_image_vs_oracle_and_reference(wfpt, tmp_path, name)

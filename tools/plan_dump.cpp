@@ -1,0 +1,94 @@
+// tools/plan_dump.cpp — the library's host-only planning units (pbrt-v4_amd/csrc/hip/wf_plan.cpp, wf_fastbvh_build.cpp) run stand-alone:
+// no device, no libwfhip / libwfhost, nothing loaded into another process.  For every scene file on the command line: ParseFiles,
+// BuildSceneTables, PlanScene under the environment's switches and the builder's self-check, then ONE line with every field of the plan,
+// the sizes and a 64-bit FNV-1a of the four arrays of the production traversal layout, a hash of the header's scalar fields and the
+// eight outputs of the self-check.  Two builds of the planning code agree on a scene exactly when their lines are equal; built with
+// sanitizers (make -C pbrt-v4_amd SAN="-fsanitize=..." ...plan_dump, tools/sanitize_checker.sh) it is how that code is run under them.
+//
+//   plan_dump [--datadir <dir>] [--rays <n>] scene.pbrt ...
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <exception>
+#include <string>
+#include "../pbrt-v4_amd/csrc/host/scene.h"
+#include "../pbrt-v4_amd/csrc/host/spectra.h"
+#include "../pbrt-v4_amd/csrc/hip/wf_plan.h"
+
+using namespace wf;
+using namespace wf::planning;
+
+static uint64_t Fnv(const void *p, size_t n, uint64_t h = 0xcbf29ce484222325ull) {
+    const unsigned char *b = (const unsigned char *)p;
+    for (size_t i = 0; i < n; ++i) h = (h ^ b[i]) * 0x100000001b3ull;
+    return h;
+}
+template <typename T>
+static uint64_t FnvOf(const std::vector<T> &v) { return Fnv(v.data(), v.size() * sizeof(T)); }
+
+static void DumpScene(const std::string &path, int nRays) {
+    RenderOptions opt;
+    opt.quiet = true;
+    ParsedScene parsed;
+    ParseFiles({path}, &opt, &parsed);
+    SceneTables T;
+    BuildSceneTables(parsed, opt, &T);
+    const size_t slash = path.rfind('/');
+    printf("%s:", (slash == std::string::npos ? path : path.substr(slash + 1)).c_str());
+    ScenePlan p;
+    FastTrees trees;
+    if (PlanScene(&T.desc, Switches::FromEnv(), &p, &trees)) { printf(" rejected: %s\n", wf_last_error()); return; }
+    printf(" nBvhPrims=%lld nInstances=%d nestedAnimated=%d haveAlpha=%d texNeedsFootprint=%d haveMix=%d haveSubsurface=%d haveQuadricAlpha=%d haveCurves=%d haveAnimated=%d",
+           (long long)p.nBvhPrims, p.nInstances, p.nestedAnimated, p.haveAlpha, p.texNeedsFootprint, p.haveMix, p.haveSubsurface, p.haveQuadricAlpha, p.haveCurves, p.haveAnimated);
+    printf(" matTypeMask=%#x matPresent=", p.matTypeMask);
+    for (bool b : p.matPresent) putchar('0' + b);
+    printf(" mediumLean=%d portalLights=%d leanShade=%d leanType=", p.mediumLean, p.portalLights, p.leanShade);
+    for (bool b : p.leanType) putchar('0' + b);
+    printf(" rareLights=%d genMode=%d deferGeneral=%d genTri=%d fastBuilt=%d fastOk=%d animFast=%d cursorChunk=%d cursorChunkShadow=%d spillRows=%d",
+           p.rareLights, p.genMode, p.deferGeneral, p.genTri, p.fastBuilt, p.fastOk, p.animFast, p.cursorChunk, p.cursorChunkShadow, p.spillRows);
+    if (!p.fastBuilt) { printf(" trees: no production layout\n"); return; }
+    const FastBVH &h = trees.header;
+    uint64_t hh = Fnv(&h.nNodes, sizeof h.nNodes);   // the header's fields one by one: no padding, no pointers
+    hh = Fnv(h.base, sizeof h.base, hh);
+    hh = Fnv(h.cell, sizeof h.cell, hh);
+    hh = Fnv(&h.absBand, sizeof h.absBand, hh);
+    hh = Fnv(&h.tieRel, sizeof h.tieRel, hh);
+    hh = Fnv(&h.tieRelTri, sizeof h.tieRelTri, hh);
+    hh = Fnv(&h.absBandTri, sizeof h.absBandTri, hh);
+    hh = Fnv(&h.firstGeneral, sizeof h.firstGeneral, hh);
+    printf(" nodes=%zu:%016llx tris=%zu:%016llx defs=%zu:%016llx subs=%zu:%016llx header=%016llx", trees.nodes.size(), (unsigned long long)FnvOf(trees.nodes),
+           trees.tris.size(), (unsigned long long)FnvOf(trees.tris), trees.defs.size(), (unsigned long long)FnvOf(trees.defs), trees.subs.size(),
+           (unsigned long long)FnvOf(trees.subs), (unsigned long long)hh);
+    int64_t out[8];
+    if (wf_debug_fastbvh_check(&T.desc, nRays, 1, out)) { printf(" check: %s\n", wf_last_error()); return; }
+    printf(" check=");
+    for (int k = 0; k < 8; ++k) printf("%s%lld", k ? "," : "", (long long)out[k]);
+    printf("\n");
+}
+
+int main(int argc, char **argv) {
+    std::string dataDir;
+    int nRays = 64;
+    std::vector<std::string> scenes;
+    for (int i = 1; i < argc; ++i) {
+        const std::string a = argv[i];
+        if (a == "--datadir" && i + 1 < argc) dataDir = argv[++i];
+        else if (a == "--rays" && i + 1 < argc) nRays = atoi(argv[++i]);
+        else scenes.push_back(a);
+    }
+    if (scenes.empty()) { fprintf(stderr, "usage: plan_dump [--datadir <dir>] [--rays <n>] scene.pbrt ...\n"); return 1; }
+    if (dataDir.empty()) {
+        // <repo>/pbrt-v4_amd/data relative to this binary's usual location pbrt-v4_amd/_build/plan_dump
+        const std::string self = argv[0];
+        const size_t p = self.rfind('/');
+        dataDir = (p == std::string::npos ? std::string(".") : self.substr(0, p)) + "/../data";
+    }
+    try {
+        SpectralData::Init(dataDir, dataDir + "/cache");
+        for (const std::string &s : scenes) { DumpScene(s, nRays); fflush(stdout); }
+    } catch (const std::exception &e) {
+        fprintf(stderr, "%s\n", e.what());
+        return 1;
+    }
+    return 0;
+}

@@ -4,6 +4,10 @@
 # incidents of the material kernels were put down to a toolchain defect; an out-of-bounds private-array index or an uninitialised read
 # in the shared source would look the same.  This rules the shared source out on these inputs (device-only code — the LDS regroup,
 # the queue allocation — is not covered).  About ten minutes on 8 cores.  Test infrastructure only.
+# Second section: the library's host-only planning units (scene checks, PlanScene, the builder of the production traversal layout and
+# its self-check) as the stand-alone program tools/plan_dump.cpp, built the same way and run over the golden scenes and the downscaled
+# benchmark stand-ins under the builder's switches (tools/plan_dump_all.sh).  Every unit of it is compiled by the clang that hipcc
+# drives (two compilers' sanitizer runtimes do not mix).  About a quarter of an hour more.
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=${1:-/tmp/asan_build}
@@ -19,4 +23,11 @@ for f in *.pbrt fuzz/*.pbrt; do
   n=$((n+1))
 done
 echo "scenes $n, with sanitizer findings $bad"
-[ $bad -eq 0 ]
+SAN="-fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -g -O1"
+CLANG=$(hipconfig -l)/clang++
+make -C $ROOT/pbrt-v4_amd -j8 OUT=$OUT/plan CXX=$CLANG PLANCXX=$CLANG SAN="$SAN" $OUT/plan/plan_dump > /dev/null
+$ROOT/tools/plan_dump_all.sh $OUT/plan/plan_dump > $OUT/plan_dump.txt 2>&1
+pbad=$(grep -cE "runtime error|AddressSanitizer" $OUT/plan_dump.txt || true)
+grep -E "runtime error|AddressSanitizer" -B1 -A6 $OUT/plan_dump.txt | head -40
+echo "plan_dump lines $(grep -vc '^==' $OUT/plan_dump.txt), sanitizer reports $pbad"
+[ $bad -eq 0 ] && [ $pbad -eq 0 ]
