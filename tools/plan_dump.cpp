@@ -5,7 +5,11 @@
 // eight outputs of the self-check.  Two builds of the planning code agree on a scene exactly when their lines are equal; built with
 // sanitizers (make -C pbrt-v4_amd SAN="-fsanitize=..." ...plan_dump, tools/sanitize_checker.sh) it is how that code is run under them.
 //
-//   plan_dump [--datadir <dir>] [--rays <n>] scene.pbrt ...
+// With --tables the line also carries what BuildSceneTables made: `name=count:fnv64` for every vector SceneTables::Save writes, the
+// scalars it writes, materialTypePresent and a hash of the descriptor with its pointers cleared — two builds of scene_build.cpp agree on
+// a scene exactly when these are equal (tools/plan_dump_all.sh tables, profiles/scene_build_tables_parent_vs_change.txt).
+//
+//   plan_dump [--datadir <dir>] [--rays <n>] [--tables] scene.pbrt ...
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -26,7 +30,30 @@ static uint64_t Fnv(const void *p, size_t n, uint64_t h = 0xcbf29ce484222325ull)
 template <typename T>
 static uint64_t FnvOf(const std::vector<T> &v) { return Fnv(v.data(), v.size() * sizeof(T)); }
 
-static void DumpScene(const std::string &path, int nRays) {
+// every array and scalar of SceneTables::Save, in its order
+static void DumpTables(const SceneTables &T) {
+#define VEC(v) (T.v.empty() ? printf(" " #v "=0") : printf(" " #v "=%zu:%016llx", T.v.size(), (unsigned long long)FnvOf(T.v)))
+    VEC(P); VEC(N); VEC(UV); VEC(triIndices); VEC(triMesh); VEC(bvhPrims); VEC(infiniteLights);
+    VEC(meshes); VEC(quadrics); VEC(instances); VEC(instanceDefs); VEC(animated); VEC(sobolMatrices); VEC(vdcSobol); VEC(vdcSobolInv); VEC(haltonPrimes); VEC(haltonPermOffsets);
+    VEC(haltonPerms); VEC(bvhNodes); VEC(pool.spectra); VEC(pool.data); VEC(textures); VEC(materials);
+    VEC(lights); VEC(lightBvh); VEC(lightTransforms); VEC(filterData); VEC(powerAlias); VEC(imageLights);
+    VEC(noisePerm); VEC(texImages); VEC(tableData); VEC(media); VEC(mediumData);
+    printf(" imageFile=%zu:%016llx", T.imageFile.size(), (unsigned long long)Fnv(T.imageFile.data(), T.imageFile.size()));
+    VEC(sRGBFromFilmRGB); VEC(S);
+#undef VEC
+    printf(" scalars=%d,%d,%d,%d,%d,%d,%d,%d matTypePresent=", T.nTopBvhNodes, T.nTopPrims, T.saveFP16 ? 1 : 0, T.spp, T.scanlinesPerPass, T.maxQueueSize, T.nPasses,
+           T.desc.rgb2spec_coeffs ? 1 : 0);
+    for (bool b : T.materialTypePresent) putchar('0' + b);
+    // the descriptor without its addresses: Finalize() of a SceneTables with no arrays sets every pointer it owns to null (and the counts,
+    // which the sizes above already give, to 0); the one pointer that is not into the tables is cleared by hand (the 0/1 flag above)
+    SceneTables E;
+    E.desc = T.desc;
+    E.Finalize();
+    E.desc.rgb2spec_coeffs = nullptr;
+    printf(" desc=%016llx", (unsigned long long)Fnv(&E.desc, sizeof E.desc));
+}
+
+static void DumpScene(const std::string &path, int nRays, bool tables) {
     RenderOptions opt;
     opt.quiet = true;
     ParsedScene parsed;
@@ -35,6 +62,7 @@ static void DumpScene(const std::string &path, int nRays) {
     BuildSceneTables(parsed, opt, &T);
     const size_t slash = path.rfind('/');
     printf("%s:", (slash == std::string::npos ? path : path.substr(slash + 1)).c_str());
+    if (tables) DumpTables(T);
     ScenePlan p;
     FastTrees trees;
     if (PlanScene(&T.desc, Switches::FromEnv(), &p, &trees)) { printf(" rejected: %s\n", wf_last_error()); return; }
@@ -69,14 +97,16 @@ static void DumpScene(const std::string &path, int nRays) {
 int main(int argc, char **argv) {
     std::string dataDir;
     int nRays = 64;
+    bool tables = false;
     std::vector<std::string> scenes;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--datadir" && i + 1 < argc) dataDir = argv[++i];
         else if (a == "--rays" && i + 1 < argc) nRays = atoi(argv[++i]);
+        else if (a == "--tables") tables = true;
         else scenes.push_back(a);
     }
-    if (scenes.empty()) { fprintf(stderr, "usage: plan_dump [--datadir <dir>] [--rays <n>] scene.pbrt ...\n"); return 1; }
+    if (scenes.empty()) { fprintf(stderr, "usage: plan_dump [--datadir <dir>] [--rays <n>] [--tables] scene.pbrt ...\n"); return 1; }
     if (dataDir.empty()) {
         // <repo>/pbrt-v4_amd/data relative to this binary's usual location pbrt-v4_amd/_build/plan_dump
         const std::string self = argv[0];
@@ -85,7 +115,7 @@ int main(int argc, char **argv) {
     }
     try {
         SpectralData::Init(dataDir, dataDir + "/cache");
-        for (const std::string &s : scenes) { DumpScene(s, nRays); fflush(stdout); }
+        for (const std::string &s : scenes) { DumpScene(s, nRays, tables); fflush(stdout); }
     } catch (const std::exception &e) {
         fprintf(stderr, "%s\n", e.what());
         return 1;

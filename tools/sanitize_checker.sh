@@ -6,8 +6,13 @@
 # the queue allocation — is not covered).  About ten minutes on 8 cores.  Test infrastructure only.
 # Second section: the library's host-only planning units (scene checks, PlanScene, the builder of the production traversal layout and
 # its self-check) as the stand-alone program tools/plan_dump.cpp, built the same way and run over the golden scenes and the downscaled
-# benchmark stand-ins under the builder's switches (tools/plan_dump_all.sh).  Every unit of it is compiled by the clang that hipcc
-# drives (two compilers' sanitizer runtimes do not mix).  About a quarter of an hour more.
+# benchmark stand-ins under the builder's switches, then with --tables (every table of BuildSceneTables hashed) over the golden AND the fuzz
+# scenes and the stand-ins (tools/plan_dump_all.sh).  Every unit of it is compiled by the clang that hipcc drives (two compilers' sanitizer
+# runtimes do not mix).  About twenty minutes more.
+# KNOWN FINDING, open: the --tables pass reports "wf_scene.h:478 runtime error: nan is outside the range of representable values of type
+# 'int'" (MIPLevel, reached from the displacement evaluation of a plymesh) on fuzz/s6300046.pbrt, so this script ends non-zero until
+# csrc/common/wf_scene.h is fixed.  The first section runs the same scene without a report: its compiler's -fsanitize=undefined does not
+# include the float-to-integer conversion check (GCC enables -fsanitize=float-cast-overflow separately), clang's does.
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=${1:-/tmp/asan_build}
@@ -27,7 +32,8 @@ SAN="-fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-fram
 CLANG=$(hipconfig -l)/clang++
 make -C $ROOT/pbrt-v4_amd -j8 OUT=$OUT/plan CXX=$CLANG PLANCXX=$CLANG SAN="$SAN" $OUT/plan/plan_dump > /dev/null
 $ROOT/tools/plan_dump_all.sh $OUT/plan/plan_dump > $OUT/plan_dump.txt 2>&1
-pbad=$(grep -cE "runtime error|AddressSanitizer" $OUT/plan_dump.txt || true)
+$ROOT/tools/plan_dump_all.sh $OUT/plan/plan_dump tables >> $OUT/plan_dump.txt 2>&1 || true   # the table builder over the fuzz scenes too, hashing every table
+pbad=$(grep -cE "runtime error|AddressSanitizer|no line \(exit 1[2-9][0-9]\)" $OUT/plan_dump.txt || true)   # (a run that was killed counts too)
 grep -E "runtime error|AddressSanitizer" -B1 -A6 $OUT/plan_dump.txt | head -40
-echo "plan_dump lines $(grep -vc '^==' $OUT/plan_dump.txt), sanitizer reports $pbad"
+echo "plan_dump lines $(grep -vcE '^==|^    \|' $OUT/plan_dump.txt), sanitizer reports $pbad"
 [ $bad -eq 0 ] && [ $pbad -eq 0 ]
