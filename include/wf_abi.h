@@ -749,9 +749,12 @@ int wf_trace_closest_device_t(wf_ctx *ctx, int n, const float *rays8, wf_hit_rec
 int wf_trace_any_device_t(wf_ctx *ctx, int n, const float *rays8, int32_t *occluded);
 /* WavefrontAggregate::IntersectShadowTr on DEVICE items (wf_trace_shadow_tr_host / _host_t below describe the values): rays8 as above;
    medium[n]; lambda / Ld / r_u / r_l / out_L = n x 4 floats, read and written in place — out_L is zeroed, then written, by the
-   launches; all device pointers.  Scenes with media.  The transmittance kernel is the one the host-array call runs for the scene (with
-   the times on a scene with animated primitives, without them otherwise).  The packed ray items live in scratch the context owns,
-   grown on demand (growth may synchronise) and reused by the next call, which the in-order stream makes safe.  Not synchronised. */
+   launches; all device pointers.  Scenes with media.  The kernels are the ones the render's own transmittance stage runs for the scene
+   ("tr_route", wf_ctx_query): the reference-order walk per lane, the per-lane production walk, or the transmittance wavefront (begin,
+   WF_TR_SEGMENTS x (trace, segment), rest) — on a scene with animated primitives at the items' times, otherwise without them.  The
+   host-array calls below always run one loop per lane and give the same values bit for bit.  The packed ray items and, on the
+   wavefront route, its per-item state live in scratch the context owns (wf_queues_alloc is not needed), grown on demand (growth may
+   synchronise) and reused by the next call, which the in-order stream makes safe.  Not synchronised. */
 int wf_trace_shadow_tr_device(wf_ctx *ctx, int n, const float *rays8, const int32_t *medium, const float *lambda,
                               const float *Ld, const float *r_u, const float *r_l, float *out_L);
 /* WavefrontAggregate::IntersectOneRandom on DEVICE segments (wf_trace_one_random_host / _host_t below): segs7 = n x {p0[3], p1[3], time}
@@ -832,7 +835,9 @@ int wf_debug_counters(wf_ctx *ctx, uint64_t out[4], int reset);
 /* Which kernel variants the uploaded scene runs (tests assert that a scene takes the path they mean to cover): key = "fast_ok" (the
    production traversal layout is in use), "gen_mode" (0 - 3: strength of the walk kernels), "gen_tri", "defer_general" (the two-class
    traversal), "anim_fast" (AnimatedPrimitives on the production walk), "lean_shade", "lean_type_<material type>", "rare_lights", "medium_lean" (the lean delta-tracking / transmittance kernels),
-   "instances", "nested_animated" (records of `instances` that are nested placements: animated shapes inside instance definitions, per use).
+   "instances", "nested_animated" (records of `instances` that are nested placements: animated shapes inside instance definitions, per use),
+   "tr_route" (the transmittance stage of the render and of wf_trace_shadow_tr_device: -1 the scene has no media, 0 the reference-order
+   walk per lane, 1 the per-lane production walk, 2 the transmittance wavefront; WF_TR_WAVEFRONT=1 | 0 at upload forces / forbids the last).
    Introspection only; nothing in the reference corresponds. */
 int wf_ctx_query(wf_ctx *ctx, const char *key, int64_t *value);
 /* Host-only self-check of the production traversal layout (no device needed; CPU suite, tests/test_fastbvh_host.py): builds the
@@ -852,7 +857,7 @@ int wf_scene_check_instances(const wf_scene_desc *d, int64_t out[4]);
 /* Host-only form of wf_ctx_query (no device and no context needed; CPU suite, tests/test_scene_plan_host.py): runs the planning step of
    wf_scene_upload on `d` under the current environment switches (every check of the description, the classification, the production
    trees) and answers the keys that follow from the description alone: "fast_ok", "gen_mode", "gen_tri", "defer_general", "anim_fast",
-   "lean_shade", "lean_type_<material type>", "rare_lights", "medium_lean", "instances", "nested_animated".  A description that
+   "lean_shade", "lean_type_<material type>", "rare_lights", "medium_lean", "instances", "nested_animated", "tr_route".  A description that
    wf_scene_upload would reject fails here with the same message.  Every call plans the scene anew, tree build included: meant for
    tests and tools on small scenes, not for asking many keys of a large one. */
 int wf_scene_plan_query(const wf_scene_desc *d, const char *key, int64_t *value);

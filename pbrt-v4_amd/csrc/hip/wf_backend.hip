@@ -114,23 +114,31 @@ struct wf_ctx {
     // WF_SAMPLES_SHADED (default 1; 0: at every depth, as the stand-alone entry point): the fused pass draws no ray samples at the last
     // depth, where it leaves before the material stage that would read them (scenes without media and subsurface)
     bool samplesShaded = true;
-    // the transmittance wavefront: -1 = for two-level scenes only (default), 1 = always, 0 = never (WF_TR_WAVEFRONT).  Measured on the
-    // cloud-like spec scene (14 triangles, 512^3 grid; gpurun_out/r3j_bench_cloud_tr*.json): per-lane loop 27.9 ms per 16 spp, wavefront
-    // 31.4 ms (begin 3.3 + trace 3.7 + segment 24.1 + rest 0.3) — the time is the ratio tracking through the grid, not the walk, and the
-    // per-lane loop keeps its state in registers; with object instances the per-lane alternative is the reference-order walk (1 wave / SIMD)
-    int trWavefront = -1;
     bool cursorDirty[2] = {false, false};   // the closest-hit / any-hit work cursor has been used since a k_reset last zeroed it
     ScenePlan plan;              // what the uploaded scene runs: written by PlanScene, read by PickWalkKernels, the launch sites and wf_queues_alloc
     WalkKernels walk;
-    // The scratch of wf_trace_shadow_tr_device: the packed shadow-queue items of the call (k_pack_shadow_items) and its counter block.
-    // Owned by the context and grown geometrically (GrowTrScratch: the only place a call may synchronise or allocate), freed in
-    // DestroyCtx.  The next call overwrites it without waiting: every launch that reads it is on the context's in-order stream, ahead
-    // of the pack kernel that rewrites it.
+    // The scratch of wf_trace_shadow_tr_device: the packed shadow-queue items of the call (k_pack_shadow_items), its counter block and —
+    // on a scene whose plan routes transmittance through the wavefront (plan.trRoute == 2) — the wavefront's per-item state, index
+    // queues and hit records: a call's n has nothing to do with the render's queue size, and the call works without wf_queues_alloc, so
+    // it borrows none of ctx->ws's arrays.  Owned by the context and grown geometrically (GrowTrScratch: the only place a call may
+    // synchronise or allocate), freed in DestroyCtx.  The next call overwrites it without waiting: every launch that reads it is on the
+    // context's in-order stream, ahead of the pack kernel that rewrites it.
     struct TrScratch {
         F4 *o = nullptr, *d = nullptr, *lambdaPdf = nullptr;
         float *pathTime = nullptr;
+        F4 *trO = nullptr, *trD = nullptr, *trT = nullptr, *trRu = nullptr, *trRl = nullptr, *hit = nullptr;   // (the wavefront's: null on the other routes)
+        I4 *trRng = nullptr;
+        int32_t *trQ[2] = {nullptr, nullptr}, *hitInst = nullptr;
         int32_t *counters = nullptr;
         size_t capacity = 0;   // items
+        // every per-item array with its element size (the counter block is not one of them)
+        struct Slot { void **p; size_t elem; bool wavefront; };
+        std::vector<Slot> slots() {
+            return {{(void **)&o, sizeof(F4), false}, {(void **)&d, sizeof(F4), false}, {(void **)&lambdaPdf, sizeof(F4), false}, {(void **)&pathTime, sizeof(float), false},
+                    {(void **)&trO, sizeof(F4), true}, {(void **)&trD, sizeof(F4), true}, {(void **)&trT, sizeof(F4), true}, {(void **)&trRu, sizeof(F4), true},
+                    {(void **)&trRl, sizeof(F4), true}, {(void **)&hit, sizeof(F4), true}, {(void **)&trRng, sizeof(I4), true},
+                    {(void **)&trQ[0], sizeof(int32_t), true}, {(void **)&trQ[1], sizeof(int32_t), true}, {(void **)&hitInst, sizeof(int32_t), true}};
+        }
     } trScratch;
     int32_t *probeCursor = nullptr;
     int W = 0, H = 0;
@@ -657,8 +665,7 @@ __device__ inline __attribute__((always_inline)) RefHit RetraceRefOrder(const Sc
     if (dbg) atomicAdd(dbg + 2, 1);
     return out;
 }
-// which kernel variants resolve their near-ties themselves
-constexpr bool RetraceInline(int gen) { return gen <= 1; }
+// (which kernel variants resolve their near ties themselves: RetraceInline, wf_plan.h — the plan's transmittance route asks it too)
 
 // -DWF_WALK_STATS (diagnostic builds only): per-phase counts of the closest-hit (slot 0) and any-hit (slot 1) production walks — how often a
 // wave ran the interior step / the leaf step / an instance transition / a refill, and how many lanes were active each time — summed
@@ -1349,6 +1356,9 @@ __global__ void __launch_bounds__(TBLOCK, INST ? WF_TWAVES_INST : WF_TWAVES_CLOS
             const int i = q[j];
             F4 o4 = ws.trO[i], d4 = ws.trD[i];
             *o = V3{o4.x, o4.y, o4.z}; *d = V3{d4.x, d4.y, d4.z}; *tMax = ws.sq.o[i].w;
+            // (the time of the ORIGINAL shadow item: every segment of one ray, the ones respawned behind an interface included, is walked
+            //  at the same time; the walk fetches a near-tie ray a second time, which stores the same value again)
+            if constexpr (GenAnim(GEN)) g_time[threadIdx.x] = ShadowTime<true>(ws, ws.sq.d[i].w);
         },
         [&](int j, bool valid, const RayWalk &w) {
             if (!valid) return;
@@ -1357,7 +1367,9 @@ __global__ void __launch_bounds__(TBLOCK, INST ? WF_TWAVES_INST : WF_TWAVES_CLOS
             if (INST) ws.hitInst[i] = w.prim >= 0 ? w.inst : -1;
         });
 }
-template <bool MLEAN>
+// MLEAN: the lean medium code.  ANIM: the scene has animated primitives (the interaction of a hit through one is rebuilt at the ray's
+// time; workgroups of BLOCK threads, like every caller of the interpolation: see RouteBlock)
+template <bool MLEAN, bool ANIM = false>
 __global__ void __launch_bounds__(BLOCK) k_tr_segment(const SceneView sv, WorkState ws, int cur) {
     const int n = ws.counters[(CNT_TR0 + cur) * CNT_STRIDE];
     for (int j = blockIdx.x * BLOCK + threadIdx.x; j < n; j += gridDim.x * BLOCK) {
@@ -1366,12 +1378,14 @@ __global__ void __launch_bounds__(BLOCK) k_tr_segment(const SceneView sv, WorkSt
         TrLoad(ws, i, &st);
         const F4 h = ws.hit[i];
         const int prim = (int)FloatToBits(h.x);
-        if (TrSegment<false, MLEAN>(sv, ws, i, &st, prim >= 0, prim, HitInst(sv, ws, i), h.y, h.z, h.w)) {
+        if (TrSegment<ANIM, MLEAN>(sv, ws, i, &st, prim >= 0, prim, HitInst(sv, ws, i), h.y, h.z, h.w)) {
             TrStore(ws, i, st);
             ws.trQ[cur ^ 1][QueueAlloc(&ws.counters[(CNT_TR0 + (cur ^ 1)) * CNT_STRIDE])] = i;
         } else TrFinish(ws, i, st);
     }
 }
+// ANIM: the reference-order walk at the shadow item's time, as k_shadow_tr<true>
+template <bool ANIM>
 __global__ void __launch_bounds__(BLOCK) k_tr_rest(const SceneView sv, WorkState ws, int cur, int *stackSpill) {
     const int n = ws.counters[(CNT_TR0 + cur) * CNT_STRIDE];
     if (n == 0) return;
@@ -1381,10 +1395,11 @@ __global__ void __launch_bounds__(BLOCK) k_tr_rest(const SceneView sv, WorkState
         const int i = ws.trQ[cur][j];
         TrState ts;
         TrLoad(ws, i, &ts);
-        KTraceTransmittanceFrom(sv, ws, i, ts, [&](V3 o, V3 d, float tMax, int *prim, int *inst, float *b0, float *b1, float *b2) {
+        const float time = ShadowTime<ANIM>(ws, ws.sq.d[i].w);
+        KTraceTransmittanceFrom<ANIM>(sv, ws, i, ts, [&](V3 o, V3 d, float tMax, int *prim, int *inst, float *b0, float *b1, float *b2) {
             ClosestHit ch;
             st.n = 0;
-            bool found = BVHIntersectClosest(sv, o, d, tMax, st, &ch);
+            bool found = BVHIntersectClosest<ANIM>(sv, o, d, tMax, st, &ch, time);
             if (found) { *prim = ch.prim; *inst = ch.inst; *b0 = ch.h.b0; *b1 = ch.h.b1; *b2 = ch.h.b2; }
             return found;
         });
@@ -1688,7 +1703,8 @@ static int PickWalkKernels(wf_ctx *ctx) {
         k.traceClosest8 = PickWalk<TraceClosestWalk8>(GenX(gen, false, ctx->plan.animFast), inst, TimedWalks{});
         k.traceAny8 = PickWalk<TraceAnyWalk8>(GenX(gen, false, ctx->plan.animFast), inst, TimedWalks{});
     }
-    if (RetraceInline(gen)) k.trTrace = PickWalk<TrTraceWalk>(gen, inst, std::integer_sequence<int, 0, 1>{});   // (resolves its near ties inside the walk)
+    // (resolves its near ties inside the walk; an animFast scene's at the shadow item's time, through the ANIM variants)
+    if (RetraceInline(gen)) k.trTrace = PickWalk<TrTraceWalk>(GenX(gen, false, ctx->plan.animFast), inst, std::integer_sequence<int, 0, 1, GenX(0, false, true), GenX(1, false, true)>{});
     if (!k.closest || !k.shadow || !k.traceClosest || !k.traceAny || !k.traceClosest8 || !k.traceAny8 || (ctx->plan.deferGeneral && (!k.closestGen || !k.shadowGen)) || (RetraceInline(gen) && !k.trTrace))
         return fail(-1, "no walk kernel for this scene (genMode %d, genTri %d, two-class %d, animated %d, instances %d)", gen, ctx->plan.genTri, (int)ctx->plan.deferGeneral, (int)ctx->plan.animFast, (int)inst);
     // resident workgroups of the queue walks (closest-hit and shadow differ in registers)
@@ -1729,8 +1745,9 @@ static void DestroyCtx(wf_ctx *ctx) {
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     if (ctx->stream3) (void)hipStreamSynchronize(ctx->stream3);
     for (void *p : ctx->allocs) (void)hipFree(p);
-    for (void *p : {(void *)ctx->trScratch.o, (void *)ctx->trScratch.d, (void *)ctx->trScratch.lambdaPdf, (void *)ctx->trScratch.pathTime, (void *)ctx->trScratch.counters})
-        if (p) (void)hipFree(p);
+    for (const wf_ctx::TrScratch::Slot &sl : ctx->trScratch.slots())
+        if (*sl.p) (void)hipFree(*sl.p);
+    if (ctx->trScratch.counters) (void)hipFree(ctx->trScratch.counters);
     for (auto &e : ctx->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     for (auto e : ctx->eventPool) (void)hipEventDestroy(e);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -2094,7 +2111,7 @@ int wf_queues_alloc(wf_ctx *ctx, int pixels_per_pass, int samples_per_pass) {
     if (ws.stripCount < 1) { ws.stripRank = 0; ws.stripCount = 1; ws.stripHeight = 1; ws.localRows = ctx->H; }
     ctx->passSamples = 1;
     const Switches sw = Switches::FromEnv();
-    // (pixelMajor here and trWavefront below are set by their switches alone, and unset switches give wf_ctx's own defaults)
+    // (pixelMajor is set by its switch alone, and an unset switch gives wf_ctx's own default)
     ctx->pixelMajor = sw.pixelMajor;
     ctx->ws.slotStride = ctx->pixelMajor ? 1 : 0;
     ctx->passStep = 1;
@@ -2114,7 +2131,6 @@ int wf_queues_alloc(wf_ctx *ctx, int pixels_per_pass, int samples_per_pass) {
         if ((e = devAlloc(ctx, &ws.sampleTops, (size_t)5 * pixels_per_pass))) return e;
     if ((e = allocRayQueue(ctx, &ws.rq[0], n)) || (e = allocRayQueue(ctx, &ws.rq[1], n))) return e;
     if (ctx->svHost.haveMedia) {
-        ctx->trWavefront = sw.trWavefront;
         if ((e = devAlloc(ctx, &ws.trO, n)) || (e = devAlloc(ctx, &ws.trD, n)) || (e = devAlloc(ctx, &ws.trT, n)) || (e = devAlloc(ctx, &ws.trRu, n)) ||
             (e = devAlloc(ctx, &ws.trRl, n)) || (e = devAlloc(ctx, &ws.trRng, n)) || (e = devAlloc(ctx, &ws.trQ[0], n)) || (e = devAlloc(ctx, &ws.trQ[1], n)))
             return e;
@@ -2298,26 +2314,30 @@ int wf_medium_sample(wf_ctx *ctx, int depth) {
     LAUNCH("Sample direct/indirect - Henyey-Greenstein", (ctx->plan.rareLights ? k_medium_scatter<true> : k_medium_scatter<false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
     return 0;
 }
+// the wavefront's segment kernel for the scene: the lean medium code or all of it, hits through animated primitives at the ray's time or not
+using TrSegmentFn = void (*)(const SceneView, WorkState, int);
+static TrSegmentFn TrSegmentKernel(const wf_ctx *ctx) {
+    if (ctx->plan.animFast) return ctx->plan.mediumLean ? k_tr_segment<true, true> : k_tr_segment<false, true>;
+    return ctx->plan.mediumLean ? k_tr_segment<true> : k_tr_segment<false>;
+}
 // TraceShadowRays with media: IntersectShadowTr (wavefront/aggregate.cpp:70-88, intersect.h:165-274)
 int wf_intersect_shadow_tr(wf_ctx *ctx, int depth) {
     if (int e = checkReady(ctx)) return e;
     if (!ctx->svHost.haveMedia) return fail(-1, "wf_intersect_shadow_tr: the scene has no media (use wf_intersect_shadow)");
-    // (a scene with AnimatedPrimitives keeps the reference-order transmittance walk, which interpolates their transformations at the shadow
-    //  ray's time: the transmittance wavefront's walk kernel has no ANIM variant — fuzz scene s6300008, round 6)
-    if (ctx->plan.fastOk && !ctx->plan.animFast && !ctx->countTraversal && RetraceInline(ctx->plan.genMode) && (ctx->trWavefront == 1 || (ctx->trWavefront < 0 && (ctx->svHost.nInstances > 0 || ctx->plan.mediumLean)))) {
-        // (round 6: also for one-level scenes whose media are all lean — k_tr_segment<true> runs at 3 waves (162 VGPRs) where the per-lane kernel is one
-        //  wave of 366 + 110 registers per SIMD: cloud scene 17.3 against 18.5 ms, profiles/r06_transmittance_lean_wavefront_ab_cloud16.txt)
+    // the scene's planned route (ScenePlan::trRoute); a counting pass keeps the reference-order walk
+    const int route = ctx->countTraversal ? 0 : ctx->plan.trRoute;
+    if (route == 2) {
         // the transmittance wavefront (see k_tr_begin)
         LAUNCH("Reset transmittance queues", k_reset, 1, ctx->ws, (1u << CNT_TR0) | (1u << CNT_TR1), -1, 0);
         LAUNCH("Intersect shadow (Tr): begin", k_tr_begin, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws);
         for (int seg = 0; seg < WF_TR_SEGMENTS; ++seg) {
             const int cur = seg & 1;
             LAUNCHT("Intersect shadow (Tr): trace", ctx->walk.trTrace, ctx->walk.grid, ctx->svHost, ctx->ws, ctx->fast, cur, ctx->spillArea());
-            LAUNCH("Intersect shadow (Tr): segment", (ctx->plan.mediumLean ? k_tr_segment<true> : k_tr_segment<false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, cur);
+            LAUNCH("Intersect shadow (Tr): segment", TrSegmentKernel(ctx), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, cur);
             LAUNCH("Reset transmittance queues", k_reset, 1, ctx->ws, 1u << (CNT_TR0 + cur), -1, 0);
         }
-        LAUNCH("Intersect shadow (Tr): rest", k_tr_rest, 128, ctx->svHost, ctx->ws, WF_TR_SEGMENTS & 1, ctx->stackSpill);
-    } else if (ctx->plan.fastOk && !ctx->plan.animFast && !ctx->countTraversal && ctx->svHost.nInstances == 0)  // (the per-lane production walk has no two-level variant)
+        LAUNCH("Intersect shadow (Tr): rest", (ctx->plan.animFast ? k_tr_rest<true> : k_tr_rest<false>), 128, ctx->svHost, ctx->ws, WF_TR_SEGMENTS & 1, ctx->stackSpill);
+    } else if (route == 1)  // (the per-lane production walk has no two-level and no ANIM variant)
         LAUNCHT("Intersect shadow (Tr)", (ctx->svHost.haveAlpha || ctx->svHost.nQuadrics > 0 ? k_shadow_tr_fast<true> : ctx->plan.mediumLean ? k_shadow_tr_fast<false, true> : k_shadow_tr_fast<false>), ctx->walk.grid,
                 ctx->svHost, ctx->ws, ctx->fast, ctx->spillArea());
     else
@@ -2726,17 +2746,38 @@ int wf_trace_any_device(wf_ctx *ctx, int n, const float *rays7, int32_t *occlude
     LAUNCHT("trace any fast (device rays)", ctx->walk.traceAny, ctx->walk.grid, ctx->svHost, ctx->fast, n, rays7, occluded, ctx->spillArea());
     return 0;
 }
-// The transmittance launch of a boundary call over its scratch WorkState `ws` of n items — wf_trace_shadow_tr_host / _host_t and
-// wf_trace_shadow_tr_device choose their kernel HERE, so that the device-buffer call runs what the host-array call of the same
-// timed-ness runs.  timed: the items carry times (ws.pathTime) and the reference-order walk's ANIM variant, the render's kernel for
-// scenes with animated primitives, interpolates at them; otherwise the render's per-lane production walk where it has one (one-level
-// scenes), else the reference-order walk.
-static int LaunchBoundaryTr(wf_ctx *ctx, const WorkState &ws, int n, bool timed, const char *nameTimed, const char *nameUntimed) {
+// The transmittance launch of the HOST-ARRAY boundary calls (wf_trace_shadow_tr_host / _host_t) over their scratch WorkState `ws` of n
+// items: one loop per lane, whatever the scene's plan routes the render through — the independent witness the device-buffer call is
+// compared with.  timed: the items carry times (ws.pathTime) and the reference-order walk's ANIM variant interpolates at them;
+// otherwise the per-lane production walk where there is one (one-level scenes), else the reference-order walk.
+static int LaunchHostTr(wf_ctx *ctx, const WorkState &ws, int n, bool timed) {
     if (timed) {
-        LAUNCH(nameTimed, k_shadow_tr<true>, gridFor(n), ctx->svHost, ws, ctx->stackSpill);
+        LAUNCH("shadow Tr (host rays, timed)", k_shadow_tr<true>, gridFor(n), ctx->svHost, ws, ctx->stackSpill);
     } else if (ctx->plan.fastOk && ctx->svHost.nInstances == 0) {
-        LAUNCHT(nameUntimed, (ctx->svHost.haveAlpha || ctx->svHost.nQuadrics > 0 ? k_shadow_tr_fast<true> : k_shadow_tr_fast<false>), ctx->walk.grid, ctx->svHost, ws, ctx->fast, ctx->spillArea());
-    } else LAUNCH(nameUntimed, k_shadow_tr<false>, gridFor(n), ctx->svHost, ws, ctx->stackSpill);
+        LAUNCHT("shadow Tr (host rays)", (ctx->svHost.haveAlpha || ctx->svHost.nQuadrics > 0 ? k_shadow_tr_fast<true> : k_shadow_tr_fast<false>), ctx->walk.grid, ctx->svHost, ws, ctx->fast, ctx->spillArea());
+    } else LAUNCH("shadow Tr (host rays)", k_shadow_tr<false>, gridFor(n), ctx->svHost, ws, ctx->stackSpill);
+    return 0;
+}
+// ... and of the DEVICE-BUFFER call (wf_trace_shadow_tr_device): the scene's planned route (ScenePlan::trRoute), with the kernels and
+// the launch sequence of the render's own stage (wf_intersect_shadow_tr), over the call's scratch WorkState.  timed: the scene has
+// animated primitives and the items carry times (ws.pathTime).
+static int LaunchDeviceTr(wf_ctx *ctx, const WorkState &ws, int n, bool timed) {
+    if (ctx->plan.trRoute == 2) {
+        LAUNCH("shadow Tr (device rays): reset", k_reset, 1, ws, (1u << CNT_TR0) | (1u << CNT_TR1), -1, 0);
+        LAUNCH("shadow Tr (device rays): begin", k_tr_begin, gridFor(n), ctx->svHost, ws);
+        for (int seg = 0; seg < WF_TR_SEGMENTS; ++seg) {
+            const int cur = seg & 1;
+            LAUNCHT("shadow Tr (device rays): trace", ctx->walk.trTrace, ctx->walk.grid, ctx->svHost, ws, ctx->fast, cur, ctx->spillArea());
+            LAUNCH("shadow Tr (device rays): segment", TrSegmentKernel(ctx), gridFor(n), ctx->svHost, ws, cur);
+            LAUNCH("shadow Tr (device rays): reset", k_reset, 1, ws, 1u << (CNT_TR0 + cur), -1, 0);
+        }
+        LAUNCH("shadow Tr (device rays): rest", (ctx->plan.animFast ? k_tr_rest<true> : k_tr_rest<false>), 128, ctx->svHost, ws, WF_TR_SEGMENTS & 1, ctx->stackSpill);
+    } else if (ctx->plan.trRoute == 1) {
+        LAUNCHT("shadow Tr (device rays)", (ctx->svHost.haveAlpha || ctx->svHost.nQuadrics > 0 ? k_shadow_tr_fast<true> : ctx->plan.mediumLean ? k_shadow_tr_fast<false, true> : k_shadow_tr_fast<false>), ctx->walk.grid,
+                ctx->svHost, ws, ctx->fast, ctx->spillArea());
+    } else if (timed) {
+        LAUNCH("shadow Tr (device rays, timed)", k_shadow_tr<true>, gridFor(n), ctx->svHost, ws, ctx->stackSpill);
+    } else LAUNCH("shadow Tr (device rays)", k_shadow_tr<false>, gridFor(n), ctx->svHost, ws, ctx->stackSpill);
     return 0;
 }
 // The two calls above with the rays' TIMES (rays8), on any scene: the walk is chosen by what the scene is.
@@ -2776,25 +2817,25 @@ int wf_trace_any_device_t(wf_ctx *ctx, int n, const float *rays8, int32_t *occlu
     if (ctx && n > 0 && !occluded) return fail(-1, "wf_trace_any_device_t: null occluded");
     return TraceDeviceTimed(ctx, "wf_trace_any_device_t", n, rays8, nullptr, occluded);
 }
-// room for n items in ctx->trScratch.  Growth waits for the launches that still read the old arrays; a call that fits allocates and
-// waits for nothing.
+// room for n items in ctx->trScratch, the wavefront's arrays among them if the scene's plan routes through it.  Growth waits for the
+// launches that still read the old arrays; a call that fits allocates and waits for nothing.
 static int GrowTrScratch(wf_ctx *ctx, size_t n) {
     wf_ctx::TrScratch &t = ctx->trScratch;
     if (!t.counters) {
         HIPCHK(hipMalloc((void **)&t.counters, (size_t)CNT_COUNT * CNT_STRIDE * sizeof(int32_t)));
         HIPCHK(hipMemsetAsync(t.counters, 0, (size_t)CNT_COUNT * CNT_STRIDE * sizeof(int32_t), ctx->stream));
     }
-    if (n <= t.capacity) return 0;
-    const size_t cap = std::max(n, 2 * t.capacity);
+    const bool wavefront = ctx->plan.trRoute == 2;
+    if (n <= t.capacity && (!wavefront || t.trO)) return 0;
+    const size_t cap = n > t.capacity ? std::max(n, 2 * t.capacity) : t.capacity;
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    for (void *p : {(void *)t.o, (void *)t.d, (void *)t.lambdaPdf, (void *)t.pathTime}) if (p) HIPCHK(hipFree(p));
-    t.o = t.d = t.lambdaPdf = nullptr;
-    t.pathTime = nullptr;
+    for (const wf_ctx::TrScratch::Slot &sl : t.slots()) {
+        if (*sl.p) HIPCHK(hipFree(*sl.p));
+        *sl.p = nullptr;
+    }
     t.capacity = 0;
-    HIPCHK(hipMalloc((void **)&t.o, cap * sizeof(F4)));
-    HIPCHK(hipMalloc((void **)&t.d, cap * sizeof(F4)));
-    HIPCHK(hipMalloc((void **)&t.lambdaPdf, cap * sizeof(F4)));
-    HIPCHK(hipMalloc((void **)&t.pathTime, cap * sizeof(float)));
+    for (const wf_ctx::TrScratch::Slot &sl : t.slots())
+        if (!sl.wavefront || wavefront) HIPCHK(hipMalloc(sl.p, cap * sl.elem));
     t.capacity = cap;
     return 0;
 }
@@ -2814,7 +2855,7 @@ int wf_trace_shadow_tr_device(wf_ctx *ctx, int n, const float *rays8, const int3
     useDevice(ctx);
     if (int e = GrowTrScratch(ctx, (size_t)n)) return e;
     const wf_ctx::TrScratch &t = ctx->trScratch;
-    const bool timed = ctx->svHost.haveAnimated;   // (a static scene's items need no times: the untimed host-array call's kernel)
+    const bool timed = ctx->svHost.haveAnimated;   // (a static scene's items need no times)
     WorkState ws = ctx->ws;   // counters / stats of the context, every per-item array replaced below (the kernels only read the caller's inputs)
     ws.sq.o = t.o; ws.sq.d = t.d; ws.lambdaPdf = t.lambdaPdf;
     ws.sq.Ld = (F4 *)Ld; ws.sq.r_u = (F4 *)r_u; ws.sq.r_l = (F4 *)r_l; ws.sq.medium = (int32_t *)medium;
@@ -2822,8 +2863,11 @@ int wf_trace_shadow_tr_device(wf_ctx *ctx, int n, const float *rays8, const int3
     ws.L = (F4 *)out_L;
     ws.counters = t.counters;
     if (timed) ws.pathTime = t.pathTime;
+    // (the wavefront's state, queues and hit records: null on the other routes, whose kernels touch none of them)
+    ws.trO = t.trO; ws.trD = t.trD; ws.trT = t.trT; ws.trRu = t.trRu; ws.trRl = t.trRl; ws.trRng = t.trRng;
+    ws.trQ[0] = t.trQ[0]; ws.trQ[1] = t.trQ[1]; ws.hit = t.hit; ws.hitInst = t.hitInst;
     LAUNCH("shadow Tr (device rays): pack items", k_pack_shadow_items, gridFor(n), n, rays8, t.o, t.d, t.lambdaPdf, timed ? t.pathTime : (float *)nullptr, (F4 *)out_L, t.counters);
-    return LaunchBoundaryTr(ctx, ws, n, timed, "shadow Tr (device rays, timed)", "shadow Tr (device rays)");
+    return LaunchDeviceTr(ctx, ws, n, timed);
 }
 // IntersectOneRandom on the caller's device segments {p0, p1, time}: the kernel of the host-array calls, at the segments' times on a
 // scene with animated primitives
@@ -2909,7 +2953,7 @@ static int TraceShadowTrHost(wf_ctx *ctx, const char *fn, int n, const float *o,
     HIPCHK(hipMemcpyAsync(cnt + CNT_SHADOW * CNT_STRIDE, &n, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     ws.counters = cnt;
     if (time && (e = tmp.upload(&ws.pathTime, time, N))) return e;
-    if ((e = LaunchBoundaryTr(ctx, ws, n, time != nullptr, "shadow Tr (host rays, timed)", "shadow Tr (host rays)"))) return e;
+    if ((e = LaunchHostTr(ctx, ws, n, time != nullptr))) return e;
     HIPCHK(hipMemcpyAsync(out_L, ws.L, n * sizeof(F4), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return 0;

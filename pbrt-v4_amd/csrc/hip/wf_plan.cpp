@@ -286,6 +286,14 @@ int wf::planning::PlanScene(const wf_scene_desc *d, const Switches &sw, ScenePla
     // reference-order walks (WF_ANIM_FAST=0: every animated scene does)
     plan->animFast = d->n_animated > 0 && plan->fastOk && plan->genMode <= 1 && plan->nInstances > 0 && sw.animFast;
     if (d->n_animated > 0 && !plan->animFast) plan->fastOk = false;
+    // Step 5: the transmittance stage's route (ScenePlan::trRoute).  The wavefront walks with k_tr_trace, which exists for the variants
+    // that resolve their near ties inside the walk, static and ANIM; the per-lane production walk has neither a two-level nor an ANIM variant.
+    if (d->have_media) {   // (what SceneView::haveMedia is: the scenes whose shadow stage is IntersectShadowTr)
+        const bool wavefront = sw.trWavefront == 1 || (sw.trWavefront < 0 && (plan->nInstances > 0 || plan->mediumLean));
+        if (plan->fastOk && RetraceInline(plan->genMode) && wavefront) plan->trRoute = 2;
+        else if (plan->fastOk && !plan->animFast && plan->nInstances == 0) plan->trRoute = 1;
+        else plan->trRoute = 0;
+    }
     return 0;
 }
 // The answers of wf_ctx_query / wf_scene_plan_query that the plan alone gives; false: not one of its keys.
@@ -302,6 +310,7 @@ bool wf::planning::PlanValue(const ScenePlan &plan, const char *key, int64_t *va
     else if (k.rfind("lean_type_", 0) == 0 && atoi(key + 10) >= 0 && atoi(key + 10) < WF_MAT_NTYPES) *value = plan.leanType[atoi(key + 10)];
     else if (k == "instances") *value = plan.nInstances;
     else if (k == "nested_animated") *value = plan.nestedAnimated;
+    else if (k == "tr_route") *value = plan.trRoute;   // -1 no media, 0 k_shadow_tr, 1 k_shadow_tr_fast, 2 the transmittance wavefront
     else return false;
     return true;
 }

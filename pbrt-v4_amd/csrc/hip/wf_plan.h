@@ -29,7 +29,7 @@ struct Switches {
     bool animFast = true;         // WF_ANIM_FAST=0
     bool pixelMajor = true;       // WF_PIXEL_MAJOR=0: items of a pass ordered sample by sample
     bool noSampleTops = false;    // WF_NO_SAMPLE_TOPS (set to anything)
-    int trWavefront = -1;         // WF_TR_WAVEFRONT (wf_ctx::trWavefront)
+    int trWavefront = -1;         // WF_TR_WAVEFRONT=1 | 0 forces / forbids the transmittance wavefront; -1 (unset): by the scene (ScenePlan::trRoute)
     int frameOverlap = 1;         // WF_FRAME_OVERLAP: 0 | 1 | 2 (wf_ctx::frameOverlap)
     bool samplesShaded = true;    // WF_SAMPLES_SHADED=0
     bool traceLaunch = false;     // WF_TRACE_LAUNCH (set to anything)
@@ -100,7 +100,19 @@ struct ScenePlan {
                                  // any-hit 12.15 at 1, 12.16 at 3, 12.4 at 4, 13.0 at 8: profiles/r06_cursor_chunk_ab_sm16.txt)
                                  // (-3 %), but on a 30 k-triangle scene one fetch per 64 rays is 83 atomics/us on one counter: the kernel's bound
     int spillRows = 0;           // rows of wf_ctx::stackSpill behind the LDS stack entries, from the trees' depths
+    // The transmittance stage (IntersectShadowTr) of the render and of wf_trace_shadow_tr_device: -1 the scene has no media, 0 the
+    // reference-order walk per lane (k_shadow_tr), 1 the per-lane production walk (k_shadow_tr_fast: one-level static scenes), 2 the
+    // transmittance wavefront (k_tr_begin / k_tr_trace / k_tr_segment / k_tr_rest).  WF_TR_WAVEFRONT: -1 (unset) = the wavefront for
+    // two-level scenes and for scenes whose media are all lean, 1 = wherever its walk exists, 0 = never.  Measured on the cloud-like spec
+    // scene (14 triangles, 512^3 grid, round 3): per-lane loop 27.9 ms per 16 spp, wavefront 31.4 ms (begin
+    // 3.3 + trace 3.7 + segment 24.1 + rest 0.3) — the time is the ratio tracking through the grid, not the walk, and the per-lane loop
+    // keeps its state in registers; with object instances the per-lane alternative is the reference-order walk (1 wave / SIMD).  Round 6,
+    // one-level scenes whose media are all lean: k_tr_segment<true> runs at 3 waves (162 VGPRs) where the per-lane kernel is one wave of
+    // 366 + 110 registers per SIMD — cloud scene 17.3 against 18.5 ms, profiles/r06_transmittance_lean_wavefront_ab_cloud16.txt.
+    int trRoute = -1;
 };
+// which walk kernel variants resolve their near ties themselves (the others mark them for a re-trace launch)
+constexpr bool RetraceInline(int gen) { return gen <= 1; }
 // The production traversal layout as BuildFastBVH leaves it on the host: what the upload copies once PlanScene has succeeded.
 struct FastTrees {
     std::vector<QNode> nodes;

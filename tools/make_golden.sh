@@ -175,3 +175,5 @@ oracle/_ref/pbrt_ref --wavefront --quiet --seed 0 --spp 4 --outfile $G/animated_
 oracle/_ref/pbrt_ref --wavefront --quiet --seed 0 --spp 4 --outfile $G/animated_in_definition_media_ref.pfm $G/animated_in_definition_media.pbrt
 oracle/_ref/pbrt_ref --wavefront --quiet --seed 0 --spp 4 --outfile $G/animated_in_definition_sss_ref.pfm $G/animated_in_definition_sss.pbrt
 oracle/_ref/pbrt_ref --wavefront --quiet --seed 0 --spp 4 --outfile $G/face_indices_ref.pfm $G/face_indices.pbrt
+# the transmittance wavefront's ANIM variants (hand-written: a moving interface box in an RGB grid, a moving alpha cut-out, the louvres; reads checker01.pfm)
+oracle/_ref/pbrt_ref --wavefront --quiet --seed 0 --spp 4 --outfile $G/animated_tr_routes_ref.pfm $G/animated_tr_routes.pbrt
