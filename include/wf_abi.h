@@ -710,6 +710,21 @@ int wf_film_copy_to_device(wf_ctx *ctx, void *dst_device);         /* D2D, wf_fi
 int wf_film_gather_strips(wf_ctx *dst, wf_ctx *src);
 int wf_stats_add(wf_ctx *dst, wf_ctx *src);
 int wf_film_copy_from_device(wf_ctx *ctx, const void *src_device);
+/* The mirrors of the two downloads above (checkpoint / restore of a spectral or GBuffer film; with wf_film_upload for the RGB sums) */
+int wf_film_spectral_upload(wf_ctx *ctx, const double *src /* [H][W][2 * n_buckets] */);
+int wf_film_gbuffer_upload(wf_ctx *ctx, const wf_gbuffer_pixel *src /* [H][W] */);
+/* The film's GetImage step on the device (RGBFilm / SpectralFilm / GBufferFilm::GetImage, film.cpp): from the accumulators to the
+   final image in a caller-owned DEVICE buffer, float32 [H][W][C] contiguous, H x W the film's pixel bounds.  *n = C: 3 (RGB film),
+   3 + n_buckets (spectral: R G B then the buckets) or 25 (GBuffer, the channel order of wfh_film_channels).  dst_floats must be
+   H * W * C.  save_fp16 != 0 stores what a half image holds (clamped to 65504 where the film clamps, rounded to nearest even).  The
+   kernel is launched on the context's stream behind whatever the render left there.  nan_values == NULL: no host synchronisation, like
+   wf_trace_*_device (wf_sync, or any synchronising call, before another stream reads dst).  nan_values != NULL: the call synchronises
+   and returns the number of channel values that were NaN and were stored as 0.  wf_film_develop_rgb_device develops the three RGB
+   channels whatever the film's type (dst_floats = H * W * 3).  A strip-partitioned context (wf_set_strips) develops its whole film:
+   the lines it does not own are zeros, as in its download. */
+int wf_film_channel_count(wf_ctx *ctx, int *n);
+int wf_film_develop_device(wf_ctx *ctx, float *dst_device, uint64_t dst_floats, int save_fp16, uint64_t *nan_values);
+int wf_film_develop_rgb_device(wf_ctx *ctx, float *dst_device, uint64_t dst_floats, int save_fp16, uint64_t *nan_values);
 int wf_stats_download(wf_ctx *ctx, wf_render_stats *out);
 int wf_profile_report(wf_ctx *ctx, wf_kernel_profile_entry *entries, int max_entries, int *n_out);
 /* per-launch hipEvent pairs on the context's stream (gpu/util.cpp:136-209): 0 off, 1 every launch,

@@ -65,6 +65,12 @@ int wfh_read_image(const char *path, const char *encoding, int32_t *width, int32
    wfh_write_film_image writes the scene's film — whatever its type — to `path` (.pfm / .exr for RGB films, .exr for the others). */
 int wfh_film_channels(wfh_scene *s, int32_t *n_channels, char *names, float *pixels);
 int wfh_write_film_image(wfh_scene *s, const char *path);
+/* The same image developed on the device (wf_film_develop_device / wf_film_develop_rgb_device, include/wf_abi.h) with the scene's
+   saveFP16: dst_device = n_floats = height * width * C floats of DEVICE memory, C = 3 when rgb_only (RGBFilm::GetImage of the RGB
+   accumulators, whatever the film: what wfh_film_to_rgb does on the host), else the film's own channel count (3 for an RGB film;
+   the names come from wfh_film_channels).  nan_values as in the ABI: NULL = launched on the context's stream without
+   synchronisation, else the call synchronises and stores the number of NaN values written as 0.  0, or -1 with wfh_last_error(). */
+int wfh_film_image_device(wfh_scene *s, float *dst_device, uint64_t n_floats, int rgb_only, uint64_t *nan_values);
 /* The NanoVDB reader of the "nanovdb" medium (csrc/host/nanovdb_io.cpp; parity unpinned: third-party format), for tools and tests:
    the float grid `grid_name` of `path` expanded over its index bounding box.  min / dim = origin and size of the block, inv_mat (9) and
    vec (3) = the grid's index-from-world map (index = inv_mat * (p - vec)), background; values = dim[0] * dim[1] * dim[2] floats (x

@@ -39,6 +39,7 @@
 #pragma clang attribute pop
 #include "wf_traverse.h"
 #include "wf_plan.h"
+#include "wf_film_develop.h"
 
 using namespace wf;
 using namespace wf::planning;
@@ -141,6 +142,7 @@ struct wf_ctx {
         }
     } trScratch;
     int32_t *probeCursor = nullptr;
+    unsigned long long *developNaN = nullptr;   // wf_film_develop_*_device's NaN counter (allocated by the first call that asks for the count)
     int W = 0, H = 0;
     int maxDepth = 5;
     float sceneBounds[6] = {};
@@ -2585,6 +2587,70 @@ int wf_film_copy_from_device(wf_ctx *ctx, const void *src_device) {
     HIPCHK(hipMemcpyAsync(ctx->ws.film, src_device, (size_t)ctx->W * ctx->H * 4 * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return 0;
+}
+// The mirrors of the two downloads above: checkpoint / restore of a spectral or GBuffer film
+int wf_film_spectral_upload(wf_ctx *ctx, const double *src) {
+    if (!ctx || !ctx->sceneLoaded) return fail(-1, "no scene uploaded");
+    useDevice(ctx);
+    if (!ctx->ws.filmSpectral) return fail(-1, "wf_film_spectral_upload: the scene's film is not a spectral film");
+    if (!src) return fail(-1, "wf_film_spectral_upload: null argument");
+    HIPCHK(hipMemcpyAsync(ctx->ws.filmSpectral, src, (size_t)ctx->W * ctx->H * 2 * ctx->svHost.film.n_buckets * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+int wf_film_gbuffer_upload(wf_ctx *ctx, const wf_gbuffer_pixel *src) {
+    if (!ctx || !ctx->sceneLoaded) return fail(-1, "no scene uploaded");
+    useDevice(ctx);
+    if (!ctx->ws.filmGBuffer) return fail(-1, "wf_film_gbuffer_upload: the scene's film is not a gbuffer film");
+    if (!src) return fail(-1, "wf_film_gbuffer_upload: null argument");
+    HIPCHK(hipMemcpyAsync(ctx->ws.filmGBuffer, src, (size_t)ctx->W * ctx->H * sizeof(wf_gbuffer_pixel), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+// The film's GetImage step on the device (kernels and launchers: wf_film_develop.hip)
+static int FilmChannelCount(const wf_ctx *ctx) {
+    return ctx->ws.filmSpectral ? 3 + ctx->svHost.film.n_buckets : ctx->ws.filmGBuffer ? develop::GBUFFER_CHANNELS : 3;
+}
+int wf_film_channel_count(wf_ctx *ctx, int *n) {
+    if (!ctx || !n) return fail(-1, "wf_film_channel_count: null argument");
+    if (!ctx->sceneLoaded) return fail(-1, "no scene uploaded");
+    *n = FilmChannelCount(ctx);
+    return 0;
+}
+static int FilmDevelop(wf_ctx *ctx, const char *what, bool rgbOnly, float *dst, uint64_t dstFloats, int saveFP16, uint64_t *nanValues) {
+    if (!ctx || !dst) return fail(-1, "%s: null argument", what);
+    if (!ctx->sceneLoaded) return fail(-1, "no scene uploaded");
+    useDevice(ctx);
+    const size_t pixels = (size_t)ctx->W * ctx->H;
+    const int nc = rgbOnly ? 3 : FilmChannelCount(ctx);
+    if (dstFloats != (uint64_t)pixels * nc)
+        return fail(-1, "%s: dst_floats is %llu, the image holds %d x %d x %d = %llu floats", what, (unsigned long long)dstFloats, ctx->H, ctx->W, nc,
+                    (unsigned long long)((uint64_t)pixels * nc));
+    if (nanValues) {
+        if (!ctx->developNaN) { if (int e = devAlloc(ctx, &ctx->developNaN, (size_t)1)) return e; }
+        HIPCHK(hipMemsetAsync(ctx->developNaN, 0, sizeof(unsigned long long), ctx->stream));
+    }
+    unsigned long long *counter = nanValues ? ctx->developNaN : nullptr;
+    const wf_film &F = ctx->svHost.film;
+    int e;
+    if (!rgbOnly && ctx->ws.filmSpectral) e = develop::LaunchDevelopSpectral(ctx->stream, ctx->ws.film, ctx->ws.filmSpectral, pixels, F, saveFP16 != 0, dst, counter);
+    else if (!rgbOnly && ctx->ws.filmGBuffer) e = develop::LaunchDevelopGBuffer(ctx->stream, ctx->ws.film, ctx->ws.filmGBuffer, pixels, F, saveFP16 != 0, dst, counter);
+    else e = develop::LaunchDevelopRGB(ctx->stream, ctx->ws.film, pixels, F, saveFP16 != 0, dst, counter);
+    if (e) return fail(e, "%s: the launch failed: %s", what, hipGetErrorString((hipError_t)e));
+    if (nanValues) {
+        unsigned long long count = 0;
+        HIPCHK(hipMemcpyAsync(&count, ctx->developNaN, sizeof(count), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        *nanValues = count;
+    }
+    return 0;
+}
+int wf_film_develop_device(wf_ctx *ctx, float *dst_device, uint64_t dst_floats, int save_fp16, uint64_t *nan_values) {
+    return FilmDevelop(ctx, "wf_film_develop_device", false, dst_device, dst_floats, save_fp16, nan_values);
+}
+int wf_film_develop_rgb_device(wf_ctx *ctx, float *dst_device, uint64_t dst_floats, int save_fp16, uint64_t *nan_values) {
+    return FilmDevelop(ctx, "wf_film_develop_rgb_device", true, dst_device, dst_floats, save_fp16, nan_values);
 }
 // The gather of a strip-partitioned render (wf_set_strips) without a host round trip or a collective: the scanline strips `src` owns
 // are copied from its film into `dst`'s film — peer to peer over xGMI when the contexts sit on different devices, device to device on

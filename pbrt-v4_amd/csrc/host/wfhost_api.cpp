@@ -148,7 +148,10 @@ int wfh_film_channels(wfh_scene *s, int32_t *n_channels, char *names, float *pix
         if (!names && !pixels) return 0;
         std::vector<std::string> nm;
         std::vector<float> chans;
-        FilmChannels(s, &nm, &chans);
+        if (pixels) FilmChannels(s, &nm, &chans);
+        // the names alone (the device path's, wfh_film_image_device): the same loops over an image of no pixels, nothing downloaded
+        else if (F.type == WF_FILM_SPECTRAL) SpectralFilmImage(F, nullptr, nullptr, 0, 0, s->T.saveFP16, &nm, &chans);
+        else GBufferFilmImage(F, nullptr, nullptr, 0, 0, s->T.saveFP16, &nm, &chans);
         if (names) for (size_t i = 0; i < nm.size(); ++i) snprintf(names + 32 * i, 32, "%s", nm[i].c_str());
         if (pixels) memcpy(pixels, chans.data(), chans.size() * sizeof(float));
         return 0;
@@ -170,6 +173,16 @@ int wfh_write_film_image(wfh_scene *s, const char *path) {
         std::vector<float> rgb((size_t)W * H * 3);
         FilmToRGB(F, film.data(), W, H, rgb.data(), s->T.saveFP16);
         return WriteFilmImage(s->T, path, rgb, W, H) ? 0 : -1;
+    });
+}
+int wfh_film_image_device(wfh_scene *s, float *dst_device, uint64_t n_floats, int rgb_only, uint64_t *nan_values) {
+    return Guard<int>(-1, [&] {
+        if (!s || !s->renderer) throw SceneError("wfh_film_image_device: the scene has no renderer");
+        wf_ctx *ctx = s->renderer->Context();
+        const int save = s->T.saveFP16 ? 1 : 0;
+        const int rc = rgb_only ? wf_film_develop_rgb_device(ctx, dst_device, n_floats, save, nan_values) : wf_film_develop_device(ctx, dst_device, n_floats, save, nan_values);
+        if (rc != 0) throw SceneError(wf_last_error());
+        return 0;
     });
 }
 int wfh_read_nanovdb(const char *path, const char *grid_name, int32_t min[3], int32_t dim[3], float inv_mat[9], float vec[3], float *background, float *values) {

@@ -74,11 +74,13 @@ ABI_SYMBOLS = [
     "wf_trace_closest_device", "wf_trace_any_device", "wf_device_alloc", "wf_device_free", "wf_device_upload", "wf_device_download", "wf_trace_shadow_tr_host",
     "wf_trace_shadow_tr_host_t", "wf_trace_one_random_host_t",
     "wf_trace_closest_device_t", "wf_trace_any_device_t", "wf_trace_shadow_tr_device", "wf_trace_one_random_device",
+    "wf_film_spectral_upload", "wf_film_gbuffer_upload", "wf_film_channel_count", "wf_film_develop_device", "wf_film_develop_rgb_device",
 ]
 HOST_SYMBOLS = [
     "wfh_init", "wfh_last_error", "wfh_scene_load", "wfh_scene_load_string", "wfh_scene_free", "wfh_scene_desc", "wfh_scene_info",
     "wfh_renderer_create", "wfh_renderer_create_strips", "wfh_renderer_set_strips", "wfh_renderer_samples_per_pass", "wfh_renderer_ctx", "wfh_render", "wfh_clear_film", "wfh_download_film", "wfh_stats",
     "wfh_film_to_rgb", "wfh_write_image", "wfh_read_image", "wfh_read_nanovdb", "wfh_build_bvh_host", "wfh_film_channels", "wfh_write_film_image",
+    "wfh_film_image_device",
 ]
 
 _hip = None
@@ -141,6 +143,12 @@ def libs():
     _hip.wf_kernel_time_ms.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]
     _hip.wf_aggregate_bounds.argtypes = [C.c_void_p, C.c_void_p]
     _hip.wf_render_pass.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    _hip.wf_film_channel_count.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+    for f in (_hip.wf_film_develop_device, _hip.wf_film_develop_rgb_device):
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]
+    for name in ("wf_film_upload", "wf_film_spectral_upload", "wf_film_gbuffer_upload", "wf_film_spectral_download", "wf_film_gbuffer_download"):
+        getattr(_hip, name).argtypes = [C.c_void_p, C.c_void_p]
+    _host.wfh_film_image_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]
     if _host.wfh_init(DATA.encode()) != 0:
         raise WfError("wfh_init failed (data dir %s)" % DATA)
     return _host, _hip
@@ -193,6 +201,8 @@ class Scene:
         if rc != 0:
             raise WfError("renderer creation failed: " + (host.wfh_last_error() or b"").decode(errors="replace"))
         self._renderer = True
+        self.device = device
+        self.nan_values = 0   # NaN channel values the last image_tensor() / film_channels_tensor() stored as 0
         self.samples_per_pass = host.wfh_renderer_samples_per_pass(self.h)
         self.ctx = host.wfh_renderer_ctx(self.h)
         return self
@@ -546,6 +556,50 @@ class Scene:
         hip.wf_debug_counters.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
         _check(hip.wf_debug_counters(self.ctx, out, 1 if reset else 0), "wf_debug_counters")
         return {"spilled_entries": int(out[0]), "overflow": int(out[1]), "inline_retraces": int(out[2]), "cursor": int(out[3])}
+
+    # ---- the film developed on the device (wf_film_develop_device): the image as a torch tensor, no host round trip ----
+    def _develop(self, what, rgb_only, channels, out):
+        import torch
+        host, hip = libs()
+        dev = torch.device("cuda", self.device)
+        shape = (self.info.height, self.info.width, channels)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=dev)
+        elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != dev:
+            raise WfError("%s: out is a contiguous float32 tensor of shape %s on %s" % (what, list(shape), dev))
+        # the kernel runs on the context's stream (wf_stream), behind the render and behind whatever torch's stream still does with `out`
+        torch.cuda.ExternalStream(hip.wf_stream(self.ctx), device=dev).wait_stream(torch.cuda.current_stream(dev))
+        nan = C.c_uint64(0)
+        if host.wfh_film_image_device(self.h, out.data_ptr(), out.numel(), 1 if rgb_only else 0, C.byref(nan)) != 0:
+            raise WfError("%s failed: %s" % (what, host.wfh_last_error().decode(errors="replace")))
+        _check(hip.wf_sync(self.ctx), "wf_sync")   # torch's stream is not the context's: the image is complete when the call returns
+        self.nan_values = int(nan.value)
+        return out
+
+    def image_tensor(self, out=None):
+        """image() developed on the device: a float32 [H, W, 3] torch tensor on the renderer's device, bit-identical with image().
+        out: a tensor to write into instead of a new one.  Sets self.nan_values (NaN values stored as 0)."""
+        if not self._renderer:
+            raise WfError("image_tensor: create_renderer() first")
+        return self._develop("image_tensor", True, 3, out)
+
+    def film_channels_tensor(self, out=None):
+        """film_channels() developed on the device: (channel names, float32 [H, W, C] torch tensor on the renderer's device), bit-identical
+        with film_channels(); (["R", "G", "B"], image_tensor()) for an RGB film.  Sets self.nan_values."""
+        if not self._renderer:
+            raise WfError("film_channels_tensor: create_renderer() first")
+        host, hip = libs()
+        nc = C.c_int(0)
+        _check(hip.wf_film_channel_count(self.ctx, C.byref(nc)), "wf_film_channel_count")
+        if nc.value == 3:   # an RGB film (wfh_film_channels names the channels of the other two)
+            return ["R", "G", "B"], self._develop("film_channels_tensor", False, 3, out)
+        host.wfh_film_channels.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_char_p, C.c_void_p]
+        names = C.create_string_buffer(32 * nc.value)
+        n32 = C.c_int32(0)
+        if host.wfh_film_channels(self.h, C.byref(n32), names, None) != 0 or n32.value != nc.value:
+            raise WfError("film_channels_tensor: " + host.wfh_last_error().decode(errors="replace"))
+        return ([names.raw[32 * i:32 * (i + 1)].split(b"\0")[0].decode() for i in range(nc.value)],
+                self._develop("film_channels_tensor", False, nc.value, out))
 
     def film_to_tensor(self, tensor):
         """device-to-device copy of the film accumulators into a torch CUDA float64 tensor (for the RCCL reduce)"""
