@@ -776,6 +776,35 @@ int wf_trace_shadow_tr_device(wf_ctx *ctx, int n, const float *rays8, const int3
    floats; material[n]; out[n]; reservoir_pdf[n]; all device pointers.  Any scene (a static one ignores the time).  Not synchronised. */
 int wf_trace_one_random_device(wf_ctx *ctx, int n, const float *segs7, const int32_t *material,
                                wf_hit_record *out, float *reservoir_pdf);
+/* From a hit record to the SurfaceInteraction the reference's aggregate answers IntersectClosest with (what EnqueueWorkAfterIntersection
+   copies into a MaterialEvalWorkItem, wavefront/intersect.h:72-162), on DEVICE buffers: rays8 = the n rays that found the hits, in the
+   layout of wf_trace_closest_device_t (o, d, tMax, time — the ray matters for wo, for the time of an animated transformation and for a
+   curve's ray-aligned frame); hits = their n records.  Every pointer is a device pointer of the context's device aligned to 16 bytes.
+   The output is plane-major: item i of plane p is the 16 bytes at out[(p * n + i) * 4].
+     out_f  plane 0  pi lower bounds | uv[0]        1  pi upper bounds | uv[1]      2  n | the ray's time     3  ns | t of the record
+            4  wo | 0      5, 6  dpdu, dpdv | 0      7, 8  shading dpdu, dpdv | 0     9, 10  shading dndu, dndv | 0
+     out_i  plane 0  material (-1: an interface surface; a MixMaterial's own id, unresolved), area light (-1: none), medium inside, medium outside
+            plane 1  mesh, valid, the mesh's WF_MESH_* flags, 0
+   valid = 1: a hit.  0: a miss (prim < 0) — ids -1, every other word 0.  -1: a record whose prim or instance lies outside the scene's
+   ranges, written like a miss (a stale buffer does not walk the tables).  The kernel variant is the scene's ("intr_variant",
+   wf_ctx_query).  Launched on the context's stream (wf_stream) and NOT synchronised; the arguments are checked before anything is
+   launched; n <= 0 touches nothing.  Needs an uploaded scene, no queues. */
+#define WF_INTR_FPLANES 11
+#define WF_INTR_IPLANES 2
+int wf_hit_interaction_device(wf_ctx *ctx, int n, const float *rays8, const wf_hit_record *hits,
+                              float *out_f /* [WF_INTR_FPLANES][n][4] */, int32_t *out_i /* [WF_INTR_IPLANES][n][4] */);
+/* The scene's own camera rays on DEVICE buffers: runs "Generate camera rays" (wf_gen_camera_rays) for the band of scanlines at y0 and ONE
+   sample index into the context's ray queue 0, then copies the queue out: rays8[i] = (o, d, tMax = infinity, time), pixel_xy[i] = the
+   ray's pixel, lambda4[i] = its four wavelengths, *n_out_device = the number of rays (a realistic camera generates fewer rays than
+   pixels, in no fixed order).  n_max = the capacity of the three arrays in rays: at least the band's pixels (pixels_per_pass of
+   wf_queues_alloc), else an argument error.  rays8 and lambda4 are aligned to 16 bytes, pixel_xy to 8, n_out_device to 4; all device
+   pointers.  Needs allocated queues, and OVERWRITES the render's per-pass state (ray queue 0, the pixel sample state, the sampler's
+   per-pixel index prefixes): a call for an idle context, not for one with a render in flight.  The host-side pass settings
+   (wf_set_pass_samples, the band of the last wf_gen_camera_rays) are left as they were, and the rays are not counted in
+   wf_render_stats.camera_rays.  Launched on the context's stream and NOT synchronised.  The camera-ray and
+   filter weights are not handed out, and there is no call that adds a caller's radiance to the film. */
+int wf_camera_rays_device(wf_ctx *ctx, int y0, int sample_index, int n_max,
+                          float *rays8, int32_t *pixel_xy /* [n_max][2] */, float *lambda4 /* [n_max][4] */, int32_t *n_out_device);
 int wf_device_alloc(wf_ctx *ctx, uint64_t nbytes, void **dptr);
 int wf_device_free(wf_ctx *ctx, void *dptr);
 int wf_device_upload(wf_ctx *ctx, void *dst_device, const void *src_host, uint64_t nbytes);
@@ -852,7 +881,10 @@ int wf_debug_counters(wf_ctx *ctx, uint64_t out[4], int reset);
    traversal), "anim_fast" (AnimatedPrimitives on the production walk), "lean_shade", "lean_type_<material type>", "rare_lights", "medium_lean" (the lean delta-tracking / transmittance kernels),
    "instances", "nested_animated" (records of `instances` that are nested placements: animated shapes inside instance definitions, per use),
    "tr_route" (the transmittance stage of the render and of wf_trace_shadow_tr_device: -1 the scene has no media, 0 the reference-order
-   walk per lane, 1 the per-lane production walk, 2 the transmittance wavefront; WF_TR_WAVEFRONT=1 | 0 at upload forces / forbids the last).
+   walk per lane, 1 the per-lane production walk, 2 the transmittance wavefront; WF_TR_WAVEFRONT=1 | 0 at upload forces / forbids the last),
+   "intr_variant" (the kernel of wf_hit_interaction_device: bit 0 the quadric / patch / curve interactions are reachable, bit 1 the replay of
+   an alpha-textured curve's recursion too, bit 2 the interpolation of animated transformations; 0 = the lean triangle kernel),
+   "pixels_per_pass" (the pixels of one band of wf_queues_alloc, 0 before it: the least n_max of wf_camera_rays_device).
    Introspection only; nothing in the reference corresponds. */
 int wf_ctx_query(wf_ctx *ctx, const char *key, int64_t *value);
 /* Host-only self-check of the production traversal layout (no device needed; CPU suite, tests/test_fastbvh_host.py): builds the
@@ -872,7 +904,7 @@ int wf_scene_check_instances(const wf_scene_desc *d, int64_t out[4]);
 /* Host-only form of wf_ctx_query (no device and no context needed; CPU suite, tests/test_scene_plan_host.py): runs the planning step of
    wf_scene_upload on `d` under the current environment switches (every check of the description, the classification, the production
    trees) and answers the keys that follow from the description alone: "fast_ok", "gen_mode", "gen_tri", "defer_general", "anim_fast",
-   "lean_shade", "lean_type_<material type>", "rare_lights", "medium_lean", "instances", "nested_animated", "tr_route".  A description that
+   "lean_shade", "lean_type_<material type>", "rare_lights", "medium_lean", "instances", "nested_animated", "tr_route", "intr_variant".  A description that
    wf_scene_upload would reject fails here with the same message.  Every call plans the scene anew, tree build included: meant for
    tests and tools on small scenes, not for asking many keys of a large one. */
 int wf_scene_plan_query(const wf_scene_desc *d, const char *key, int64_t *value);

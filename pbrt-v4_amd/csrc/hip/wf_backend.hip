@@ -40,6 +40,7 @@
 #include "wf_traverse.h"
 #include "wf_plan.h"
 #include "wf_film_develop.h"
+#include "wf_boundary_intr.h"
 
 using namespace wf;
 using namespace wf::planning;
@@ -2076,6 +2077,7 @@ int wf_ctx_query(wf_ctx *ctx, const char *key, int64_t *value) {
     if (k == "frame_overlap_active") *value = FrameOverlapActive(ctx);
     else if (k == "frame_overlap_mode") *value = ctx->frameOverlap;
     else if (k == "skip_last_samples") *value = SkipLastSamples(ctx);
+    else if (k == "pixels_per_pass") *value = ctx->queuesAllocated ? ctx->ws.pixelsPerPass : 0;   // the rays a band holds per sample index (wf_camera_rays_device's n_max)
     else return fail(-1, "wf_ctx_query: unknown key '%s'", key);
     return 0;
 }
@@ -2222,7 +2224,8 @@ int wf_reset_stage_queues(wf_ctx *ctx, int depth) {
     ctx->cursorDirty[0] = false;
     return 0;
 }
-int wf_gen_camera_rays(wf_ctx *ctx, int y0, int sample_index) {
+// countStats = false (wf_camera_rays_device): the band's rays are a caller's, not the render's — they stay out of stats->cameraRays
+static int GenCameraRays(wf_ctx *ctx, int y0, int sample_index, bool countStats) {
     if (int e = checkReady(ctx)) return e;
     ctx->passY0 = y0;
     if (ctx->ws.sampleTops) LAUNCH("Sampler index prefixes", k_sample_tops, gridFor(5 * ctx->ws.pixelsPerPass), ctx->svHost, ctx->ws, y0, 0);
@@ -2230,9 +2233,10 @@ int wf_gen_camera_rays(wf_ctx *ctx, int y0, int sample_index) {
         LAUNCH("Reset ray queue", k_reset, 1, ctx->ws, 1u << CNT_RAY0, -1, 0);
     LAUNCH("Generate camera rays", (ctx->svHost.camera.anim.actually_animated ? k_gen_camera_rays<true> : k_gen_camera_rays<false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, y0, sample_index,
            ctx->passStep, ctx->passSamples);
-    LAUNCH("Update camera ray stats", k_reset, 1, ctx->ws, 0u, 0, CNT_RAY0);
+    if (countStats) LAUNCH("Update camera ray stats", k_reset, 1, ctx->ws, 0u, 0, CNT_RAY0);
     return 0;
 }
+int wf_gen_camera_rays(wf_ctx *ctx, int y0, int sample_index) { return GenCameraRays(ctx, y0, sample_index, true); }
 int wf_gen_ray_samples(wf_ctx *ctx, int depth, int sample_index) {
     if (int e = checkReady(ctx)) return e;
     // the pixel-only digits of the sample-index permutation, once per pixel and dimension instead of once per ray
@@ -2882,6 +2886,48 @@ int wf_trace_closest_device_t(wf_ctx *ctx, int n, const float *rays8, wf_hit_rec
 int wf_trace_any_device_t(wf_ctx *ctx, int n, const float *rays8, int32_t *occluded) {
     if (ctx && n > 0 && !occluded) return fail(-1, "wf_trace_any_device_t: null occluded");
     return TraceDeviceTimed(ctx, "wf_trace_any_device_t", n, rays8, nullptr, occluded);
+}
+// The hit records of wf_trace_closest_device_t as SurfaceInteractions, and the scene's camera rays as rays8 (kernels and launchers:
+// wf_boundary_intr.hip).  Everything is checked before anything is launched.
+int wf_hit_interaction_device(wf_ctx *ctx, int n, const float *rays8, const wf_hit_record *hits, float *out_f, int32_t *out_i) {
+    const char *fn = "wf_hit_interaction_device";
+    if (!ctx) return fail(-1, "%s: null context", fn);
+    if (!ctx->sceneLoaded) return fail(-1, "%s: no scene uploaded", fn);
+    if (n <= 0) return 0;
+    if (n > (1 << 30)) return fail(-1, "%s: n = %d is more than 2^30 items", fn, n);
+    if (!rays8 || !hits || !out_f || !out_i) return fail(-1, "%s: null %s", fn, !rays8 ? "rays8" : !hits ? "hits" : !out_f ? "out_f" : "out_i");
+    if (!Aligned16(rays8) || !Aligned16(hits) || !Aligned16(out_f) || !Aligned16(out_i))
+        return fail(-1, "%s: %s is not aligned to 16 bytes (rays, records and planes are read and written 16 bytes at a time)", fn,
+                    !Aligned16(rays8) ? "rays8" : !Aligned16(hits) ? "hits" : !Aligned16(out_f) ? "out_f" : "out_i");
+    useDevice(ctx);
+    Prof prof_(ctx, "Hit interaction (device records)");
+    const int e = boundary::LaunchHitInteraction(ctx->stream, ctx->plan.intrVariant, ctx->svDev, n, rays8, hits, out_f, out_i);
+    if (e) return fail(e, "%s: the launch failed: %s", fn, e < 0 ? "the library holds no kernel for the scene's intr_variant" : hipGetErrorString((hipError_t)e));
+    return 0;
+}
+int wf_camera_rays_device(wf_ctx *ctx, int y0, int sample_index, int n_max, float *rays8, int32_t *pixel_xy, float *lambda4, int32_t *n_out_device) {
+    const char *fn = "wf_camera_rays_device";
+    if (!ctx) return fail(-1, "%s: null context", fn);
+    if (!ctx->sceneLoaded) return fail(-1, "%s: no scene uploaded", fn);
+    if (!ctx->queuesAllocated) return fail(-1, "%s: queues not allocated (wf_queues_alloc)", fn);
+    if (!rays8 || !pixel_xy || !lambda4 || !n_out_device)
+        return fail(-1, "%s: null %s", fn, !rays8 ? "rays8" : !pixel_xy ? "pixel_xy" : !lambda4 ? "lambda4" : "n_out_device");
+    if (!Aligned16(rays8) || !Aligned16(lambda4) || ((uintptr_t)pixel_xy & 7u) || ((uintptr_t)n_out_device & 3u))
+        return fail(-1, "%s: misaligned buffer (rays8 and lambda4: 16 bytes, pixel_xy: 8, n_out_device: 4)", fn);
+    if (n_max < ctx->ws.pixelsPerPass) return fail(-1, "%s: n_max = %d, a band holds up to %d rays", fn, n_max, ctx->ws.pixelsPerPass);
+    if (sample_index < 0) return fail(-1, "%s: sample_index %d", fn, sample_index);
+    // one sample index per call, whatever the last render's passes carried: the pass state is the call's own for its launches and is
+    // put back afterwards (the kernels have taken their copy of it as an argument by then)
+    const int step = ctx->passStep, samples = ctx->passSamples, slotStride = ctx->ws.slotStride, passY0 = ctx->passY0;
+    ctx->passStep = 1; ctx->passSamples = 1; ctx->ws.slotStride = ctx->pixelMajor ? 1 : 0;
+    int e = GenCameraRays(ctx, y0, sample_index, false);
+    if (!e) {
+        Prof prof_(ctx, "Pack camera rays (device buffers)");
+        e = boundary::LaunchPackCameraRays(ctx->stream, ctx->ws, n_max, rays8, pixel_xy, lambda4, n_out_device);
+        if (e) e = fail(e, "%s: the launch failed: %s", fn, hipGetErrorString((hipError_t)e));
+    }
+    ctx->passStep = step; ctx->passSamples = samples; ctx->ws.slotStride = slotStride; ctx->passY0 = passY0;
+    return e;
 }
 // room for n items in ctx->trScratch, the wavefront's arrays among them if the scene's plan routes through it.  Growth waits for the
 // launches that still read the old arrays; a call that fits allocates and waits for nothing.

@@ -217,6 +217,13 @@ static void ClassifyScene(const wf_scene_desc *d, const Switches &sw, ScenePlan 
         if (t == WF_MAT_SUBSURFACE) plan->haveSubsurface = true;
     }
     if (d->n_quadrics > 0) plan->genMode = (plan->haveCurves || plan->haveQuadricAlpha) ? 3 : 2;
+    {
+        // the hit-interaction kernel of the device-buffer boundary (ScenePlan::intrVariant): allocated what the scene can make it reach
+        bool curveAlpha = false;
+        for (int i = 0; i < d->n_quadrics; ++i)
+            if (d->quadrics[i].type == WF_QUADRIC_CURVE && d->meshes[d->quadrics[i].mesh].alpha_tex >= 0) curveAlpha = true;
+        plan->intrVariant = IntrVariant(d->n_quadrics > 0, curveAlpha, d->n_animated > 0);
+    }
     int alphaGen = 0;   // what the TRIANGLES of the scene ask of the walk: 0 nothing, 1 simple alpha cut-outs, 2 texture-graph alpha
     for (int i = 0; i < d->n_meshes && alphaGen < 2; ++i)
         if (d->meshes[i].alpha_tex >= 0) {
@@ -310,6 +317,7 @@ bool wf::planning::PlanValue(const ScenePlan &plan, const char *key, int64_t *va
     else if (k.rfind("lean_type_", 0) == 0 && atoi(key + 10) >= 0 && atoi(key + 10) < WF_MAT_NTYPES) *value = plan.leanType[atoi(key + 10)];
     else if (k == "instances") *value = plan.nInstances;
     else if (k == "nested_animated") *value = plan.nestedAnimated;
+    else if (k == "intr_variant") *value = plan.intrVariant;   // k_hit_interaction<GENERAL, CURVE_ALPHA, ANIM> (IntrVariant, wf_plan.h)
     else if (k == "tr_route") *value = plan.trRoute;   // -1 no media, 0 k_shadow_tr, 1 k_shadow_tr_fast, 2 the transmittance wavefront
     else return false;
     return true;

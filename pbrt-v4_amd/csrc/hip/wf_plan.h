@@ -110,7 +110,17 @@ struct ScenePlan {
     // one-level scenes whose media are all lean: k_tr_segment<true> runs at 3 waves (162 VGPRs) where the per-lane kernel is one wave of
     // 366 + 110 registers per SIMD — cloud scene 17.3 against 18.5 ms, profiles/r06_transmittance_lean_wavefront_ab_cloud16.txt.
     int trRoute = -1;
+    // The kernel of wf_hit_interaction_device (wf_boundary_intr.hip), k_hit_interaction<GENERAL, CURVE_ALPHA, ANIM>, as IntrVariant() below
+    // encodes it: GENERAL — the scene has quadrics / patches / curves; CURVE_ALPHA — one of its curves carries an alpha texture; ANIM — it
+    // has animated primitives (nested placements included).  0: the lean triangle kernel.
+    int intrVariant = 0;
 };
+// The encoding of ScenePlan::intrVariant ("intr_variant"): the one place it is written down — the planner builds the value with it, the
+// launcher of wf_boundary_intr.hip switches on it.  CURVE_ALPHA exists only with GENERAL (a curve is a general primitive).
+constexpr int INTR_GENERAL = 1, INTR_CURVE_ALPHA = 2, INTR_ANIM = 4;
+constexpr int IntrVariant(bool general, bool curveAlpha, bool anim) {
+    return (general ? INTR_GENERAL : 0) | (general && curveAlpha ? INTR_CURVE_ALPHA : 0) | (anim ? INTR_ANIM : 0);
+}
 // which walk kernel variants resolve their near ties themselves (the others mark them for a re-trace launch)
 constexpr bool RetraceInline(int gen) { return gen <= 1; }
 // The production traversal layout as BuildFastBVH leaves it on the host: what the upload copies once PlanScene has succeeded.

@@ -75,7 +75,11 @@ ABI_SYMBOLS = [
     "wf_trace_shadow_tr_host_t", "wf_trace_one_random_host_t",
     "wf_trace_closest_device_t", "wf_trace_any_device_t", "wf_trace_shadow_tr_device", "wf_trace_one_random_device",
     "wf_film_spectral_upload", "wf_film_gbuffer_upload", "wf_film_channel_count", "wf_film_develop_device", "wf_film_develop_rgb_device",
+    "wf_hit_interaction_device", "wf_camera_rays_device",
 ]
+# the planes of wf_hit_interaction_device (include/wf_abi.h): WF_INTR_FPLANES float planes, WF_INTR_IPLANES int planes, 4 words per item each
+INTR_FPLANES = 11
+INTR_IPLANES = 2
 HOST_SYMBOLS = [
     "wfh_init", "wfh_last_error", "wfh_scene_load", "wfh_scene_load_string", "wfh_scene_free", "wfh_scene_desc", "wfh_scene_info",
     "wfh_renderer_create", "wfh_renderer_create_strips", "wfh_renderer_set_strips", "wfh_renderer_samples_per_pass", "wfh_renderer_ctx", "wfh_render", "wfh_clear_film", "wfh_download_film", "wfh_stats",
@@ -426,6 +430,85 @@ class Scene:
         ts = [segs7, material, out, pdf]
         self._device_call("wf_trace_one_random_device", hip.wf_trace_one_random_device, [C.c_void_p, C.c_int] + [C.c_void_p] * 4, ts, n, *[t.data_ptr() for t in ts])
         return out, pdf
+
+    def interactions_device(self, rays8, hits, out=None):
+        """wf_hit_interaction_device: the SurfaceInteractions of the hit records `hits` (the int32 [n, 8] tensor of trace_device) that the
+        rays `rays8` (float32 [n, 8]) found.  Returns a dict of tensor VIEWS into the call's two plane tensors — float32 [n, 3]: pi_lo,
+        pi_hi, n, ns, wo, dpdu, dpdv, dpdus, dpdvs, dndus, dndvs; float32 [n, 2]: uv; float32 [n]: time, t; int32 [n]: material (-1: an
+        interface surface), area_light (-1: none), medium_inside, medium_outside, mesh, valid (1 hit, 0 miss, -1 a record outside the
+        scene's ranges), mesh_flags (WF_MESH_*) — and the plane tensors themselves as "planes_f" [11, n, 4] / "planes_i" [2, n, 4].
+        out = (float32 tensor, int32 tensor), contiguous, of at least 11 * n * 4 and 2 * n * 4 elements: written into instead of new
+        ones (the planes are the leading elements)."""
+        import torch
+        _, hip = libs()
+        self._as(rays8, torch.float32, 8, "interactions_device rays8")
+        self._as(hits, torch.int32, 8, "interactions_device hits")
+        n = rays8.shape[0]
+        if hits.shape[0] != n:
+            raise WfError("interactions_device: rays8 and hits hold different numbers of items")
+        nf, ni = INTR_FPLANES * n * 4, INTR_IPLANES * n * 4
+        if out is None:
+            of = torch.empty((nf,), dtype=torch.float32, device=rays8.device)
+            oi = torch.empty((ni,), dtype=torch.int32, device=rays8.device)
+        else:
+            of, oi = out
+            if not (isinstance(of, torch.Tensor) and isinstance(oi, torch.Tensor) and of.dtype == torch.float32 and oi.dtype == torch.int32
+                    and of.is_contiguous() and oi.is_contiguous() and of.numel() >= nf and oi.numel() >= ni):
+                raise WfError("interactions_device: out is (float32 tensor of >= %d elements, int32 tensor of >= %d elements), contiguous" % (nf, ni))
+            of, oi = of.view(-1), oi.view(-1)
+        self._device_call("wf_hit_interaction_device", hip.wf_hit_interaction_device, [C.c_void_p, C.c_int] + [C.c_void_p] * 4, [rays8, hits, of, oi],
+                          n, rays8.data_ptr(), hits.data_ptr(), of.data_ptr(), oi.data_ptr())
+        F = of[:nf].view(INTR_FPLANES, n, 4)
+        I = oi[:ni].view(INTR_IPLANES, n, 4)
+        r = {"planes_f": F, "planes_i": I}
+        for k, name in enumerate(("pi_lo", "pi_hi", "n", "ns", "wo", "dpdu", "dpdv", "dpdus", "dpdvs", "dndus", "dndvs")):
+            r[name] = F[k, :, :3]
+        r["uv"] = torch.as_strided(F, (n, 2), (4, 4 * n), F.storage_offset() + 3)   # the w words of planes 0 and 1
+        r["time"], r["t"] = F[2, :, 3], F[3, :, 3]
+        for k, name in enumerate(("material", "area_light", "medium_inside", "medium_outside")):
+            r[name] = I[0, :, k]
+        r["mesh"], r["valid"], r["mesh_flags"] = I[1, :, 0], I[1, :, 1], I[1, :, 2]
+        return r
+
+    def camera_rays_device(self, sample_index, y0=None):
+        """wf_camera_rays_device: the scene's own camera rays of sample index `sample_index` as device tensors (rays8 float32 [n, 8] rows
+        {o, d, tMax = inf, time}, pixel_xy int32 [n, 2], lambda4 float32 [n, 4]), trimmed to the number of rays generated (a realistic
+        camera's lens blocks some).  y0: the first scanline of ONE band of the renderer's passes; None: every band of the image, in
+        order.  Reads the ray count back, so it synchronises; overwrites the renderer's per-pass state (for an idle renderer)."""
+        import torch
+        _, hip = libs()
+        if not self._renderer:
+            raise WfError("camera_rays_device: create_renderer() first")
+        dev = torch.device("cuda", self.device)
+        cap = self.query("pixels_per_pass")
+        rows = max(1, cap // self.info.width)
+        bands = [y0] if y0 is not None else list(range(self.info.y0, self.info.y0 + self.info.height, rows))
+        parts = []
+        for y in bands:
+            rays = torch.empty((cap, 8), dtype=torch.float32, device=dev)
+            pix = torch.empty((cap, 2), dtype=torch.int32, device=dev)
+            lam = torch.empty((cap, 4), dtype=torch.float32, device=dev)
+            count = torch.zeros((1,), dtype=torch.int32, device=dev)
+            ts = [rays, pix, lam, count]
+            self._device_call("wf_camera_rays_device", hip.wf_camera_rays_device, [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4, ts,
+                              y, sample_index, cap, *[t.data_ptr() for t in ts])
+            parts.append((rays, pix, lam, count))
+        out = []
+        for rays, pix, lam, count in parts:
+            k = int(count.item())
+            out.append((rays[:k], pix[:k], lam[:k]))
+        if len(out) == 1:
+            return out[0]
+        return tuple(torch.cat([o[j] for o in out]) for j in range(3))
+
+    def first_hit(self, sample_index):
+        """The closed loop of the device-buffer boundary: the camera rays of `sample_index`, their closest hits and the hits'
+        interactions, all as device tensors.  Returns the dict of interactions_device plus "rays8", "pixel_xy", "lambda4" and "hits"."""
+        rays, pix, lam = self.camera_rays_device(sample_index)
+        hits = self.trace_device(rays)
+        r = self.interactions_device(rays, hits)
+        r.update(rays8=rays, pixel_xy=pix, lambda4=lam, hits=hits)
+        return r
 
     def bounds(self):
         """WavefrontAggregate::Bounds() in rendering space: (pMin[3], pMax[3])"""
