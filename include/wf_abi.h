@@ -884,6 +884,10 @@ int wf_debug_counters(wf_ctx *ctx, uint64_t out[4], int reset);
    walk per lane, 1 the per-lane production walk, 2 the transmittance wavefront; WF_TR_WAVEFRONT=1 | 0 at upload forces / forbids the last),
    "intr_variant" (the kernel of wf_hit_interaction_device: bit 0 the quadric / patch / curve interactions are reachable, bit 1 the replay of
    an alpha-textured curve's recursion too, bit 2 the interpolation of animated transformations; 0 = the lean triangle kernel),
+   "camera_anim" (the camera moves: the ray-generation kernel interpolates its transformation), "route_variant" (the routing pass behind the
+   production closest-hit walk: 0 triangles only, 1 general primitives or object instances, 2 animated primitives), "shade_variant_<material type>"
+   (the type's shade kernel: 0 / 1 lean without / with texture footprints, 2 general, 3 general + visible surface, moving camera, animated
+   primitives or alpha-textured curves; the variants agree bit for bit),
    "pixels_per_pass" (the pixels of one band of wf_queues_alloc, 0 before it: the least n_max of wf_camera_rays_device).
    Introspection only; nothing in the reference corresponds. */
 int wf_ctx_query(wf_ctx *ctx, const char *key, int64_t *value);
@@ -904,7 +908,8 @@ int wf_scene_check_instances(const wf_scene_desc *d, int64_t out[4]);
 /* Host-only form of wf_ctx_query (no device and no context needed; CPU suite, tests/test_scene_plan_host.py): runs the planning step of
    wf_scene_upload on `d` under the current environment switches (every check of the description, the classification, the production
    trees) and answers the keys that follow from the description alone: "fast_ok", "gen_mode", "gen_tri", "defer_general", "anim_fast",
-   "lean_shade", "lean_type_<material type>", "rare_lights", "medium_lean", "instances", "nested_animated", "tr_route", "intr_variant".  A description that
+   "lean_shade", "lean_type_<material type>", "rare_lights", "medium_lean", "instances", "nested_animated", "tr_route", "intr_variant",
+   "camera_anim", "route_variant", "shade_variant_<material type>".  A description that
    wf_scene_upload would reject fails here with the same message.  Every call plans the scene anew, tree build included: meant for
    tests and tools on small scenes, not for asking many keys of a large one. */
 int wf_scene_plan_query(const wf_scene_desc *d, const char *key, int64_t *value);

@@ -47,6 +47,11 @@ enum {
 // (~88 returning atomics/us on MI355X), and with adjacent ints every queue of a stage shared that budget
 constexpr int CNT_STRIDE = 64;
 static_assert(CNT_COUNT <= 32, "k_reset takes the counters to zero as a 32-bit mask");
+// The layout of WorkState::stats: wf_render_stats' cameraRays, indirectRays[64] and shadowRays[64] (by depth, see StatDepth), then the
+// items each material queue and the medium-sample queue held (k_reset adds them as it zeroes counter CNT_MAT0 + i)
+constexpr int STAT_DEPTHS = 64, STAT_NITEMS = 16;
+constexpr int STAT_CAMERA = 0, STAT_INDIRECT = 1, STAT_SHADOW = STAT_INDIRECT + STAT_DEPTHS, STAT_ITEMS = STAT_SHADOW + STAT_DEPTHS, STAT_COUNT = STAT_ITEMS + STAT_NITEMS;
+static_assert(CNT_MEDIUM_SAMPLE - CNT_MAT0 < STAT_NITEMS, "one item slot per material queue and one for the medium-sample queue");
 enum { RAYFLAG_SPECULAR_BOUNCE = 1, RAYFLAG_ANY_NONSPECULAR = 2 };
 
 struct RayQueueV {

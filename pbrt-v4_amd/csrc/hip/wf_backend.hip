@@ -86,7 +86,32 @@ struct WalkKernels {
     TraceClosestFn traceClosest8 = nullptr;
     TraceAnyFn traceAny8 = nullptr;
 };
-
+// ... and the stage kernels that have variants, the same way: filled once, by PickStageKernels beside PickWalkKernels, the only function
+// that names a template argument of a stage kernel.  What a launch site may still choose is an index of run-time state: a counting pass
+// (ctx->countTraversal), items that carry times.
+using StageFn = void (*)(const SceneView, WorkState, int);                  // (sv, ws, cur)
+using StageSpillFn = void (*)(const SceneView, WorkState, int *);           // (sv, ws, stackSpill): the reference-order any-hit / transmittance / probe walks
+using StageCurSpillFn = void (*)(const SceneView, WorkState, int, int *);   // (sv, ws, cur, stackSpill): k_intersect_closest, k_tr_rest
+using CameraRaysFn = void (*)(const SceneView, WorkState, int, int, int, int);
+using ShadowTrFastFn = void (*)(const SceneView, WorkState, FastBVH, SpillArea);
+using TraceOneRandomFn = void (*)(const SceneView, int, const float *, int, const int32_t *, const float *, int, wf_hit_record *, float *, int *);
+// the two halves of the material stage (wf_mat.hip): shade variant 0 | 1 (lean) | 2 | 3, next-event estimation variant 0 | 1
+using MatShadeFn = void (*)(hipStream_t, int, const SceneView *, const WorkState *, int);
+using MatNeeFn = void (*)(hipStream_t, int, const SceneView *, const WorkState *);
+struct StageKernels {
+    CameraRaysFn genCameraRays = nullptr;
+    StageCurSpillFn intersectClosest[2] = {};   // the reference-order walks, [counting pass]
+    StageSpillFn intersectShadow[2] = {}, intersectOneRandom = nullptr;   // ... and the subsurface probe's
+    StageFn routeHits = nullptr;
+    int routeBlock = 0;                         // ... and the threads of its workgroups (RouteBlock)
+    StageFn resolveMix = nullptr, mediumSample = nullptr, mediumRoute = nullptr, mediumScatter = nullptr, handleEscaped = nullptr, trSegment = nullptr;
+    StageCurSpillFn trRest = nullptr;           // (with trSegment the transmittance wavefront's; its walk: WalkKernels::trTrace)
+    StageSpillFn shadowTr[2] = {};              // the reference-order transmittance walk, [items carry times]
+    ShadowTrFastFn shadowTrFast = nullptr, shadowTrFastWitness = nullptr;   // the per-lane production transmittance walk: of plan.trRoute == 1, of the host-array calls (LaunchHostTr)
+    TraceOneRandomFn traceOneRandom[2] = {};    // [segments carry times]
+    MatShadeFn shade[WF_MAT_NTYPES] = {};       // the rows of kMatShade / kMatNee the plan chose; [0]: WF_MAT_INTERFACE has no kernel
+    MatNeeFn nee[WF_MAT_NTYPES] = {};
+};
 
 struct wf_ctx {
     int device = 0;
@@ -117,8 +142,9 @@ struct wf_ctx {
     // depth, where it leaves before the material stage that would read them (scenes without media and subsurface)
     bool samplesShaded = true;
     bool cursorDirty[2] = {false, false};   // the closest-hit / any-hit work cursor has been used since a k_reset last zeroed it
-    ScenePlan plan;              // what the uploaded scene runs: written by PlanScene, read by PickWalkKernels, the launch sites and wf_queues_alloc
+    ScenePlan plan;              // what the uploaded scene runs: written by PlanScene, read by PickWalkKernels / PickStageKernels, the launch sites and wf_queues_alloc
     WalkKernels walk;
+    StageKernels stage;
     // The scratch of wf_trace_shadow_tr_device: the packed shadow-queue items of the call (k_pack_shadow_items), its counter block and —
     // on a scene whose plan routes transmittance through the wavefront (plan.trRoute == 2) — the wavefront's per-item state, index
     // queues and hit records: a call's n has nothing to do with the render's queue size, and the call works without wf_queues_alloc, so
@@ -255,10 +281,10 @@ __global__ void __launch_bounds__(BLOCK) k_reset(WorkState ws, unsigned mask, in
     }
     __syncthreads();
     if (blockIdx.x == 0 && threadIdx.x < CNT_COUNT && ((mask >> threadIdx.x) & 1u)) {
-        // the items a material queue held go to stats[129 + type] before the counter is zeroed (wf_material_items_download: the item
-        // counts of the material stage's roofline) — the same for the medium-sample queue at stats[129 + WF_MAT_NTYPES]
+        // the items a material queue held go to stats[STAT_ITEMS + type] before the counter is zeroed (wf_material_items_download: the item
+        // counts of the material stage's roofline) — the same for the medium-sample queue at stats[STAT_ITEMS + WF_MAT_NTYPES]
         const int t = (int)threadIdx.x;
-        if (t >= CNT_MAT0 && t <= CNT_MEDIUM_SAMPLE) ws.stats[129 + (t - CNT_MAT0)] += (unsigned long long)ws.counters[t * CNT_STRIDE];
+        if (t >= CNT_MAT0 && t <= CNT_MEDIUM_SAMPLE) ws.stats[STAT_ITEMS + (t - CNT_MAT0)] += (unsigned long long)ws.counters[t * CNT_STRIDE];
         ws.counters[t * CNT_STRIDE] = 0;
     }
 }
@@ -1425,9 +1451,6 @@ __global__ void __launch_bounds__(BLOCK) k_handle_emissive(const SceneView svArg
 // the material kernels live in wf_mat.hip (one translation unit per material type)
 // the material types that have kernels (wf_material_type 1 .. WF_MAT_NTYPES - 1): the one list the declarations and tables below are made from
 #define WF_MAT_TYPES(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10)
-// the two halves of the material stage (wf_mat.hip): shade variant 0 | 1 (lean) | 2 | 3, next-event estimation variant 0 | 1
-using MatShadeFn = void (*)(hipStream_t, int, const SceneView *, const WorkState *, int);
-using MatNeeFn = void (*)(hipStream_t, int, const SceneView *, const WorkState *);
 extern "C" {
 #define WF_MAT_DECL(n) void wf_launch_mat_shade_##n##_0(hipStream_t, int, const SceneView *, const WorkState *, int); \
                        void wf_launch_mat_shade_##n##_1(hipStream_t, int, const SceneView *, const WorkState *, int); \
@@ -1615,25 +1638,22 @@ struct Prof {
     }
 };
 
-// (the _ON forms name the stream: the shadow stage of the fused pass runs on ctx->stream3, and its HIP-event times are taken there)
-#define LAUNCH_ON(strm, name, kernel, grid, ...)                                           \
+// (the _ON forms name the stream: the shadow stage of the fused pass runs on ctx->stream3, and its HIP-event times are taken there;
+//  LAUNCHB_ON names the workgroup's threads too)
+#define LAUNCHB_ON(strm, name, kernel, grid, block, ...)                                   \
     do {                                                                                   \
         Prof prof_(ctx, name, strm);                                                       \
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(BLOCK), 0, strm, __VA_ARGS__);         \
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, strm, __VA_ARGS__);         \
     } while (0)
+#define LAUNCH_ON(strm, name, kernel, grid, ...) LAUNCHB_ON(strm, name, kernel, grid, BLOCK, __VA_ARGS__)
 #define LAUNCH(name, kernel, grid, ...) LAUNCH_ON(ctx->stream, name, kernel, grid, __VA_ARGS__)
-
 // a walk kernel (workgroups of TBLOCK threads), usually one of ctx->walk on its resident grid
-#define LAUNCHT_ON(strm, name, kernel, grid, ...)                                          \
-    do {                                                                                   \
-        Prof prof_(ctx, name, strm);                                                       \
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(TBLOCK), 0, strm, __VA_ARGS__);        \
-    } while (0)
+#define LAUNCHT_ON(strm, name, kernel, grid, ...) LAUNCHB_ON(strm, name, kernel, grid, TBLOCK, __VA_ARGS__)
 #define LAUNCHT(name, kernel, grid, ...) LAUNCHT_ON(ctx->stream, name, kernel, grid, __VA_ARGS__)
 
 // wf_render_stats carries 64 per-depth slots (indirect_rays[64], shadow_rays[64]); deeper bounces (volumetric scenes
 // set maxdepth 100 and more) accumulate in the last slot instead of running past the array
-static int statDepth(int depth) { return depth < 63 ? depth : 63; }
+static int statDepth(int depth) { return depth < STAT_DEPTHS - 1 ? depth : STAT_DEPTHS - 1; }
 
 // SceneView::gridCorners: cell (cx, cy, cz) of the (nx + 1)(ny + 1)(nz + 1) table <- the eight values a trilinear lookup with
 // floor(p * res - .5) = (cx - 1, cy - 1, cz - 1) reads (wf_media.h: GridLookupPacked), zeros outside the grid
@@ -1725,6 +1745,36 @@ static int PickWalkKernels(wf_ctx *ctx) {
     if (ctx->plan.deferGeneral && ((e = residentGrid(k.closestGen, &k.gridGen)) || (e = residentGrid(k.shadowGen, &k.gridShadowGen)))) return e;
     ctx->walk = k;
     return 0;
+}
+// ---- the scene's stage kernels (StageKernels): the plan's values onto instantiations, each named here and nowhere else.  Only what the
+// library has always compiled: no k_route_hits<false, true> (an animated primitive is an instance), no k_shadow_tr_fast<true, true> (ALPHA
+// wins over MLEAN).  The order of the statements means nothing to the result: any order picks the same kernels (it only moves them in the code object).
+static void PickStageKernels(wf_ctx *ctx) {
+    const ScenePlan &p = ctx->plan;
+    const bool anim = p.haveAnimated;   // the reference-order walks' ANIM: every scene with animated primitives (p.animFast: those the production walks take)
+    StageKernels &k = ctx->stage;
+    k.genCameraRays = p.cameraAnim ? k_gen_camera_rays<true> : k_gen_camera_rays<false>;
+    k.intersectClosest[1] = anim ? k_intersect_closest<true, true> : k_intersect_closest<true, false>;   // <COUNT, ANIM>
+    if (p.routeVariant == 2) k.routeHits = k_route_hits<true, true>;   // (animated primitives: two-level)
+    else k.routeHits = p.routeVariant == 1 ? k_route_hits<true> : k_route_hits<false>;
+    k.routeBlock = RouteBlock(p.routeVariant == 2);
+    k.resolveMix = anim ? k_resolve_mix<true> : k_resolve_mix<false>;
+    k.intersectClosest[0] = anim ? k_intersect_closest<false, true> : k_intersect_closest<false, false>;
+    k.mediumSample = p.mediumLean ? k_medium_sample<true> : k_medium_sample<false>;
+    k.mediumRoute = anim ? k_medium_route<true> : k_medium_route<false>;
+    k.mediumScatter = p.rareLights ? k_medium_scatter<true> : k_medium_scatter<false>;
+    if (p.animFast) k.trSegment = p.mediumLean ? k_tr_segment<true, true> : k_tr_segment<false, true>;   // <MLEAN, ANIM>
+    else k.trSegment = p.mediumLean ? k_tr_segment<true> : k_tr_segment<false>;
+    k.trRest = p.animFast ? k_tr_rest<true> : k_tr_rest<false>;
+    k.shadowTrFast = p.trFastAlpha ? k_shadow_tr_fast<true> : p.mediumLean ? k_shadow_tr_fast<false, true> : k_shadow_tr_fast<false>;   // <ALPHA, MLEAN>
+    k.shadowTrFastWitness = p.trFastAlpha ? k_shadow_tr_fast<true> : k_shadow_tr_fast<false>;
+    k.shadowTr[1] = k_shadow_tr<true>; k.shadowTr[0] = k_shadow_tr<false>;
+    k.handleEscaped = p.portalLights ? k_handle_escaped<true> : k_handle_escaped<false>;
+    k.intersectShadow[1] = anim ? k_intersect_shadow<true, true> : k_intersect_shadow<true, false>;
+    k.intersectShadow[0] = anim ? k_intersect_shadow<false, true> : k_intersect_shadow<false, false>;
+    k.intersectOneRandom = anim ? k_intersect_one_random<true> : k_intersect_one_random<false>;
+    k.traceOneRandom[1] = k_trace_one_random<true>; k.traceOneRandom[0] = k_trace_one_random<false>;
+    for (int t = 1; t < WF_MAT_NTYPES; ++t) { k.shade[t] = kMatShade[t][p.shadeVariant[t]]; k.nee[t] = kMatNee[t][p.rareLights]; }
 }
 
 extern "C" {
@@ -2002,6 +2052,7 @@ static int UploadTraversal(wf_ctx *ctx, const FastTrees &trees) {
         HIPCHK(hipStreamSynchronize(ctx->stream));
     }
     if ((e = PickWalkKernels(ctx))) return e;
+    PickStageKernels(ctx);
     if ((e = devAlloc(ctx, &ctx->probeCursor, (size_t)1))) return e;
     // the walk on stream3 pushes into spill rows of its own: a column is indexed by the global thread, which both walks have
     if (FrameOverlapScene(ctx) && (e = devAlloc(ctx, &ctx->stackSpill2, (size_t)plan.spillRows * MAX_GRID * BLOCK))) return e;
@@ -2019,7 +2070,7 @@ static int UploadFilmAndView(wf_ctx *ctx, const wf_scene_desc *d) {
     ctx->ws.filmGBuffer = nullptr;
     if (d->film.type == WF_FILM_GBUFFER && (e = devAlloc(ctx, &ctx->ws.filmGBuffer, (size_t)ctx->W * ctx->H))) return e;
     if (d->film.type == WF_FILM_SPECTRAL && (e = devAlloc(ctx, &ctx->ws.filmSpectral, (size_t)ctx->W * ctx->H * 2 * d->film.n_buckets))) return e;
-    if ((e = devAlloc(ctx, &ctx->ws.stats, (size_t)(129 + 16)))) return e;   // [129 ..]: items per material queue / the medium-sample queue
+    if ((e = devAlloc(ctx, &ctx->ws.stats, (size_t)STAT_COUNT))) return e;
     if ((e = devAlloc(ctx, &ctx->ws.trav, (size_t)8))) return e;
     if ((e = devAlloc(ctx, &ctx->ws.counters, (size_t)CNT_COUNT * CNT_STRIDE))) return e;
     SceneView *dev = nullptr;
@@ -2057,6 +2108,7 @@ int wf_scene_upload(wf_ctx *ctx, const wf_scene_desc *d) {
             ctx->ws = WorkState{};
             ctx->fast = FastBVH{};
             ctx->walk = WalkKernels{};
+            ctx->stage = StageKernels{};
             ctx->plan = ScenePlan{};
             ctx->stackSpill = ctx->stackSpill2 = ctx->dbgWords = nullptr;
             ctx->probeCursor = nullptr;
@@ -2196,7 +2248,7 @@ int wf_film_clear(wf_ctx *ctx) {
     HIPCHK(hipMemsetAsync(ctx->ws.film, 0, (size_t)ctx->W * ctx->H * 4 * sizeof(double), ctx->stream));
     if (ctx->ws.filmGBuffer) HIPCHK(hipMemsetAsync(ctx->ws.filmGBuffer, 0, (size_t)ctx->W * ctx->H * sizeof(wf_gbuffer_pixel), ctx->stream));
     if (ctx->ws.filmSpectral) HIPCHK(hipMemsetAsync(ctx->ws.filmSpectral, 0, (size_t)ctx->W * ctx->H * 2 * ctx->svHost.film.n_buckets * sizeof(double), ctx->stream));
-    HIPCHK(hipMemsetAsync(ctx->ws.stats, 0, (129 + 16) * sizeof(unsigned long long), ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->ws.stats, 0, STAT_COUNT * sizeof(unsigned long long), ctx->stream));
     HIPCHK(hipMemsetAsync(ctx->ws.trav, 0, 8 * sizeof(unsigned long long), ctx->stream));
     return 0;
 }
@@ -2218,9 +2270,9 @@ int wf_reset_stage_queues(wf_ctx *ctx, int depth) {
     const unsigned mask = stageMask | (1u << (CNT_RAY0 + (cur ^ 1)));
     // (NOT in the mask, and not to be: CNT_SHADOW, CNT_CURSOR_SHADOW, CNT_DEFER_SHADOW — in the fused pass the previous depth's shadow stage
     //  may still be running on stream3 when this launch executes; it owns those three and zeroes them itself ("Reset shadowRayQueue").
-    //  The stats slots differ too: [1 + depth] here, [65 + depth] there, [129 ..] here only.)
+    //  The stats slots differ too: [STAT_INDIRECT + depth] here, [STAT_SHADOW + depth] there, [STAT_ITEMS ..] here only.)
     // stats->indirectRays[depth] += queue size (integrator.cpp:411-414)
-    LAUNCH("Reset queues before tracing rays", k_reset, 1, ctx->ws, mask, 1 + statDepth(depth), CNT_RAY0 + cur);
+    LAUNCH("Reset queues before tracing rays", k_reset, 1, ctx->ws, mask, STAT_INDIRECT + statDepth(depth), CNT_RAY0 + cur);
     ctx->cursorDirty[0] = false;
     return 0;
 }
@@ -2231,9 +2283,8 @@ static int GenCameraRays(wf_ctx *ctx, int y0, int sample_index, bool countStats)
     if (ctx->ws.sampleTops) LAUNCH("Sampler index prefixes", k_sample_tops, gridFor(5 * ctx->ws.pixelsPerPass), ctx->svHost, ctx->ws, y0, 0);
     if (ctx->svHost.camera.type == WF_CAMERA_REALISTIC)  // rays blocked by the lenses leave no queue entry: the kernel appends
         LAUNCH("Reset ray queue", k_reset, 1, ctx->ws, 1u << CNT_RAY0, -1, 0);
-    LAUNCH("Generate camera rays", (ctx->svHost.camera.anim.actually_animated ? k_gen_camera_rays<true> : k_gen_camera_rays<false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, y0, sample_index,
-           ctx->passStep, ctx->passSamples);
-    if (countStats) LAUNCH("Update camera ray stats", k_reset, 1, ctx->ws, 0u, 0, CNT_RAY0);
+    LAUNCH("Generate camera rays", ctx->stage.genCameraRays, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, y0, sample_index, ctx->passStep, ctx->passSamples);
+    if (countStats) LAUNCH("Update camera ray stats", k_reset, 1, ctx->ws, 0u, STAT_CAMERA, CNT_RAY0);
     return 0;
 }
 int wf_gen_camera_rays(wf_ctx *ctx, int y0, int sample_index) { return GenCameraRays(ctx, y0, sample_index, true); }
@@ -2255,12 +2306,8 @@ static int JoinRetrace(wf_ctx *ctx) {
 }
 int wf_intersect_closest(wf_ctx *ctx, int depth) {
     if (int e = checkReady(ctx)) return e;
-    // counting on: the reference-order walk (its visit counts define the algorithmic bytes);
-    // otherwise the production traversal (wf_traverse.h)
-    const bool anim = ctx->svHost.haveAnimated;
-    if (ctx->countTraversal)
-        LAUNCH("Intersect closest", (anim ? k_intersect_closest<true, true> : k_intersect_closest<true, false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1, ctx->stackSpill);
-    else if (ctx->plan.fastOk) {
+    // counting on: the reference-order walk (its visit counts define the algorithmic bytes); otherwise the production traversal (wf_traverse.h)
+    if (!ctx->countTraversal && ctx->plan.fastOk) {
         const WalkKernels &k = ctx->walk;
         // the work cursor starts at 0: zeroed by the stage's "Reset queues" launch (wf_reset_stage_queues) — a memset node of its own
         // cost a launch's latency per traversal launch (139 fillBuffer launches, 6 ms, in three renders of the spec scene, round 4);
@@ -2292,69 +2339,60 @@ int wf_intersect_closest(wf_ctx *ctx, int depth) {
             HIPCHK(hipEventRecord(ctx->evJoin, ctx->stream2));
             ctx->retracePending = true;
         }
-        {
-            Prof prof_(ctx, "Route hits");
-            const int g = std::min(MAX_GRID, std::max(1, (ctx->maxQueueSize + RBLOCK - 1) / RBLOCK));
-            if (anim)   // (two-level)
-                hipLaunchKernelGGL((k_route_hits<true, true>), dim3(std::min(MAX_GRID, std::max(1, (ctx->maxQueueSize + BLOCK - 1) / BLOCK))), dim3(BLOCK), 0, ctx->stream, ctx->svHost, ctx->ws, depth & 1);
-            else if (ctx->plan.genMode > 1 || ctx->svHost.nInstances > 0) hipLaunchKernelGGL(k_route_hits<true>, dim3(g), dim3(RBLOCK), 0, ctx->stream, ctx->svHost, ctx->ws, depth & 1);
-            else hipLaunchKernelGGL(k_route_hits<false>, dim3(g), dim3(RBLOCK), 0, ctx->stream, ctx->svHost, ctx->ws, depth & 1);
-        }
+        const int rb = ctx->stage.routeBlock;
+        LAUNCHB_ON(ctx->stream, "Route hits", ctx->stage.routeHits, std::min(MAX_GRID, std::max(1, (ctx->maxQueueSize + rb - 1) / rb)), rb, ctx->svHost, ctx->ws, depth & 1);
         if (ctx->retracePending) {
             if (ctx->deferJoin) return 0;   // the fused pass joins after its sample-generation launch (JoinRetrace)
             if (int e = JoinRetrace(ctx)) return e;
         } else if (!RetraceInline(ctx->plan.genMode))
             LAUNCH("Intersect closest: near-tie re-trace", k_closest_retrace, 128, ctx->svHost, ctx->ws, depth & 1, ctx->stackSpill);
-        if (ctx->svHost.haveMix) LAUNCH("Resolve MixMaterial hits", (anim ? k_resolve_mix<true> : k_resolve_mix<false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
+        if (ctx->svHost.haveMix) LAUNCH("Resolve MixMaterial hits", ctx->stage.resolveMix, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
     } else
-        LAUNCH("Intersect closest", (anim ? k_intersect_closest<false, true> : k_intersect_closest<false, false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1, ctx->stackSpill);
+        LAUNCH("Intersect closest", ctx->stage.intersectClosest[ctx->countTraversal], gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1, ctx->stackSpill);
     return 0;
 }
 // SampleMediumInteraction (wavefront/media.cpp:22-257): K5, then K6 for the Henyey-Greenstein phase function
 int wf_medium_sample(wf_ctx *ctx, int depth) {
     if (int e = checkReady(ctx)) return e;
     if (!ctx->svHost.haveMedia) return 0;
-    LAUNCH("Sample medium interaction", (ctx->plan.mediumLean ? k_medium_sample<true> : k_medium_sample<false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
-    LAUNCH("Sample medium interaction: route surface hits", (ctx->svHost.haveAnimated ? k_medium_route<true> : k_medium_route<false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
+    LAUNCH("Sample medium interaction", ctx->stage.mediumSample, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
+    LAUNCH("Sample medium interaction: route surface hits", ctx->stage.mediumRoute, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
     if (depth == ctx->maxDepth) return 0;
-    LAUNCH("Sample direct/indirect - Henyey-Greenstein", (ctx->plan.rareLights ? k_medium_scatter<true> : k_medium_scatter<false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
+    LAUNCH("Sample direct/indirect - Henyey-Greenstein", ctx->stage.mediumScatter, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
     return 0;
 }
-// the wavefront's segment kernel for the scene: the lean medium code or all of it, hits through animated primitives at the ray's time or not
-using TrSegmentFn = void (*)(const SceneView, WorkState, int);
-static TrSegmentFn TrSegmentKernel(const wf_ctx *ctx) {
-    if (ctx->plan.animFast) return ctx->plan.mediumLean ? k_tr_segment<true, true> : k_tr_segment<false, true>;
-    return ctx->plan.mediumLean ? k_tr_segment<true> : k_tr_segment<false>;
+// The transmittance stage's launches over `ws` (n items) by `route` (ScenePlan::trRoute): 2 the wavefront (see k_tr_begin), 1 the per-lane
+// production walk (static one-level scenes), 0 the reference-order walk per lane, at the items' times if they carry them (`timed`).
+// The one copy of the sequence: the render's stage and wf_trace_shadow_tr_device run it, each over its WorkState and under its own names.
+struct TrNames { const char *reset, *begin, *trace, *segment, *rest, *perLane; };
+static void LaunchTransmittance(wf_ctx *ctx, const WorkState &ws, int n, int route, bool timed, const TrNames &names) {
+    if (route == 2) {
+        LAUNCH(names.reset, k_reset, 1, ws, (1u << CNT_TR0) | (1u << CNT_TR1), -1, 0);
+        LAUNCH(names.begin, k_tr_begin, gridFor(n), ctx->svHost, ws);
+        for (int seg = 0; seg < WF_TR_SEGMENTS; ++seg) {
+            const int cur = seg & 1;
+            LAUNCHT(names.trace, ctx->walk.trTrace, ctx->walk.grid, ctx->svHost, ws, ctx->fast, cur, ctx->spillArea());
+            LAUNCH(names.segment, ctx->stage.trSegment, gridFor(n), ctx->svHost, ws, cur);
+            LAUNCH(names.reset, k_reset, 1, ws, 1u << (CNT_TR0 + cur), -1, 0);
+        }
+        LAUNCH(names.rest, ctx->stage.trRest, 128, ctx->svHost, ws, WF_TR_SEGMENTS & 1, ctx->stackSpill);
+    } else if (route == 1) LAUNCHT(names.perLane, ctx->stage.shadowTrFast, ctx->walk.grid, ctx->svHost, ws, ctx->fast, ctx->spillArea());
+    else LAUNCH(names.perLane, ctx->stage.shadowTr[timed], gridFor(n), ctx->svHost, ws, ctx->stackSpill);
 }
 // TraceShadowRays with media: IntersectShadowTr (wavefront/aggregate.cpp:70-88, intersect.h:165-274)
 int wf_intersect_shadow_tr(wf_ctx *ctx, int depth) {
     if (int e = checkReady(ctx)) return e;
     if (!ctx->svHost.haveMedia) return fail(-1, "wf_intersect_shadow_tr: the scene has no media (use wf_intersect_shadow)");
-    // the scene's planned route (ScenePlan::trRoute); a counting pass keeps the reference-order walk
-    const int route = ctx->countTraversal ? 0 : ctx->plan.trRoute;
-    if (route == 2) {
-        // the transmittance wavefront (see k_tr_begin)
-        LAUNCH("Reset transmittance queues", k_reset, 1, ctx->ws, (1u << CNT_TR0) | (1u << CNT_TR1), -1, 0);
-        LAUNCH("Intersect shadow (Tr): begin", k_tr_begin, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws);
-        for (int seg = 0; seg < WF_TR_SEGMENTS; ++seg) {
-            const int cur = seg & 1;
-            LAUNCHT("Intersect shadow (Tr): trace", ctx->walk.trTrace, ctx->walk.grid, ctx->svHost, ctx->ws, ctx->fast, cur, ctx->spillArea());
-            LAUNCH("Intersect shadow (Tr): segment", TrSegmentKernel(ctx), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, cur);
-            LAUNCH("Reset transmittance queues", k_reset, 1, ctx->ws, 1u << (CNT_TR0 + cur), -1, 0);
-        }
-        LAUNCH("Intersect shadow (Tr): rest", (ctx->plan.animFast ? k_tr_rest<true> : k_tr_rest<false>), 128, ctx->svHost, ctx->ws, WF_TR_SEGMENTS & 1, ctx->stackSpill);
-    } else if (route == 1)  // (the per-lane production walk has no two-level and no ANIM variant)
-        LAUNCHT("Intersect shadow (Tr)", (ctx->svHost.haveAlpha || ctx->svHost.nQuadrics > 0 ? k_shadow_tr_fast<true> : ctx->plan.mediumLean ? k_shadow_tr_fast<false, true> : k_shadow_tr_fast<false>), ctx->walk.grid,
-                ctx->svHost, ctx->ws, ctx->fast, ctx->spillArea());
-    else
-        LAUNCH("Intersect shadow (Tr)", (ctx->svHost.haveAnimated ? k_shadow_tr<true> : k_shadow_tr<false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, ctx->stackSpill);
-    LAUNCH("Reset shadowRayQueue", k_reset, 1, ctx->ws, (1u << CNT_SHADOW), 65 + statDepth(depth), CNT_SHADOW);
+    LaunchTransmittance(ctx, ctx->ws, ctx->maxQueueSize, ctx->countTraversal ? 0 : ctx->plan.trRoute, ctx->plan.haveAnimated,   // (a counting pass keeps the reference-order walk)
+                        {"Reset transmittance queues", "Intersect shadow (Tr): begin", "Intersect shadow (Tr): trace", "Intersect shadow (Tr): segment",
+                         "Intersect shadow (Tr): rest", "Intersect shadow (Tr)"});
+    LAUNCH("Reset shadowRayQueue", k_reset, 1, ctx->ws, (1u << CNT_SHADOW), STAT_SHADOW + statDepth(depth), CNT_SHADOW);
     return 0;
 }
 int wf_handle_escaped(wf_ctx *ctx, int depth) {
     if (int e = checkReady(ctx)) return e;
     if (ctx->svHost.nInfiniteLights == 0) return 0;  // escapedRayQueue == nullptr (integrator.cpp:496-497)
-    LAUNCH("Handle escaped rays", (ctx->plan.portalLights ? k_handle_escaped<true> : k_handle_escaped<false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
+    LAUNCH("Handle escaped rays", ctx->stage.handleEscaped, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
     return 0;
 }
 int wf_handle_emissive(wf_ctx *ctx, int depth) {
@@ -2371,25 +2409,13 @@ static int EvalMaterial(wf_ctx *ctx, int material_type, int depth) {
                                                "MeasuredMaterial + BxDF eval (Basic tex)"};
     if (material_type == WF_MAT_INTERFACE) return 0;
     if (material_type < 0 || material_type >= WF_MAT_NTYPES) return fail(-1, "material type %d has no HIP kernel", material_type);
-    const bool tex = ctx->svHost.texNeedsFootprint != 0;
-    const bool vs = ctx->svHost.film.type == WF_FILM_GBUFFER || ctx->svHost.camera.anim.actually_animated || ctx->svHost.haveAnimated ||
-                    (ctx->svHost.haveCurves && ctx->svHost.haveQuadricAlpha);   // the variant that fills the visible surface / differentiates a moving camera / meets animated instances or alpha-textured curves
-    // the two halves (wf_kernels.h MatShade / MatNee; the items' NeeItems stay in ws.neeRec between them)
-    {
-        Prof prof_(ctx, names[material_type]);
-        // shade variant: 0 / 1 the LEAN kernels (triangle-only scenes whose textures are all constants, image maps or bilerps: SceneLean),
-        // without / with the texture footprint and bump block; 2 general; 3 general + visible surface / moving camera
-        const int v = vs ? 3 : (!ctx->plan.leanType[material_type] ? 2 : (tex ? 1 : 0));
-        kMatShade[material_type][v](ctx->stream, g, &ctx->svHost, &ctx->ws, cur);
-    }
-    {
-        static const char *neeNames[WF_MAT_NTYPES] = {"", "DiffuseMaterial: next-event estimation", "ConductorMaterial: next-event estimation", "DielectricMaterial: next-event estimation",
-                                                      "ThinDielectricMaterial: next-event estimation", "DiffuseTransmissionMaterial: next-event estimation",
-                                                      "CoatedDiffuseMaterial: next-event estimation", "CoatedConductorMaterial: next-event estimation",
-                                                      "SubsurfaceMaterial: next-event estimation", "HairMaterial: next-event estimation", "MeasuredMaterial: next-event estimation"};
-        Prof prof_(ctx, neeNames[material_type]);
-        kMatNee[material_type][ctx->plan.rareLights ? 1 : 0](ctx->stream, g, &ctx->svHost, &ctx->ws);
-    }
+    // the two halves (wf_kernels.h MatShade / MatNee; the items' NeeItems stay in ws.neeRec between them), in the plan's variants (shadeVariant, rareLights)
+    { Prof prof_(ctx, names[material_type]); ctx->stage.shade[material_type](ctx->stream, g, &ctx->svHost, &ctx->ws, cur); }
+    static const char *neeNames[WF_MAT_NTYPES] = {"", "DiffuseMaterial: next-event estimation", "ConductorMaterial: next-event estimation", "DielectricMaterial: next-event estimation",
+                                                  "ThinDielectricMaterial: next-event estimation", "DiffuseTransmissionMaterial: next-event estimation",
+                                                  "CoatedDiffuseMaterial: next-event estimation", "CoatedConductorMaterial: next-event estimation",
+                                                  "SubsurfaceMaterial: next-event estimation", "HairMaterial: next-event estimation", "MeasuredMaterial: next-event estimation"};
+    { Prof prof_(ctx, neeNames[material_type]); ctx->stage.nee[material_type](ctx->stream, g, &ctx->svHost, &ctx->ws); }
     return 0;
 }
 int wf_eval_material(wf_ctx *ctx, int material_type, int depth) {
@@ -2409,10 +2435,7 @@ static int EvalMaterials(wf_ctx *ctx, int depth) {
 // The shadow stage of one depth on `strm` with the spill rows `spill`: the main stream and the context's own rows for the per-stage entry
 // point; stream3 and stackSpill2 where the fused pass runs it beside the next depth (IssueShadowAside).
 static int ShadowStage(wf_ctx *ctx, int depth, hipStream_t strm, int *spill) {
-    const bool anim = ctx->svHost.haveAnimated;
-    if (ctx->countTraversal)
-        LAUNCH_ON(strm, "Intersect shadow", (anim ? k_intersect_shadow<true, true> : k_intersect_shadow<true, false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, spill);
-    else if (ctx->plan.fastOk) {
+    if (!ctx->countTraversal && ctx->plan.fastOk) {
         const WalkKernels &k = ctx->walk;
         const SpillArea area{spill, ctx->plan.spillRows, ctx->dbgWords};   // (the debug words are shared: every update of them is an atomic)
         int *cursor = ctx->ws.counters + CNT_CURSOR_SHADOW * CNT_STRIDE;   // (zeroed by the "Reset shadowRayQueue" launch that follows every any-hit launch)
@@ -2426,9 +2449,9 @@ static int ShadowStage(wf_ctx *ctx, int depth, hipStream_t strm, int *spill) {
         if (k.shadowGen)
             LAUNCHT_ON(strm, "Intersect shadow: rays that met a general primitive", k.shadowGen, k.gridShadowGen, ctx->svHost, ws, ctx->fast, area, (int *)nullptr, ctx->plan.cursorChunkShadow, (const int *)ws.deferQ);
     } else
-        LAUNCH_ON(strm, "Intersect shadow", (anim ? k_intersect_shadow<false, true> : k_intersect_shadow<false, false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, spill);
+        LAUNCH_ON(strm, "Intersect shadow", ctx->stage.intersectShadow[ctx->countTraversal], gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, spill);
     // "Reset shadowRayQueue": stats->shadowRays[depth] += size; Reset (integrator.cpp:581-585)
-    LAUNCH_ON(strm, "Reset shadowRayQueue", k_reset, 1, ctx->ws, (1u << CNT_SHADOW) | (1u << CNT_CURSOR_SHADOW) | (1u << CNT_DEFER_SHADOW), 65 + statDepth(depth), CNT_SHADOW);
+    LAUNCH_ON(strm, "Reset shadowRayQueue", k_reset, 1, ctx->ws, (1u << CNT_SHADOW) | (1u << CNT_CURSOR_SHADOW) | (1u << CNT_DEFER_SHADOW), STAT_SHADOW + statDepth(depth), CNT_SHADOW);
     ctx->cursorDirty[1] = false;
     return 0;
 }
@@ -2467,7 +2490,7 @@ int wf_intersect_one_random(wf_ctx *ctx) {
     if (int e = checkReady(ctx)) return e;
     if (!ctx->svHost.haveSubsurface) return 0;
     // reference-order walk (the chain of probe hits is a dependent sequence per item; the subsurface path is a side path)
-    LAUNCH("Intersect one random (subsurface probe)", (ctx->svHost.haveAnimated ? k_intersect_one_random<true> : k_intersect_one_random<false>), gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, ctx->stackSpill);
+    LAUNCH("Intersect one random (subsurface probe)", ctx->stage.intersectOneRandom, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, ctx->stackSpill);
     return 0;
 }
 int wf_subsurface_scatter(wf_ctx *ctx, int depth) {
@@ -2687,14 +2710,12 @@ int wf_film_gather_strips(wf_ctx *dst, wf_ctx *src) {
 // the ray counters of another context added to this one's (the statistics of a multi-device render, summed on the gathering context)
 int wf_stats_add(wf_ctx *dst, wf_ctx *src) {
     if (!dst || !src || !dst->sceneLoaded || !src->sceneLoaded) return fail(-1, "wf_stats_add: no scene uploaded");
-    // cameraRays + indirect[64] + shadow[64], then the per-material-type and medium-sample item counters ([129, 129 + 16))
-    constexpr int NSTAT = 129 + 16;
-    unsigned long long a[NSTAT], b[NSTAT];
+    unsigned long long a[STAT_COUNT], b[STAT_COUNT];   // the ray counts and the item counters behind them
     useDevice(src);
     HIPCHK(hipMemcpy(b, src->ws.stats, sizeof(b), hipMemcpyDeviceToHost));
     useDevice(dst);
     HIPCHK(hipMemcpy(a, dst->ws.stats, sizeof(a), hipMemcpyDeviceToHost));
-    for (int i = 0; i < NSTAT; ++i) a[i] += b[i];
+    for (int i = 0; i < STAT_COUNT; ++i) a[i] += b[i];
     HIPCHK(hipMemcpy(dst->ws.stats, a, sizeof(a), hipMemcpyHostToDevice));
     useDevice(src);
     HIPCHK(hipMemset(src->ws.stats, 0, sizeof(b)));   // (moved, not copied: a second call adds only what src counted since)
@@ -2705,22 +2726,22 @@ int wf_stats_add(wf_ctx *dst, wf_ctx *src) {
 // medium-sample stage (out[WF_MAT_NTYPES]): the counts the queues held when they were reset, plus what they hold now
 int wf_material_items_download(wf_ctx *ctx, uint64_t out[16]) {
     if (int e = checkReady(ctx)) return e;
-    unsigned long long h[16];
+    unsigned long long h[STAT_NITEMS];
     std::vector<int32_t> cnt((size_t)CNT_COUNT * CNT_STRIDE);
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    HIPCHK(hipMemcpy(h, ctx->ws.stats + 129, sizeof(h), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h, ctx->ws.stats + STAT_ITEMS, sizeof(h), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(cnt.data(), ctx->ws.counters, cnt.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    for (int i = 0; i < 16; ++i) out[i] = i <= WF_MAT_NTYPES ? h[i] + (uint64_t)cnt[(size_t)(CNT_MAT0 + i) * CNT_STRIDE] : 0;
+    for (int i = 0; i < STAT_NITEMS; ++i) out[i] = i <= WF_MAT_NTYPES ? h[i] + (uint64_t)cnt[(size_t)(CNT_MAT0 + i) * CNT_STRIDE] : 0;
     return 0;
 }
 int wf_stats_download(wf_ctx *ctx, wf_render_stats *out) {
     if (!ctx || !ctx->sceneLoaded) return fail(-1, "no scene uploaded");
     useDevice(ctx);
-    unsigned long long h[129];
+    unsigned long long h[STAT_ITEMS];
     HIPCHK(hipMemcpyAsync(h, ctx->ws.stats, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    out->camera_rays = h[0];
-    for (int i = 0; i < 64; ++i) { out->indirect_rays[i] = h[1 + i]; out->shadow_rays[i] = h[65 + i]; }
+    out->camera_rays = h[STAT_CAMERA];
+    for (int i = 0; i < STAT_DEPTHS; ++i) { out->indirect_rays[i] = h[STAT_INDIRECT + i]; out->shadow_rays[i] = h[STAT_SHADOW + i]; }
     return 0;
 }
 
@@ -2818,36 +2839,12 @@ int wf_trace_any_device(wf_ctx *ctx, int n, const float *rays7, int32_t *occlude
 }
 // The transmittance launch of the HOST-ARRAY boundary calls (wf_trace_shadow_tr_host / _host_t) over their scratch WorkState `ws` of n
 // items: one loop per lane, whatever the scene's plan routes the render through — the independent witness the device-buffer call is
-// compared with.  timed: the items carry times (ws.pathTime) and the reference-order walk's ANIM variant interpolates at them;
-// otherwise the per-lane production walk where there is one (one-level scenes), else the reference-order walk.
+// compared with, hence a rule of its own and not LaunchTransmittance's.  timed: the items carry times (ws.pathTime), read by the reference-order
+// walk's ANIM variant on any scene; otherwise the per-lane production walk where there is one (one-level fastOk scenes; never its MLEAN variant), else the reference-order walk.
 static int LaunchHostTr(wf_ctx *ctx, const WorkState &ws, int n, bool timed) {
-    if (timed) {
-        LAUNCH("shadow Tr (host rays, timed)", k_shadow_tr<true>, gridFor(n), ctx->svHost, ws, ctx->stackSpill);
-    } else if (ctx->plan.fastOk && ctx->svHost.nInstances == 0) {
-        LAUNCHT("shadow Tr (host rays)", (ctx->svHost.haveAlpha || ctx->svHost.nQuadrics > 0 ? k_shadow_tr_fast<true> : k_shadow_tr_fast<false>), ctx->walk.grid, ctx->svHost, ws, ctx->fast, ctx->spillArea());
-    } else LAUNCH("shadow Tr (host rays)", k_shadow_tr<false>, gridFor(n), ctx->svHost, ws, ctx->stackSpill);
-    return 0;
-}
-// ... and of the DEVICE-BUFFER call (wf_trace_shadow_tr_device): the scene's planned route (ScenePlan::trRoute), with the kernels and
-// the launch sequence of the render's own stage (wf_intersect_shadow_tr), over the call's scratch WorkState.  timed: the scene has
-// animated primitives and the items carry times (ws.pathTime).
-static int LaunchDeviceTr(wf_ctx *ctx, const WorkState &ws, int n, bool timed) {
-    if (ctx->plan.trRoute == 2) {
-        LAUNCH("shadow Tr (device rays): reset", k_reset, 1, ws, (1u << CNT_TR0) | (1u << CNT_TR1), -1, 0);
-        LAUNCH("shadow Tr (device rays): begin", k_tr_begin, gridFor(n), ctx->svHost, ws);
-        for (int seg = 0; seg < WF_TR_SEGMENTS; ++seg) {
-            const int cur = seg & 1;
-            LAUNCHT("shadow Tr (device rays): trace", ctx->walk.trTrace, ctx->walk.grid, ctx->svHost, ws, ctx->fast, cur, ctx->spillArea());
-            LAUNCH("shadow Tr (device rays): segment", TrSegmentKernel(ctx), gridFor(n), ctx->svHost, ws, cur);
-            LAUNCH("shadow Tr (device rays): reset", k_reset, 1, ws, 1u << (CNT_TR0 + cur), -1, 0);
-        }
-        LAUNCH("shadow Tr (device rays): rest", (ctx->plan.animFast ? k_tr_rest<true> : k_tr_rest<false>), 128, ctx->svHost, ws, WF_TR_SEGMENTS & 1, ctx->stackSpill);
-    } else if (ctx->plan.trRoute == 1) {
-        LAUNCHT("shadow Tr (device rays)", (ctx->svHost.haveAlpha || ctx->svHost.nQuadrics > 0 ? k_shadow_tr_fast<true> : ctx->plan.mediumLean ? k_shadow_tr_fast<false, true> : k_shadow_tr_fast<false>), ctx->walk.grid,
-                ctx->svHost, ws, ctx->fast, ctx->spillArea());
-    } else if (timed) {
-        LAUNCH("shadow Tr (device rays, timed)", k_shadow_tr<true>, gridFor(n), ctx->svHost, ws, ctx->stackSpill);
-    } else LAUNCH("shadow Tr (device rays)", k_shadow_tr<false>, gridFor(n), ctx->svHost, ws, ctx->stackSpill);
+    if (timed) LAUNCH("shadow Tr (host rays, timed)", ctx->stage.shadowTr[1], gridFor(n), ctx->svHost, ws, ctx->stackSpill);
+    else if (ctx->plan.fastOk && ctx->svHost.nInstances == 0) LAUNCHT("shadow Tr (host rays)", ctx->stage.shadowTrFastWitness, ctx->walk.grid, ctx->svHost, ws, ctx->fast, ctx->spillArea());
+    else LAUNCH("shadow Tr (host rays)", ctx->stage.shadowTr[0], gridFor(n), ctx->svHost, ws, ctx->stackSpill);
     return 0;
 }
 // The two calls above with the rays' TIMES (rays8), on any scene: the walk is chosen by what the scene is.
@@ -2979,7 +2976,10 @@ int wf_trace_shadow_tr_device(wf_ctx *ctx, int n, const float *rays8, const int3
     ws.trO = t.trO; ws.trD = t.trD; ws.trT = t.trT; ws.trRu = t.trRu; ws.trRl = t.trRl; ws.trRng = t.trRng;
     ws.trQ[0] = t.trQ[0]; ws.trQ[1] = t.trQ[1]; ws.hit = t.hit; ws.hitInst = t.hitInst;
     LAUNCH("shadow Tr (device rays): pack items", k_pack_shadow_items, gridFor(n), n, rays8, t.o, t.d, t.lambdaPdf, timed ? t.pathTime : (float *)nullptr, (F4 *)out_L, t.counters);
-    return LaunchDeviceTr(ctx, ws, n, timed);
+    // the scene's planned route, as the render's own stage runs it (route 1 is for static scenes: only route 0's name tells timed items)
+    LaunchTransmittance(ctx, ws, n, ctx->plan.trRoute, timed, {"shadow Tr (device rays): reset", "shadow Tr (device rays): begin", "shadow Tr (device rays): trace", "shadow Tr (device rays): segment",
+                                                                "shadow Tr (device rays): rest", timed ? "shadow Tr (device rays, timed)" : "shadow Tr (device rays)"});
+    return 0;
 }
 // IntersectOneRandom on the caller's device segments {p0, p1, time}: the kernel of the host-array calls, at the segments' times on a
 // scene with animated primitives
@@ -2990,8 +2990,8 @@ int wf_trace_one_random_device(wf_ctx *ctx, int n, const float *segs7, const int
     if (!segs7 || !material) return fail(-1, "%s: null input array", fn);
     if (!out || !reservoir_pdf) return fail(-1, "%s: null output buffer", fn);
     useDevice(ctx);
-    if (ctx->svHost.haveAnimated) LAUNCH("intersect one random (device segments, timed)", k_trace_one_random<true>, gridFor(n), ctx->svHost, n, segs7, 7, material, segs7 + 6, 7, out, reservoir_pdf, ctx->stackSpill);
-    else LAUNCH("intersect one random (device segments)", k_trace_one_random<false>, gridFor(n), ctx->svHost, n, segs7, 7, material, (const float *)nullptr, 0, out, reservoir_pdf, ctx->stackSpill);
+    if (ctx->svHost.haveAnimated) LAUNCH("intersect one random (device segments, timed)", ctx->stage.traceOneRandom[1], gridFor(n), ctx->svHost, n, segs7, 7, material, segs7 + 6, 7, out, reservoir_pdf, ctx->stackSpill);
+    else LAUNCH("intersect one random (device segments)", ctx->stage.traceOneRandom[0], gridFor(n), ctx->svHost, n, segs7, 7, material, (const float *)nullptr, 0, out, reservoir_pdf, ctx->stackSpill);
     return 0;
 }
 int wf_device_alloc(wf_ctx *ctx, uint64_t nbytes, void **dptr) {
@@ -3098,8 +3098,8 @@ static int TraceOneRandomHost(wf_ctx *ctx, int n, const float *p0, const float *
     if ((e = tmp.upload(&ds, segs.data(), segs.size())) || (e = tmp.upload(&dm, material, (size_t)n)) || (e = tmp.alloc(&dh, (size_t)n)) || (e = tmp.alloc(&dp, (size_t)n))) return e;
     if (time) {
         if ((e = tmp.upload(&dt, time, (size_t)n))) return e;
-        LAUNCH("intersect one random (host segments, timed)", k_trace_one_random<true>, gridFor(n), ctx->svHost, n, ds, 6, dm, (const float *)dt, 1, dh, dp, ctx->stackSpill);
-    } else LAUNCH("intersect one random (host segments)", k_trace_one_random<false>, gridFor(n), ctx->svHost, n, ds, 6, dm, (const float *)nullptr, 0, dh, dp, ctx->stackSpill);
+        LAUNCH("intersect one random (host segments, timed)", ctx->stage.traceOneRandom[1], gridFor(n), ctx->svHost, n, ds, 6, dm, (const float *)dt, 1, dh, dp, ctx->stackSpill);
+    } else LAUNCH("intersect one random (host segments)", ctx->stage.traceOneRandom[0], gridFor(n), ctx->svHost, n, ds, 6, dm, (const float *)nullptr, 0, dh, dp, ctx->stackSpill);
     HIPCHK(hipMemcpyAsync(out, dh, (size_t)n * sizeof(wf_hit_record), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(reservoir_pdf, dp, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));

@@ -242,6 +242,12 @@ static void ClassifyScene(const wf_scene_desc *d, const Switches &sw, ScenePlan 
         const bool few = (int64_t)d->n_quadrics * 16 <= (int64_t)d->n_triangles;
         plan->deferGeneral = sw.deferGeneral >= 0 ? sw.deferGeneral != 0 : few;
     }
+    // the stage kernels' remaining variants (genMode is final here)
+    plan->cameraAnim = d->camera.anim.actually_animated;
+    plan->trFastAlpha = plan->haveAlpha || d->n_quadrics > 0;
+    plan->routeVariant = plan->haveAnimated ? 2 : (plan->genMode > 1 || plan->nInstances > 0) ? 1 : 0;
+    const bool visibleSurface = d->film.type == WF_FILM_GBUFFER || plan->cameraAnim || plan->haveAnimated || (plan->haveCurves && plan->haveQuadricAlpha);
+    for (int t = 0; t < WF_MAT_NTYPES; ++t) plan->shadeVariant[t] = visibleSurface ? 3 : !plan->leanType[t] ? 2 : plan->texNeedsFootprint ? 1 : 0;
 }
 // levels of the reference's binary tree under `root`
 static int RefTreeDepth(const wf_scene_desc *d, int root) {
@@ -303,6 +309,13 @@ int wf::planning::PlanScene(const wf_scene_desc *d, const Switches &sw, ScenePla
     }
     return 0;
 }
+// "<prefix><t>" with t a material type written in digits alone -> t; any other key -> -1
+static int TypeKey(const std::string &k, const char *prefix) {
+    const size_t n = strlen(prefix);
+    if (k.compare(0, n, prefix) != 0 || k.size() == n || k.size() > n + 2 || k.find_first_not_of("0123456789", n) != std::string::npos) return -1;
+    const int t = atoi(k.c_str() + n);
+    return t < WF_MAT_NTYPES ? t : -1;
+}
 // The answers of wf_ctx_query / wf_scene_plan_query that the plan alone gives; false: not one of its keys.
 bool wf::planning::PlanValue(const ScenePlan &plan, const char *key, int64_t *value) {
     const std::string k = key;
@@ -314,11 +327,14 @@ bool wf::planning::PlanValue(const ScenePlan &plan, const char *key, int64_t *va
     else if (k == "lean_shade") *value = plan.leanShade;
     else if (k == "rare_lights") *value = plan.rareLights;
     else if (k == "medium_lean") *value = plan.mediumLean;   // k_medium_sample<true> / k_tr_segment<true>: every medium is homogeneous or a non-emissive uniform grid
-    else if (k.rfind("lean_type_", 0) == 0 && atoi(key + 10) >= 0 && atoi(key + 10) < WF_MAT_NTYPES) *value = plan.leanType[atoi(key + 10)];
+    else if (TypeKey(k, "lean_type_") >= 0) *value = plan.leanType[TypeKey(k, "lean_type_")];
     else if (k == "instances") *value = plan.nInstances;
     else if (k == "nested_animated") *value = plan.nestedAnimated;
     else if (k == "intr_variant") *value = plan.intrVariant;   // k_hit_interaction<GENERAL, CURVE_ALPHA, ANIM> (IntrVariant, wf_plan.h)
     else if (k == "tr_route") *value = plan.trRoute;   // -1 no media, 0 k_shadow_tr, 1 k_shadow_tr_fast, 2 the transmittance wavefront
+    else if (k == "camera_anim") *value = plan.cameraAnim;   // k_gen_camera_rays<ANIM>
+    else if (k == "route_variant") *value = plan.routeVariant;   // 0 k_route_hits<false>, 1 <true>, 2 <true, true>
+    else if (TypeKey(k, "shade_variant_") >= 0) *value = plan.shadeVariant[TypeKey(k, "shade_variant_")];   // k_mat_shade's variant for material type t
     else return false;
     return true;
 }

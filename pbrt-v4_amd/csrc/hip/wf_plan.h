@@ -88,6 +88,13 @@ struct ScenePlan {
     // when such shapes appear elsewhere in the scene (their hits are items of other types' queues)
     bool leanType[WF_MAT_NTYPES] = {};
     bool rareLights = false;     // the scene has a light type only the VARIANT 2 material kernels sample (portal infinite lights)
+    bool cameraAnim = false;     // the camera moves: k_gen_camera_rays<ANIM>
+    // The shade kernel of each material type (k_mat_shade's variant): 0 / 1 the LEAN kernels (leanType), without / with the texture
+    // footprint and bump block; 2 general; 3 general + what fills the visible surface (GBuffer film), differentiates a moving camera
+    // and meets animated primitives or alpha-textured curves.  The variants agree bit for bit: a wrong rule here only costs time.
+    int shadeVariant[WF_MAT_NTYPES] = {};
+    int routeVariant = 0;        // the routing pass of the production closest-hit walk: 0 k_route_hits<false>, 1 <true> (general primitives or instances), 2 <true, true> (animated primitives)
+    bool trFastAlpha = false;    // k_shadow_tr_fast<ALPHA>: alpha cut-outs or quadrics (wins over its MLEAN variant: there is no <true, true>)
     // the walk kernels' variants (PickWalkKernels turns these into template instantiations)
     int genMode = 0;             // general-primitive strength of the traversal kernels: 0 triangles only, 1 simple alpha, 2 anything but curves and alpha on quadrics, 3 anything (see GeneralPrims)
     bool deferGeneral = false;   // TWO-CLASS TRAVERSAL (see WalkKernels)

@@ -260,7 +260,8 @@ def test_variant_selection_queries(wfpt):
     # the host-only planning step (Scene.plan, tests/test_scene_plan_host.py) gives, without a device, the answers the uploaded scene gives.
     # Both sides read one key table over a PlanScene result, so what this pins is that the upload keeps the plan as it was made (and that
     # the context's copy is the one queried); the values themselves are pinned above and in the CPU suite.
-    shared = ["fast_ok", "gen_mode", "gen_tri", "defer_general", "anim_fast", "lean_shade", "rare_lights", "medium_lean", "instances", "nested_animated"] + ["lean_type_%d" % t for t in range(11)]
+    shared = ["fast_ok", "gen_mode", "gen_tri", "defer_general", "anim_fast", "lean_shade", "rare_lights", "medium_lean", "instances", "nested_animated", "camera_anim", "route_variant"] + \
+        ["lean_type_%d" % t for t in range(11)] + ["shade_variant_%d" % t for t in range(11)]
     for name in ["cornell64", "instances_quadrics", "media_box", "media_instances", "cloud_medium", "rgbgrid_medium", "tempgrid_medium", "animated", "animated_sss", "animated_tris",
                  "animated_tris_alpha", "animated_interface", "animated_interface_sphere", "animated_mix", "animated_subsurface", "animated_in_definition", "animated_in_definition_general", "animated_in_definition_media",
                  "animated_in_definition_sss"]:

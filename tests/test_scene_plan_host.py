@@ -91,3 +91,110 @@ def test_rejected_description_fails_in_the_planning_step(wfpt):
         assert s.plan("fast_ok") == 1
     finally:
         s.close()
+
+
+# ---- the stage kernels' variants: "shade_variant_<t>", "route_variant", "camera_anim" (ScenePlan::shadeVariant, routeVariant, cameraAnim) ----
+# Each expected value is worked out here with the rule the launch site applied while the choice was still made there (EvalMaterial's `v`,
+# the three-way choice around "Route hits", the `?:` of "Generate camera rays"), from facts read off the scene file — not read back from
+# the plan.  The variants of a material kernel agree bit for bit, so a wrong rule would be a slowdown no parity test sees.
+DIFFUSE, CONDUCTOR, DIELECTRIC, THIN_DIELECTRIC, DIFFUSE_TRANSMISSION, COATED_DIFFUSE, COATED_CONDUCTOR = range(1, 8)   # wf_material_type
+
+
+def _shade_rule(gbuffer, moving_camera, animated, alpha_curves, lean, footprint):
+    """EvalMaterial: 3 the visible-surface variant (any of its four conditions), else 2 general, else the lean kernel with (1) or without (0) the texture footprint"""
+    if gbuffer or moving_camera or animated or alpha_curves:
+        return 3
+    return 2 if not lean else (1 if footprint else 0)
+
+
+def _route_rule(animated, general, instanced):
+    """wf_intersect_closest: k_route_hits<true, true> for animated primitives, <true> for general primitives (genMode > 1) or instances, else <false>"""
+    return 2 if animated else (1 if general or instanced else 0)
+
+
+# scene -> the material types it uses, which condition of the visible-surface variant it meets (if any), whether a texture needs a
+# footprint (an image map, a displacement), and the types that are lean under the default switches: none of their materials on a shape
+# that is not a triangle, every texture of the scene a constant, an image map or a bilerp, nothing animated
+SHADE_SCENES = {
+    # triangles, constant reflectances only
+    "cornell64": dict(types=[DIFFUSE], lean=[DIFFUSE]),
+    # triangles; image-map reflectance / roughness and image-map displacement
+    "image_textures": dict(types=[DIFFUSE, CONDUCTOR], lean=[DIFFUSE, CONDUCTOR], footprint=True),
+    # disks and cylinders only
+    "quadrics": dict(types=[DIFFUSE, CONDUCTOR, DIELECTRIC], lean=[]),
+    # Film "gbuffer" (its "scale" / "mix" textures would make it general otherwise)
+    "gbuffer_film": dict(types=[DIFFUSE, CONDUCTOR, DIELECTRIC, THIN_DIELECTRIC, DIFFUSE_TRANSMISSION, COATED_DIFFUSE, COATED_CONDUCTOR], lean=[], gbuffer=True),
+    # image_textures under a camera with two transformations (ActiveTransform StartTime / EndTime before Camera)
+    "camera_motion": dict(types=[DIFFUSE, CONDUCTOR], lean=[DIFFUSE, CONDUCTOR], footprint=True, moving_camera=True),
+    # triangle meshes under two transformations
+    "animated_tris": dict(types=[DIFFUSE, CONDUCTOR, COATED_DIFFUSE], lean=[], animated=True),
+    # curves, some with "texture alpha" / "float alpha"
+    "curves_alpha": dict(types=[DIFFUSE, DIELECTRIC, COATED_DIFFUSE], lean=[], alpha_curves=True),
+    # WF_LEAN_PER_TYPE, a lean type beside general ones (instances_quadrics does not qualify: its checkerboard texture makes every type
+    # general): diffuse on triangle meshes only, coated diffuse and conductor on spheres; constant textures
+    "portal_light": dict(types=[DIFFUSE, CONDUCTOR, COATED_DIFFUSE], lean=[DIFFUSE]),
+    # ... and with a footprint: coated diffuse (with a normal map) on triangles only, diffuse on a bilinear patch and a sphere too, conductor on a sphere; image maps
+    "png_textures": dict(types=[DIFFUSE, CONDUCTOR, COATED_DIFFUSE], lean=[COATED_DIFFUSE], footprint=True),
+}
+# what the rule comes to, scene by scene (the scenes not named: 3 for every type, each by a different one of the four conditions)
+SHADE_EXPECTED = {"cornell64": {DIFFUSE: 0}, "image_textures": {DIFFUSE: 1, CONDUCTOR: 1}, "quadrics": {DIFFUSE: 2, CONDUCTOR: 2, DIELECTRIC: 2},
+                  "portal_light": {DIFFUSE: 0, CONDUCTOR: 2, COATED_DIFFUSE: 2}, "png_textures": {DIFFUSE: 2, CONDUCTOR: 2, COATED_DIFFUSE: 1}}
+VISIBLE_SURFACE = ["gbuffer_film", "camera_motion", "animated_tris", "curves_alpha"]
+
+
+def _check_shade_variants(wfpt, name, lean_types):
+    f = SHADE_SCENES[name]
+    types = f["types"]
+    p = plan(wfpt, name, ["lean_type_%d" % t for t in types] + ["shade_variant_%d" % t for t in types])
+    # the scene is in the class it is listed for (the lean types are the plan's older keys, pinned before this one existed)
+    lean = {t: int(t in lean_types) for t in types}
+    assert {t: p["lean_type_%d" % t] for t in types} == lean, p
+    want = {t: _shade_rule(f.get("gbuffer", False), f.get("moving_camera", False), f.get("animated", False), f.get("alpha_curves", False), lean[t], f.get("footprint", False))
+            for t in types}
+    assert {t: p["shade_variant_%d" % t] for t in types} == want, p
+    return want
+
+
+@pytest.mark.parametrize("name", sorted(SHADE_SCENES))
+def test_shade_variant_follows_the_launch_site_rule(wfpt, name):
+    want = _check_shade_variants(wfpt, name, SHADE_SCENES[name]["lean"])
+    assert want == SHADE_EXPECTED.get(name, {t: 3 for t in SHADE_SCENES[name]["types"]}), want
+    assert (name in VISIBLE_SURFACE) == (name not in SHADE_EXPECTED)
+
+
+@pytest.mark.parametrize("name", sorted(SHADE_SCENES))
+def test_shade_variant_without_the_lean_kernels(wfpt, monkeypatch, name):
+    monkeypatch.setenv("WF_LEAN_SHADE", "0")
+    want = _check_shade_variants(wfpt, name, [])
+    assert set(want.values()) == {3 if name in VISIBLE_SURFACE else 2}, want
+
+
+@pytest.mark.parametrize("name", ["portal_light", "png_textures"])
+def test_shade_variant_without_the_per_type_lean_kernels(wfpt, monkeypatch, name):
+    monkeypatch.setenv("WF_LEAN_PER_TYPE", "0")
+    assert set(_check_shade_variants(wfpt, name, []).values()) == {2}
+
+
+# cornell64: triangles only, no ObjectInstance; media_instances: plain triangle meshes under ObjectInstance; quadrics: disks and cylinders
+# (gen_mode 2), no instances; instances: ObjectInstance and a checkerboard alpha cut-out (a texture graph: gen_mode 2) — both conditions
+# of <true> at once; animated_tris: moving meshes (each an instance)
+@pytest.mark.parametrize("name,animated,general,instanced,variant", [("cornell64", False, False, False, 0), ("media_instances", False, False, True, 1), ("quadrics", False, True, False, 1),
+                                                                      ("instances", False, True, True, 1), ("animated_tris", True, False, True, 2)])
+def test_route_variant_follows_the_launch_site_rule(wfpt, name, animated, general, instanced, variant):
+    p = plan(wfpt, name, ["gen_mode", "instances", "anim_fast", "route_variant"])
+    assert (p["gen_mode"] > 1, p["instances"] > 0) == (general, instanced), p
+    assert p["route_variant"] == _route_rule(animated, general, instanced) == variant, p
+    assert p["anim_fast"] == animated
+
+
+def test_camera_anim(wfpt):
+    """camera_motion: ActiveTransform StartTime / EndTime give the camera two transformations; cornell64: one LookAt"""
+    assert plan(wfpt, "camera_motion", ["camera_anim"]) == {"camera_anim": 1}
+    assert plan(wfpt, "cornell64", ["camera_anim"]) == {"camera_anim": 0}
+
+
+@pytest.mark.parametrize("key", ["shade_variant_", "shade_variant_x", "shade_variant_1x", "shade_variant_-1", "shade_variant_11", "lean_type_", "lean_type_x"])
+def test_a_type_key_needs_a_type_in_digits(wfpt, key):
+    """(a key without a number used to answer for type 0)"""
+    with pytest.raises(wfpt.WfError, match="unknown key"):
+        plan(wfpt, "cornell64", [key])

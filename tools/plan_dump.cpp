@@ -74,6 +74,8 @@ static void DumpScene(const std::string &path, int nRays, bool tables) {
     for (bool b : p.leanType) putchar('0' + b);
     printf(" rareLights=%d genMode=%d deferGeneral=%d genTri=%d fastBuilt=%d fastOk=%d animFast=%d cursorChunk=%d cursorChunkShadow=%d spillRows=%d trRoute=%d",
            p.rareLights, p.genMode, p.deferGeneral, p.genTri, p.fastBuilt, p.fastOk, p.animFast, p.cursorChunk, p.cursorChunkShadow, p.spillRows, p.trRoute);
+    printf(" cameraAnim=%d routeVariant=%d trFastAlpha=%d shadeVariant=", p.cameraAnim, p.routeVariant, p.trFastAlpha);
+    for (int v : p.shadeVariant) putchar('0' + v);
     if (!p.fastBuilt) { printf(" trees: no production layout\n"); return; }
     const FastBVH &h = trees.header;
     uint64_t hh = Fnv(&h.nNodes, sizeof h.nNodes);   // the header's fields one by one: no padding, no pointers
