@@ -545,6 +545,9 @@ static int Main(int argc, char **argv) {
     if (F.type == WF_FILM_GBUFFER) { ws.vsP = Alloc<F4>(n); ws.vsN = Alloc<F4>(n); ws.vsNs = Alloc<F4>(n); ws.vsDpdx = Alloc<F4>(n); ws.vsDpdy = Alloc<F4>(n); ws.vsAlbedo = Alloc<F4>(n); }
     ws.stats = Alloc<unsigned long long>(129);
     unsigned long long nodesVisited = 0, trisTested = 0, sssProbes = 0, sssExits = 0;
+    // per material type: the items its queue held over the render, every depth (what the device's wf_material_items_download counts: the
+    // last depth's queue is filled and never evaluated), and the items the material stage evaluated (every depth but the last)
+    unsigned long long matQueued[WF_MAT_NTYPES] = {}, matEvaluated[WF_MAT_NTYPES] = {};
     std::atomic<unsigned long long> shadowNodes{0}, shadowTris{0};
 
 
@@ -815,6 +818,10 @@ static int Main(int argc, char **argv) {
                 ParallelFor(ws.counters[(CNT_ESCAPED) * CNT_STRIDE], [&](int i) { KHandleEscaped(sv, ws, cur, i); });
                 ParallelFor(ws.counters[(CNT_HITLIGHT) * CNT_STRIDE], [&](int i) { KHandleEmissive(sv, ws, cur, i); });
                 traceL("emitted", depth);
+                for (int m = 0; m < WF_MAT_NTYPES; ++m) {
+                    matQueued[m] += ws.counters[(CNT_MAT0 + m) * CNT_STRIDE];
+                    if (depth != maxDepth) matEvaluated[m] += ws.counters[(CNT_MAT0 + m) * CNT_STRIDE];
+                }
                 if (depth == maxDepth) break;
                 // in the order of the reference's Material::Types (base/material.h:36-39; ForEachType, integrator.cpp EvaluateMaterialsAndBSDFs): the image
                 // does not depend on it, but the ORDER of the next ray queue does, and with it which medium-sample slot a ray gets at the next
@@ -905,6 +912,10 @@ static int Main(int argc, char **argv) {
     }
     if (false) printf("], \"shadow_rays\": [");
     for (int d = 0; d < 64; ++d) printf("%s%llu", d ? ", " : "", ws.stats[65 + d]);
+    printf("], \"material_items\": [");
+    for (int m = 0; m < WF_MAT_NTYPES; ++m) printf("%s%llu", m ? ", " : "", matQueued[m]);
+    printf("], \"material_items_evaluated\": [");
+    for (int m = 0; m < WF_MAT_NTYPES; ++m) printf("%s%llu", m ? ", " : "", matEvaluated[m]);
     printf("]}\n");
 
     if (!dumpFilm.empty()) {

@@ -200,6 +200,8 @@ static void ClassifyScene(const wf_scene_desc *d, const Switches &sw, ScenePlan 
     }
     // ... and, since round 5, emitters that are not triangles (sphere / disk / cylinder / patch / curve lights: an out-of-line sampler of
     // 214 VGPRs) and emitters with an alpha texture (the texture-graph evaluator): LightSampleLi<RARE>, AreaLightL<ALPHA> (wf_lights.h)
+    // (WF_RARE_LIGHTS=1 forces both: the RARE kernels are supersets, they sample every light type)
+    if (sw.rareLights) plan->rareLights = plan->portalLights = true;
     for (int i = 0; i < d->n_lights; ++i) {
         const wf_light &l = d->lights[i];
         if (l.type == WF_LIGHT_PORTAL_INFINITE) plan->rareLights = plan->portalLights = true;
@@ -246,7 +248,8 @@ static void ClassifyScene(const wf_scene_desc *d, const Switches &sw, ScenePlan 
     plan->cameraAnim = d->camera.anim.actually_animated;
     plan->trFastAlpha = plan->haveAlpha || d->n_quadrics > 0;
     plan->routeVariant = plan->haveAnimated ? 2 : (plan->genMode > 1 || plan->nInstances > 0) ? 1 : 0;
-    const bool visibleSurface = d->film.type == WF_FILM_GBUFFER || plan->cameraAnim || plan->haveAnimated || (plan->haveCurves && plan->haveQuadricAlpha);
+    // (WF_VISIBLE_SURFACE=1 forces it: variant 3 is a superset of the others, and its visible-surface store is guarded by the film's type)
+    const bool visibleSurface = sw.visibleSurface || d->film.type == WF_FILM_GBUFFER || plan->cameraAnim || plan->haveAnimated || (plan->haveCurves && plan->haveQuadricAlpha);
     for (int t = 0; t < WF_MAT_NTYPES; ++t) plan->shadeVariant[t] = visibleSurface ? 3 : !plan->leanType[t] ? 2 : plan->texNeedsFootprint ? 1 : 0;
 }
 // levels of the reference's binary tree under `root`
@@ -325,7 +328,8 @@ bool wf::planning::PlanValue(const ScenePlan &plan, const char *key, int64_t *va
     else if (k == "defer_general") *value = plan.deferGeneral;
     else if (k == "anim_fast") *value = plan.animFast;
     else if (k == "lean_shade") *value = plan.leanShade;
-    else if (k == "rare_lights") *value = plan.rareLights;
+    else if (k == "rare_lights") *value = plan.rareLights;     // k_mat_nee<t, RARE>, k_medium_scatter<RARE>
+    else if (k == "portal_lights") *value = plan.portalLights; // k_handle_escaped<RARE>
     else if (k == "medium_lean") *value = plan.mediumLean;   // k_medium_sample<true> / k_tr_segment<true>: every medium is homogeneous or a non-emissive uniform grid
     else if (TypeKey(k, "lean_type_") >= 0) *value = plan.leanType[TypeKey(k, "lean_type_")];
     else if (k == "instances") *value = plan.nInstances;

@@ -24,6 +24,8 @@ struct Switches {
     bool mediumLean = true;       // WF_MEDIUM_LEAN=0
     bool leanShade = true;        // WF_LEAN_SHADE=0
     bool leanPerType = true;      // WF_LEAN_PER_TYPE=0
+    bool visibleSurface = false;  // WF_VISIBLE_SURFACE=1: every material type takes shade variant 3, whatever the scene (on only: a scene that needs it keeps it)
+    bool rareLights = false;      // WF_RARE_LIGHTS=1: the RARE kernels (k_mat_nee<t, true>, k_medium_scatter<true>, k_handle_escaped<true>), whatever the scene's lights (on only)
     int deferGeneral = -1;        // WF_DEFER_GENERAL=1 | 0 forces / forbids the two-class traversal; -1 (unset): by the scene's counts
     bool noFast = false;          // WF_NO_FAST (set to anything): the reference-order walks only
     bool animFast = true;         // WF_ANIM_FAST=0
@@ -51,6 +53,8 @@ struct Switches {
         s.mediumLean = on("WF_MEDIUM_LEAN");
         s.leanShade = on("WF_LEAN_SHADE");
         s.leanPerType = on("WF_LEAN_PER_TYPE");
+        s.visibleSurface = number("WF_VISIBLE_SURFACE", 0) != 0;
+        s.rareLights = number("WF_RARE_LIGHTS", 0) != 0;
         if (isSet("WF_DEFER_GENERAL")) s.deferGeneral = number("WF_DEFER_GENERAL", 0) != 0;
         s.noFast = isSet("WF_NO_FAST");
         s.animFast = on("WF_ANIM_FAST");

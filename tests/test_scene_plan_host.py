@@ -96,7 +96,8 @@ def test_rejected_description_fails_in_the_planning_step(wfpt):
 # ---- the stage kernels' variants: "shade_variant_<t>", "route_variant", "camera_anim" (ScenePlan::shadeVariant, routeVariant, cameraAnim) ----
 # Each expected value is worked out here with the rule the launch site applied while the choice was still made there (EvalMaterial's `v`,
 # the three-way choice around "Route hits", the `?:` of "Generate camera rays"), from facts read off the scene file — not read back from
-# the plan.  The variants of a material kernel agree bit for bit, so a wrong rule would be a slowdown no parity test sees.
+# the plan.  The variants of a material kernel agree bit for bit (every one of them is rendered and compared on the device by
+# tests/test_material_matrix_gpu.py), so a wrong rule would be a slowdown no parity test sees.
 DIFFUSE, CONDUCTOR, DIELECTRIC, THIN_DIELECTRIC, DIFFUSE_TRANSMISSION, COATED_DIFFUSE, COATED_CONDUCTOR = range(1, 8)   # wf_material_type
 
 
@@ -173,6 +174,37 @@ def test_shade_variant_without_the_lean_kernels(wfpt, monkeypatch, name):
 def test_shade_variant_without_the_per_type_lean_kernels(wfpt, monkeypatch, name):
     monkeypatch.setenv("WF_LEAN_PER_TYPE", "0")
     assert set(_check_shade_variants(wfpt, name, []).values()) == {2}
+
+
+@pytest.mark.parametrize("name", sorted(SHADE_SCENES))
+def test_visible_surface_switch_forces_variant_3_and_only_on(wfpt, monkeypatch, name):
+    """WF_VISIBLE_SURFACE=1: every type takes the superset kernel, whatever the scene (the lean classification itself is untouched);
+    =0 is "unset": a scene that needs variant 3 keeps it, every other scene its own plan"""
+    types = SHADE_SCENES[name]["types"]
+    keys = ["lean_type_%d" % t for t in types] + ["rare_lights"]
+    before = plan(wfpt, name, keys)
+    monkeypatch.setenv("WF_VISIBLE_SURFACE", "1")
+    assert plan(wfpt, name, ["shade_variant_%d" % t for t in range(1, 11)]) == {"shade_variant_%d" % t: 3 for t in range(1, 11)}
+    assert plan(wfpt, name, keys) == before
+    monkeypatch.setenv("WF_VISIBLE_SURFACE", "0")
+    want = _check_shade_variants(wfpt, name, SHADE_SCENES[name]["lean"])
+    assert want == SHADE_EXPECTED.get(name, {t: 3 for t in types}), want
+
+
+# cornell64: one triangle emitter; portal_light: a portal infinite light; bilinear_lights: emissive bilinear patches; arealight_alpha:
+# alpha-masked triangle emitters — the last three are RARE by themselves
+@pytest.mark.parametrize("name,rare,portal", [("cornell64", 0, 0), ("image_textures", 0, 0), ("portal_light", 1, 1), ("bilinear_lights", 1, 0), ("arealight_alpha", 1, 0)])
+def test_rare_lights_switch_forces_the_rare_kernels_and_only_on(wfpt, monkeypatch, name, rare, portal):
+    """WF_RARE_LIGHTS=1: k_mat_nee<t, true>, k_medium_scatter<true> ("rare_lights") and k_handle_escaped<true> ("portal_lights") whatever the scene's lights;
+    =0 is "unset": a scene with such lights keeps them.  The shade variants do not depend on it."""
+    keys = ["shade_variant_%d" % t for t in range(1, 11)]
+    before = plan(wfpt, name, keys)
+    assert plan(wfpt, name, ["rare_lights", "portal_lights"]) == {"rare_lights": rare, "portal_lights": portal}
+    monkeypatch.setenv("WF_RARE_LIGHTS", "1")
+    assert plan(wfpt, name, ["rare_lights", "portal_lights"]) == {"rare_lights": 1, "portal_lights": 1}
+    assert plan(wfpt, name, keys) == before
+    monkeypatch.setenv("WF_RARE_LIGHTS", "0")
+    assert plan(wfpt, name, ["rare_lights", "portal_lights"]) == {"rare_lights": rare, "portal_lights": portal}
 
 
 # cornell64: triangles only, no ObjectInstance; media_instances: plain triangle meshes under ObjectInstance; quadrics: disks and cylinders

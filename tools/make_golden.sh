@@ -177,3 +177,6 @@ oracle/_ref/pbrt_ref --wavefront --quiet --seed 0 --spp 4 --outfile $G/animated_
 oracle/_ref/pbrt_ref --wavefront --quiet --seed 0 --spp 4 --outfile $G/face_indices_ref.pfm $G/face_indices.pbrt
 # the transmittance wavefront's ANIM variants (hand-written: a moving interface box in an RGB grid, a moving alpha cut-out, the louvres; reads checker01.pfm)
 oracle/_ref/pbrt_ref --wavefront --quiet --seed 0 --spp 4 --outfile $G/animated_tr_routes_ref.pfm $G/animated_tr_routes.pbrt
+# the material-kernel matrix (hand-written: ten triangle quads, one per material type; constant textures / image maps and bilerps) — tests/variant_matrix_cases.py
+oracle/_ref/pbrt_ref --wavefront --quiet --seed 0 --spp 4 --outfile $G/matrix_lean_ref.pfm $G/matrix_lean.pbrt
+oracle/_ref/pbrt_ref --wavefront --quiet --seed 0 --spp 4 --outfile $G/matrix_lean_tex_ref.pfm $G/matrix_lean_tex.pbrt

@@ -19,7 +19,7 @@ sys.path.insert(0, '$ROOT/tools')
 import make_scenes
 for n in make_scenes.BENCH_SMALL: make_scenes.bench_small(n, '$TMP/' + n)
 " > /dev/null || exit 1
-unset WF_BRAID WF_BRAID_MIN_FRAC WF_TIGHT_INSTANCES WF_LEAF_COLLAPSE WF_BRAID_VERBOSE WF_NO_FAST WF_ANIM_FAST WF_DEFER_GENERAL WF_LEAN_SHADE WF_LEAN_PER_TYPE WF_MEDIUM_LEAN
+unset WF_BRAID WF_BRAID_MIN_FRAC WF_TIGHT_INSTANCES WF_LEAF_COLLAPSE WF_BRAID_VERBOSE WF_NO_FAST WF_ANIM_FAST WF_DEFER_GENERAL WF_LEAN_SHADE WF_LEAN_PER_TYPE WF_MEDIUM_LEAN WF_VISIBLE_SURFACE WF_RARE_LIGHTS
 SCENES=$(ls "$ROOT"/tests/golden/*.pbrt "$TMP"/*/*.pbrt)
 run() {   # run <scene>: one line; a scene file that is no scene of its own (an include) or a crash still gives a line
   local out
