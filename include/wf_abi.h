@@ -802,9 +802,46 @@ int wf_hit_interaction_device(wf_ctx *ctx, int n, const float *rays8, const wf_h
    per-pixel index prefixes): a call for an idle context, not for one with a render in flight.  The host-side pass settings
    (wf_set_pass_samples, the band of the last wf_gen_camera_rays) are left as they were, and the rays are not counted in
    wf_render_stats.camera_rays.  Launched on the context's stream and NOT synchronised.  The camera-ray and
-   filter weights are not handed out, and there is no call that adds a caller's radiance to the film. */
+   filter weights come with wf_camera_samples_device, and wf_film_add_samples_device adds a caller's radiance to the film (both below). */
 int wf_camera_rays_device(wf_ctx *ctx, int y0, int sample_index, int n_max,
                           float *rays8, int32_t *pixel_xy /* [n_max][2] */, float *lambda4 /* [n_max][4] */, int32_t *n_out_device);
+/* ... with the three weights UpdateFilm (wavefront/film.cpp:14-38) reads beside a pixel sample's radiance, in the same ray-queue order:
+   lambda_pdf4[i] = the PDF of the item's four wavelengths, camera_weight4[i] = its camera-ray weight, filter_weight[i] = its filter
+   weight.  The PDF is handed out and not recomputed: it is the one the camera-ray stage sampled, untouched — a caller that terminates
+   the secondary wavelengths (a dispersive refraction) zeroes their PDFs itself, as the render does.  The same preconditions, argument
+   checks and effects as wf_camera_rays_device (allocated queues; overwrites the per-pass state; puts the host-side pass settings back;
+   not counted in the statistics; not synchronised); lambda_pdf4 and camera_weight4 are aligned to 16 bytes, filter_weight to 4. */
+int wf_camera_samples_device(wf_ctx *ctx, int y0, int sample_index, int n_max,
+                             float *rays8, int32_t *pixel_xy /* [n_max][2] */, float *lambda4 /* [n_max][4] */, float *lambda_pdf4 /* [n_max][4] */,
+                             float *camera_weight4 /* [n_max][4] */, float *filter_weight /* [n_max] */, int32_t *n_out_device);
+/* Film::AddSample on a caller's DEVICE items: for item i what UpdateFilm does for a pixel sample of the render (RGBFilm::AddSample /
+   SpectralFilm::AddSample), with the render's arithmetic operation for operation — a caller's samples and the render's go through one
+   film, and wf_film_develop_device develops them.  pixel_xy[i] = the sample's pixel; L4[i] = its radiance ALREADY multiplied by the
+   camera-ray weight (the reference's Lw: the caller does that one fp32 multiply per channel); lambda4 / lambda_pdf4 / filter_weight as
+   wf_camera_samples_device hands them out.  Per item: SafeDiv of L4 by the PDF, the three sensor products times the imaging ratio, the
+   max_component_value rescale, four fp64 adds into the pixel's rgb / weight sums; a spectral film also gets the radiance itself (not
+   divided by the PDF), clamped, into the buckets of the four wavelengths.  A GBuffer film gets the RGB part only: AddSample with a
+   null VisibleSurface (its geometry channels and variance are not touched).  An item whose pixel lies outside the film's pixel bounds
+   is skipped and counted nowhere (UpdateFilm's InsideExclusive test: crop windows); NaN and infinite radiance are added as the render
+   adds them.
+     n_device   NULL, or a device word: min(n, *n_device) items are processed, read by the kernel — the n_out_device of
+                wf_camera_samples_device, without a host synchronisation in between.
+     ONE SAMPLE PER PIXEL PER CALL.  The sums are plain fp64 loads and stores (no fp64 atomics: the result is bit-reproducible), so two
+                items of one call must not name one pixel — what wf_camera_samples_device hands out, one sample index per call; k samples
+                of a pixel are k calls, added in call order by the in-order stream (the render's sample order).  The contract is
+                enforced on the device: the context owns one int32 stamp per film pixel, every item inside the bounds claims its pixel
+                with one returning atomic that writes the call's epoch, and an item that finds the epoch already there is NOT added.
+                Which of two such items is kept is unspecified.  The stamps are allocated by the scene's first call (that call may
+                synchronise for the allocation); the epoch advances with every call and the stamps are cleared when it wraps.
+     rejected_device   NULL, or a device counter the number of items rejected that way is ADDED to (the caller zeroes it).
+   Launched on the context's stream (wf_stream) and NOT synchronised: ordered with the render's launches and with other calls.  Every
+   argument is checked before anything is launched — L4, lambda4 and lambda_pdf4 are aligned to 16 bytes, pixel_xy to 8,
+   filter_weight, n_device and rejected_device to 4; all device pointers of the context's device; n <= 0 touches nothing.  Needs an
+   uploaded scene, no queues.  A strip-partitioned context (wf_set_strips) holds the film of the WHOLE image — the strips only choose
+   which scanlines its render passes cover — so any pixel of the film is accepted there too. */
+int wf_film_add_samples_device(wf_ctx *ctx, int n, const int32_t *n_device /* may be NULL */, const int32_t *pixel_xy /* [n][2] */,
+                               const float *L4 /* [n][4] */, const float *lambda4 /* [n][4] */, const float *lambda_pdf4 /* [n][4] */,
+                               const float *filter_weight /* [n] */, uint32_t *rejected_device /* may be NULL */);
 int wf_device_alloc(wf_ctx *ctx, uint64_t nbytes, void **dptr);
 int wf_device_free(wf_ctx *ctx, void *dptr);
 int wf_device_upload(wf_ctx *ctx, void *dst_device, const void *src_host, uint64_t nbytes);

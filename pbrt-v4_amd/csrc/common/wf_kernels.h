@@ -1733,15 +1733,10 @@ WF_HD void KRecordShadowRay(const WorkState &ws, int i, bool occluded) {
 // K13: UpdateFilm (wavefront/film.cpp:14-38) -> RGBFilm::AddSample (film.h:239-255) -> PixelSensor::ToSensorRGB (film.h:95-101)
 // One thread per band pixel p; it adds the pass's sample slots in sample order (the order the reference's
 // successive passes would add them), so the double-precision sums are bit-identical for any samplesPerPass.
-// the RGBFilm part of one item: the sample's sensor RGB times its filter weight, and the weight (what AddSample adds to the pixel's
-// four double accumulators).  Returns false for an item outside the film's pixel bounds.
-WF_HD bool FilmSampleRGBW(const SceneView &sv, const WorkState &ws, int pixelIndex, float out[4], size_t *filmIdx) {
+// The value-taking core of the RGBFilm part: from the weighted radiance Lw = L * cameraRayWeight, the wavelengths and the filter weight
+// to the four addends (also what wf_film_add_samples_device adds for a caller's sample, csrc/hip/wf_film_add.h)
+WF_HD void FilmSensorRGBW(const SceneView &sv, S4 Lw, const Wavelengths &lambda, float filterWeight, float out[4]) {
     const wf_film &F = sv.film;
-    I2 pp = ws.pPixel[pixelIndex];
-    if (!(pp.x >= F.pixel_min[0] && pp.x < F.pixel_max[0] && pp.y >= F.pixel_min[1] && pp.y < F.pixel_max[1])) return false;
-    S4 Lw = toS4(ws.L[pixelIndex]) * toS4(ws.cameraRayWeight[pixelIndex]);
-    Wavelengths lambda = LoadLambda(ws, pixelIndex);
-    float filterWeight = ws.filterWeight[pixelIndex];
     S4 L = SafeDiv(Lw, lambda.PDF());
     float r = F.imaging_ratio * (DenseSample(sv, F.rbar_offset, lambda) * L).Average();
     float g = F.imaging_ratio * (DenseSample(sv, F.gbar_offset, lambda) * L).Average();
@@ -1752,6 +1747,17 @@ WF_HD bool FilmSampleRGBW(const SceneView &sv, const WorkState &ws, int pixelInd
         r *= sc; g *= sc; b *= sc;
     }
     out[0] = filterWeight * r; out[1] = filterWeight * g; out[2] = filterWeight * b; out[3] = filterWeight;
+}
+// the RGBFilm part of one item: the sample's sensor RGB times its filter weight, and the weight (what AddSample adds to the pixel's
+// four double accumulators).  Returns false for an item outside the film's pixel bounds.
+WF_HD bool FilmSampleRGBW(const SceneView &sv, const WorkState &ws, int pixelIndex, float out[4], size_t *filmIdx) {
+    const wf_film &F = sv.film;
+    I2 pp = ws.pPixel[pixelIndex];
+    if (!(pp.x >= F.pixel_min[0] && pp.x < F.pixel_max[0] && pp.y >= F.pixel_min[1] && pp.y < F.pixel_max[1])) return false;
+    S4 Lw = toS4(ws.L[pixelIndex]) * toS4(ws.cameraRayWeight[pixelIndex]);
+    Wavelengths lambda = LoadLambda(ws, pixelIndex);
+    float filterWeight = ws.filterWeight[pixelIndex];
+    FilmSensorRGBW(sv, Lw, lambda, filterWeight, out);
     const int width = F.pixel_max[0] - F.pixel_min[0];
     *filmIdx = (size_t)(pp.y - F.pixel_min[1]) * width + (pp.x - F.pixel_min[0]);
     return true;

@@ -41,6 +41,7 @@
 #include "wf_plan.h"
 #include "wf_film_develop.h"
 #include "wf_boundary_intr.h"
+#include "wf_film_add.h"
 
 using namespace wf;
 using namespace wf::planning;
@@ -170,6 +171,8 @@ struct wf_ctx {
     } trScratch;
     int32_t *probeCursor = nullptr;
     unsigned long long *developNaN = nullptr;   // wf_film_develop_*_device's NaN counter (allocated by the first call that asks for the count)
+    int32_t *filmStamps = nullptr;   // wf_film_add_samples_device: per film pixel, the epoch of the last call that added to it (allocated by the scene's first call)
+    int32_t filmEpoch = 0;           // ... the last call's epoch, 1 .. INT32_MAX (then the stamps are zeroed and the epochs start over)
     int W = 0, H = 0;
     int maxDepth = 5;
     float sceneBounds[6] = {};
@@ -2902,15 +2905,20 @@ int wf_hit_interaction_device(wf_ctx *ctx, int n, const float *rays8, const wf_h
     if (e) return fail(e, "%s: the launch failed: %s", fn, e < 0 ? "the library holds no kernel for the scene's intr_variant" : hipGetErrorString((hipError_t)e));
     return 0;
 }
-int wf_camera_rays_device(wf_ctx *ctx, int y0, int sample_index, int n_max, float *rays8, int32_t *pixel_xy, float *lambda4, int32_t *n_out_device) {
-    const char *fn = "wf_camera_rays_device";
+// wf_camera_rays_device, and with the three weight arrays wf_camera_samples_device (all of them or none): one set of checks, one pass state
+static int CameraRaysDevice(wf_ctx *ctx, const char *fn, bool weights, int y0, int sample_index, int n_max, float *rays8, int32_t *pixel_xy, float *lambda4,
+                            float *lambda_pdf4, float *camera_weight4, float *filter_weight, int32_t *n_out_device) {
     if (!ctx) return fail(-1, "%s: null context", fn);
     if (!ctx->sceneLoaded) return fail(-1, "%s: no scene uploaded", fn);
     if (!ctx->queuesAllocated) return fail(-1, "%s: queues not allocated (wf_queues_alloc)", fn);
     if (!rays8 || !pixel_xy || !lambda4 || !n_out_device)
         return fail(-1, "%s: null %s", fn, !rays8 ? "rays8" : !pixel_xy ? "pixel_xy" : !lambda4 ? "lambda4" : "n_out_device");
+    if (weights && (!lambda_pdf4 || !camera_weight4 || !filter_weight))
+        return fail(-1, "%s: null %s", fn, !lambda_pdf4 ? "lambda_pdf4" : !camera_weight4 ? "camera_weight4" : "filter_weight");
     if (!Aligned16(rays8) || !Aligned16(lambda4) || ((uintptr_t)pixel_xy & 7u) || ((uintptr_t)n_out_device & 3u))
         return fail(-1, "%s: misaligned buffer (rays8 and lambda4: 16 bytes, pixel_xy: 8, n_out_device: 4)", fn);
+    if (weights && (!Aligned16(lambda_pdf4) || !Aligned16(camera_weight4) || ((uintptr_t)filter_weight & 3u)))
+        return fail(-1, "%s: misaligned buffer (lambda_pdf4 and camera_weight4: 16 bytes, filter_weight: 4)", fn);
     if (n_max < ctx->ws.pixelsPerPass) return fail(-1, "%s: n_max = %d, a band holds up to %d rays", fn, n_max, ctx->ws.pixelsPerPass);
     if (sample_index < 0) return fail(-1, "%s: sample_index %d", fn, sample_index);
     // one sample index per call, whatever the last render's passes carried: the pass state is the call's own for its launches and is
@@ -2919,12 +2927,56 @@ int wf_camera_rays_device(wf_ctx *ctx, int y0, int sample_index, int n_max, floa
     ctx->passStep = 1; ctx->passSamples = 1; ctx->ws.slotStride = ctx->pixelMajor ? 1 : 0;
     int e = GenCameraRays(ctx, y0, sample_index, false);
     if (!e) {
-        Prof prof_(ctx, "Pack camera rays (device buffers)");
-        e = boundary::LaunchPackCameraRays(ctx->stream, ctx->ws, n_max, rays8, pixel_xy, lambda4, n_out_device);
+        Prof prof_(ctx, weights ? "Pack camera samples (device buffers)" : "Pack camera rays (device buffers)");
+        e = weights ? boundary::LaunchPackCameraSamples(ctx->stream, ctx->ws, n_max, rays8, pixel_xy, lambda4, lambda_pdf4, camera_weight4, filter_weight, n_out_device)
+                    : boundary::LaunchPackCameraRays(ctx->stream, ctx->ws, n_max, rays8, pixel_xy, lambda4, n_out_device);
         if (e) e = fail(e, "%s: the launch failed: %s", fn, hipGetErrorString((hipError_t)e));
     }
     ctx->passStep = step; ctx->passSamples = samples; ctx->ws.slotStride = slotStride; ctx->passY0 = passY0;
     return e;
+}
+int wf_camera_rays_device(wf_ctx *ctx, int y0, int sample_index, int n_max, float *rays8, int32_t *pixel_xy, float *lambda4, int32_t *n_out_device) {
+    return CameraRaysDevice(ctx, "wf_camera_rays_device", false, y0, sample_index, n_max, rays8, pixel_xy, lambda4, nullptr, nullptr, nullptr, n_out_device);
+}
+int wf_camera_samples_device(wf_ctx *ctx, int y0, int sample_index, int n_max, float *rays8, int32_t *pixel_xy, float *lambda4, float *lambda_pdf4,
+                             float *camera_weight4, float *filter_weight, int32_t *n_out_device) {
+    return CameraRaysDevice(ctx, "wf_camera_samples_device", true, y0, sample_index, n_max, rays8, pixel_xy, lambda4, lambda_pdf4, camera_weight4, filter_weight,
+                            n_out_device);
+}
+// Film::AddSample on a caller's device items (kernel and launcher: wf_film_add.hip).  Everything is checked before anything is launched.
+// The stamps (one int32 per film pixel: the epoch of the last call that added to it) are allocated and zeroed by the scene's first call;
+// epochs run from 1, and when they are used up the stamps are zeroed again, in stream order.
+int wf_film_add_samples_device(wf_ctx *ctx, int n, const int32_t *n_device, const int32_t *pixel_xy, const float *L4, const float *lambda4,
+                               const float *lambda_pdf4, const float *filter_weight, uint32_t *rejected_device) {
+    const char *fn = "wf_film_add_samples_device";
+    if (!ctx) return fail(-1, "%s: null context", fn);
+    if (!ctx->sceneLoaded) return fail(-1, "%s: no scene uploaded", fn);
+    if (n <= 0) return 0;
+    if (!pixel_xy || !L4 || !lambda4 || !lambda_pdf4 || !filter_weight)
+        return fail(-1, "%s: null %s", fn, !pixel_xy ? "pixel_xy" : !L4 ? "L4" : !lambda4 ? "lambda4" : !lambda_pdf4 ? "lambda_pdf4" : "filter_weight");
+    if (!Aligned16(L4) || !Aligned16(lambda4) || !Aligned16(lambda_pdf4))
+        return fail(-1, "%s: %s is not aligned to 16 bytes (an item's four floats are one 16-byte load)", fn, !Aligned16(L4) ? "L4" : !Aligned16(lambda4) ? "lambda4" : "lambda_pdf4");
+    if ((uintptr_t)pixel_xy & 7u) return fail(-1, "%s: pixel_xy is not aligned to 8 bytes", fn);
+    if (((uintptr_t)filter_weight & 3u) || ((uintptr_t)n_device & 3u) || ((uintptr_t)rejected_device & 3u))
+        return fail(-1, "%s: %s is not aligned to 4 bytes", fn, ((uintptr_t)filter_weight & 3u) ? "filter_weight" : ((uintptr_t)n_device & 3u) ? "n_device" : "rejected_device");
+    useDevice(ctx);
+    const size_t pixels = (size_t)ctx->W * ctx->H;
+    if (!ctx->filmStamps) {
+        if (int e = devAlloc(ctx, &ctx->filmStamps, pixels)) return e;   // (zeroed on the context's stream)
+        ctx->filmEpoch = 0;
+    }
+    bool clear;
+    const int32_t epoch = filmadd::NextEpoch(ctx->filmEpoch, &clear);
+    if (clear) HIPCHK(hipMemsetAsync(ctx->filmStamps, 0, pixels * sizeof(int32_t), ctx->stream));
+    ctx->filmEpoch = epoch;
+    filmadd::Args a{};
+    a.film = ctx->ws.film; a.spectral = ctx->ws.filmSpectral; a.stamps = ctx->filmStamps; a.epoch = ctx->filmEpoch;
+    a.n = n; a.nDevice = n_device; a.pixelXY = pixel_xy; a.L4 = L4; a.lambda4 = lambda4; a.lambdaPdf4 = lambda_pdf4; a.filterWeight = filter_weight;
+    a.rejected = rejected_device;
+    Prof prof_(ctx, "Add film samples (device items)");
+    const int e = filmadd::LaunchFilmAdd(ctx->stream, ctx->svDev, a);
+    if (e) return fail(e, "%s: the launch failed: %s", fn, hipGetErrorString((hipError_t)e));
+    return 0;
 }
 // room for n items in ctx->trScratch, the wavefront's arrays among them if the scene's plan routes through it.  Growth waits for the
 // launches that still read the old arrays; a call that fits allocates and waits for nothing.

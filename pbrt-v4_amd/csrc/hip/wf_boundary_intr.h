@@ -18,5 +18,8 @@ int LaunchHitInteraction(hipStream_t stream, int variant, const SceneView *svDev
                          int32_t *outI);
 // k_pack_camera_rays: ray queue 0 of `ws` (at most nMax items) to the caller's arrays, the queue's size to *nOut
 int LaunchPackCameraRays(hipStream_t stream, const WorkState &ws, int nMax, float *rays8, int32_t *pixelXY, float *lambda4, int32_t *nOut);
+// k_pack_camera_samples (wf_camera_samples_device): the same, with the wavelengths' PDF, the camera-ray weight and the filter weight of each item's pixel sample
+int LaunchPackCameraSamples(hipStream_t stream, const WorkState &ws, int nMax, float *rays8, int32_t *pixelXY, float *lambda4, float *lambdaPdf4,
+                            float *cameraWeight4, float *filterWeight, int32_t *nOut);
 
 }}  // namespace wf::boundary

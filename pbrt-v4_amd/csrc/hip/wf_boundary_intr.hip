@@ -5,6 +5,7 @@
 //                                                  (wavefront/intersect.h:72-162): the SurfaceInteraction of every hit record, built by
 //                                                  the functions the material kernels build it with (HitInteraction / IntrWo, wf_shapes.h)
 //   k_pack_camera_rays                             ray queue 0 after "Generate camera rays", as rays8 + pixel + wavelengths
+//   k_pack_camera_samples                          ... plus the wavelengths' PDF, the camera-ray weight and the filter weight (wf_camera_samples_device)
 #include <hip/hip_runtime.h>
 
 #include "../common/wf_kernels.h"
@@ -93,6 +94,30 @@ __global__ void __launch_bounds__(BLOCK) k_pack_camera_rays(WorkState ws, int nM
     }
 }
 
+// ... and with the three weights of the item's pixel sample (wf_camera_samples_device): the wavelengths' PDF as the camera-ray stage
+// sampled it, the camera-ray weight and the filter weight — what UpdateFilm reads beside the radiance.  A kernel of its own, so that
+// k_pack_camera_rays stays the code it was.
+__global__ void __launch_bounds__(BLOCK) k_pack_camera_samples(WorkState ws, int nMax, F4 *__restrict__ rays, I2 *__restrict__ pixel, F4 *__restrict__ lambda4,
+                                                                F4 *__restrict__ lambdaPdf4, F4 *__restrict__ cameraWeight4, float *__restrict__ filterWeight,
+                                                                int32_t *__restrict__ nOut) {
+    int n = ws.counters[CNT_RAY0 * CNT_STRIDE];
+    if (n > nMax) n = nMax;
+    if (n > ws.maxQueueSize) n = ws.maxQueueSize;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *nOut = n;
+    const RayQueueV &q = ws.rq[0];
+    for (int i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) {
+        const F4 o = q.o[i], d = q.d[i];
+        const int pixelIndex = q.meta[i].x;
+        rays[2 * (size_t)i] = F4{o.x, o.y, o.z, d.x};
+        rays[2 * (size_t)i + 1] = F4{d.y, d.z, WF_INFINITY, o.w};
+        pixel[i] = ws.pPixel[pixelIndex];
+        lambda4[i] = ws.lambda[pixelIndex];
+        lambdaPdf4[i] = ws.lambdaPdf[pixelIndex];
+        cameraWeight4[i] = ws.cameraRayWeight[pixelIndex];
+        filterWeight[i] = ws.filterWeight[pixelIndex];
+    }
+}
+
 using IntrFn = void (*)(const SceneView *, int, const F4 *, const I4 *, F4 *, I4 *);
 static IntrFn IntrKernel(int variant) {
     using wf::planning::IntrVariant;
@@ -121,5 +146,12 @@ int wf::boundary::LaunchPackCameraRays(hipStream_t stream, const WorkState &ws, 
     static_assert(sizeof(I2) == 8, "pixel_xy holds two ints per ray");
     hipLaunchKernelGGL(k_pack_camera_rays, dim3(GridFor(nMax)), dim3(BLOCK), 0, stream, ws, nMax, reinterpret_cast<F4 *>(rays8), reinterpret_cast<I2 *>(pixelXY),
                        reinterpret_cast<F4 *>(lambda4), nOut);
+    return (int)hipGetLastError();
+}
+
+int wf::boundary::LaunchPackCameraSamples(hipStream_t stream, const WorkState &ws, int nMax, float *rays8, int32_t *pixelXY, float *lambda4, float *lambdaPdf4,
+                                          float *cameraWeight4, float *filterWeight, int32_t *nOut) {
+    hipLaunchKernelGGL(k_pack_camera_samples, dim3(GridFor(nMax)), dim3(BLOCK), 0, stream, ws, nMax, reinterpret_cast<F4 *>(rays8), reinterpret_cast<I2 *>(pixelXY),
+                       reinterpret_cast<F4 *>(lambda4), reinterpret_cast<F4 *>(lambdaPdf4), reinterpret_cast<F4 *>(cameraWeight4), filterWeight, nOut);
     return (int)hipGetLastError();
 }

@@ -76,6 +76,7 @@ ABI_SYMBOLS = [
     "wf_trace_closest_device_t", "wf_trace_any_device_t", "wf_trace_shadow_tr_device", "wf_trace_one_random_device",
     "wf_film_spectral_upload", "wf_film_gbuffer_upload", "wf_film_channel_count", "wf_film_develop_device", "wf_film_develop_rgb_device",
     "wf_hit_interaction_device", "wf_camera_rays_device",
+    "wf_camera_samples_device", "wf_film_add_samples_device",
 ]
 # the planes of wf_hit_interaction_device (include/wf_abi.h): WF_INTR_FPLANES float planes, WF_INTR_IPLANES int planes, 4 words per item each
 INTR_FPLANES = 11
@@ -500,6 +501,63 @@ class Scene:
         if len(out) == 1:
             return out[0]
         return tuple(torch.cat([o[j] for o in out]) for j in range(3))
+
+    def camera_samples_device(self, sample_index, y0=None):
+        """wf_camera_samples_device: camera_rays_device plus the three weights the film needs — returns (rays8, pixel_xy, lambda4,
+        lambda_pdf4 float32 [n, 4], camera_weight4 float32 [n, 4], filter_weight float32 [n]), in ray-queue order, trimmed to the number
+        of rays generated.  y0 / bands, the synchronisation and the overwritten per-pass state: as camera_rays_device."""
+        import torch
+        _, hip = libs()
+        if not self._renderer:
+            raise WfError("camera_samples_device: create_renderer() first")
+        dev = torch.device("cuda", self.device)
+        cap = self.query("pixels_per_pass")
+        rows = max(1, cap // self.info.width)
+        bands = [y0] if y0 is not None else list(range(self.info.y0, self.info.y0 + self.info.height, rows))
+        parts = []
+        for y in bands:
+            ts = [torch.empty((cap, 8), dtype=torch.float32, device=dev), torch.empty((cap, 2), dtype=torch.int32, device=dev)]
+            ts += [torch.empty((cap, 4), dtype=torch.float32, device=dev) for _ in range(3)]
+            ts += [torch.empty((cap,), dtype=torch.float32, device=dev), torch.zeros((1,), dtype=torch.int32, device=dev)]
+            self._device_call("wf_camera_samples_device", hip.wf_camera_samples_device, [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 7, ts,
+                              y, sample_index, cap, *[t.data_ptr() for t in ts])
+            parts.append(ts)
+        out = []
+        for ts in parts:
+            k = int(ts[-1].item())
+            out.append(tuple(t[:k] for t in ts[:-1]))
+        if len(out) == 1:
+            return out[0]
+        return tuple(torch.cat([o[j] for o in out]) for j in range(6))
+
+    def film_add_device(self, pixel_xy, L4, lambda4, lambda_pdf4, filter_weight, n_device=None, rejected=None):
+        """wf_film_add_samples_device: Film::AddSample for n device items — pixel_xy int32 [n, 2], L4 float32 [n, 4] = the radiance times
+        the camera-ray weight, lambda4 / lambda_pdf4 float32 [n, 4], filter_weight float32 [n] (what camera_samples_device returns).
+        One sample per pixel per call: a second item of one pixel is not added, and counted into `rejected` (an int32 or uint32 tensor
+        of one element that the caller zeroes; None: not counted).  n_device: an int32 tensor of one element; only the first
+        min(n, n_device) items are added, without a host synchronisation.  Not synchronised: ordered with torch's current stream on
+        both sides, like every device-buffer call; image_tensor() / film() see the samples."""
+        import torch
+        _, hip = libs()
+        self._as(pixel_xy, torch.int32, 2, "film_add_device pixel_xy")
+        for t in (L4, lambda4, lambda_pdf4):
+            self._as(t, torch.float32, 4, "film_add_device L4 / lambda4 / lambda_pdf4")
+        self._as(filter_weight, torch.float32, 0, "film_add_device filter_weight")
+        n = pixel_xy.shape[0]
+        ts = [pixel_xy, L4, lambda4, lambda_pdf4, filter_weight]
+        if any(t.shape[0] != n for t in ts):
+            raise WfError("film_add_device: the arrays hold different numbers of items")
+        if n == 0:
+            return
+        for t, what in ((n_device, "n_device"), (rejected, "rejected")):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or t.numel() != 1 or t.element_size() != 4 or t.is_floating_point():
+                raise WfError("film_add_device: %s is a 32-bit integer tensor of one element" % what)
+            ts.append(t)
+        self._device_call("wf_film_add_samples_device", hip.wf_film_add_samples_device, [C.c_void_p, C.c_int] + [C.c_void_p] * 7, ts, n,
+                          n_device.data_ptr() if n_device is not None else None, pixel_xy.data_ptr(), L4.data_ptr(), lambda4.data_ptr(), lambda_pdf4.data_ptr(),
+                          filter_weight.data_ptr(), rejected.data_ptr() if rejected is not None else None)
 
     def first_hit(self, sample_index):
         """The closed loop of the device-buffer boundary: the camera rays of `sample_index`, their closest hits and the hits'

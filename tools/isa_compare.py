@@ -2,8 +2,9 @@
 """tools/isa_compare.py OLD NEW [--allow REGEX] — are two builds' gfx950 device functions the same, instruction for instruction?
 
 OLD and NEW are libraries / object files (dumped with tools/isa_dump.py) or directories isa_dump.py already wrote.  Functions are paired by
-name and compared with the pc-relative literals masked (the `s_add_u32` / `s_addc_u32` after an `s_getpc_b64`: they move whenever the
-functions of a unit sit in another order, no instruction does).  Prints the functions that exist on one side only and those whose bodies
+name and compared with the pc-relative literals masked (the `s_add_u32` / `s_addc_u32` after an `s_getpc_b64`, into an SGPR pair or into
+vcc: they move whenever the functions of a unit sit in another order or gain a neighbour, no instruction does) and the `s_nop` padding
+after a function's last instruction dropped (it depends on what the unit places next).  Prints the functions that exist on one side only and those whose bodies
 differ; exits 1 if any of them does not match --allow (a regular expression over the mangled name: the functions a change is MEANT to
 touch, e.g. the ANIM kernel variants).  This is how "static scenes pay nothing" is shown at build time for a change to shared walk code:
 build the parent commit, build the branch, compare.  Build-time analysis only; nothing is executed on a device.
@@ -13,11 +14,13 @@ import argparse, os, re, sys, tempfile
 
 import isa_dump
 
-_LITERAL = re.compile(r"(s_add_u32|s_addc_u32) (s\d+), (s\d+), (0x[0-9a-f]+|-?\d+)")
+_LITERAL = re.compile(r"(s_add_u32|s_addc_u32) (s\d+|vcc_lo|vcc_hi), (s\d+|vcc_lo|vcc_hi), (0x[0-9a-f]+|-?\d+)")
+# after a function's last instruction: alignment for whatever the unit places next (the disassembler prints a long run's tail as `...`)
+_PADDING = re.compile(r"(\s*(s_nop \d+|\.\.\.))+\s*\Z")
 
 
 def normalised(path):
-    return _LITERAL.sub(r"\1 \2, \3, LIT", open(path).read())
+    return _PADDING.sub("\n", _LITERAL.sub(r"\1 \2, \3, LIT", open(path).read()))
 
 
 def compare(old_dir, new_dir):
