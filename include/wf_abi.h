@@ -925,7 +925,14 @@ int wf_debug_counters(wf_ctx *ctx, uint64_t out[4], int reset);
    production closest-hit walk: 0 triangles only, 1 general primitives or object instances, 2 animated primitives), "shade_variant_<material type>"
    (the type's shade kernel: 0 / 1 lean without / with texture footprints, 2 general, 3 general + visible surface, moving camera, animated
    primitives or alpha-textured curves; the variants agree bit for bit),
-   "pixels_per_pass" (the pixels of one band of wf_queues_alloc, 0 before it: the least n_max of wf_camera_rays_device).
+   "pixels_per_pass" (the pixels of one band of wf_queues_alloc, 0 before it: the least n_max of wf_camera_rays_device),
+   "stage_rounds" / "stage_grid_cap" (WF_STAGE_ROUNDS, WF_STAGE_GRID_CAP as the upload read them: the stage kernels' grids are
+   min(one workgroup per block of the full queue, rounds x the workgroups the chip keeps resident of the kernel), at most the cap),
+   "stage_grid_fallbacks" (launch sites whose occupancy query failed: they keep the fixed bound of 2048 workgroups), "stage_grid_sites"
+   (the number of launch sites) and, per site 0 .. sites - 1, "stage_grid_<site>" (workgroups of its launches; -1: the scene launches
+   nothing there; 0 before wf_queues_alloc), "stage_need_<site>" (one workgroup per block of the full queue) and "stage_resident_<site>"
+   (resident workgroups of its kernel on the whole chip; 0: not known).  "stage_grid:<n_max>:<block>:<per CU>:<CUs>:<rounds>:<cap>"
+   evaluates the grid rule itself for the given numbers.
    Introspection only; nothing in the reference corresponds. */
 int wf_ctx_query(wf_ctx *ctx, const char *key, int64_t *value);
 /* Host-only self-check of the production traversal layout (no device needed; CPU suite, tests/test_fastbvh_host.py): builds the
@@ -946,7 +953,7 @@ int wf_scene_check_instances(const wf_scene_desc *d, int64_t out[4]);
    wf_scene_upload on `d` under the current environment switches (every check of the description, the classification, the production
    trees) and answers the keys that follow from the description alone: "fast_ok", "gen_mode", "gen_tri", "defer_general", "anim_fast",
    "lean_shade", "lean_type_<material type>", "rare_lights", "medium_lean", "instances", "nested_animated", "tr_route", "intr_variant",
-   "camera_anim", "route_variant", "shade_variant_<material type>".  A description that
+   "camera_anim", "route_variant", "shade_variant_<material type>", and "stage_grid:<...>" (the grid rule, whatever the scene).  A description that
    wf_scene_upload would reject fails here with the same message.  Every call plans the scene anew, tree build included: meant for
    tests and tools on small scenes, not for asking many keys of a large one. */
 int wf_scene_plan_query(const wf_scene_desc *d, const char *key, int64_t *value);

@@ -24,6 +24,7 @@
 #include <cstring>
 #include <algorithm>
 #include <map>
+#include <mutex>
 #include <string>
 #include <type_traits>
 #include <utility>
@@ -113,6 +114,29 @@ struct StageKernels {
     MatShadeFn shade[WF_MAT_NTYPES] = {};       // the rows of kMatShade / kMatNee the plan chose; [0]: WF_MAT_INTERFACE has no kernel
     MatNeeFn nee[WF_MAT_NTYPES] = {};
 };
+// STAGE GRIDS (wf_plan.h StageGrid): the launch sites of the render pass whose kernels are grid-stride loops over a queue, and
+// what PickStageGrids found out about the kernel each of them launches for this scene.  ("stage_grid_<site>" of wf_ctx_query counts in
+// this order.)  Not among them: k_reset (one workgroup), the production walks (WalkKernels: resident grids of their own), the near-tie
+// re-trace and the transmittance wavefront's rest (128 workgroups), the film update, and the reference-order walks of a counting pass.
+enum StageSite {
+    SITE_SAMPLE_TOPS, SITE_CAMERA_RAYS, SITE_RAY_SAMPLES, SITE_ROUTE_HITS, SITE_RESOLVE_MIX, SITE_INTERSECT_CLOSEST, SITE_MEDIUM_SAMPLE, SITE_MEDIUM_ROUTE,
+    SITE_MEDIUM_SCATTER, SITE_TR_BEGIN, SITE_TR_SEGMENT, SITE_SHADOW_TR, SITE_HANDLE_ESCAPED, SITE_HANDLE_EMISSIVE, SITE_INTERSECT_SHADOW,
+    SITE_SUBSURFACE_PROBE, SITE_INTERSECT_ONE_RANDOM, SITE_SUBSURFACE_SCATTER,
+    SITE_SHADE0,                              // + material type
+    SITE_NEE0 = SITE_SHADE0 + WF_MAT_NTYPES,   // + material type
+    SITE_COUNT = SITE_NEE0 + WF_MAT_NTYPES
+};
+struct StageGrids {
+    struct Site {
+        bool used = false;      // the scene launches a kernel here
+        int block = 0;          // threads of its workgroups
+        int perCU = 0;          // workgroups of it one CU keeps resident; 0: the query failed, the site keeps the fixed bound
+        bool spillRows = false; // a reference-order walk: indexes wf_ctx::stackSpill by global thread, so its grid stays within MAX_GRID
+    } site[SITE_COUNT];
+    int rounds = 0, cap = 0;    // WF_STAGE_ROUNDS, WF_STAGE_GRID_CAP as the upload read them
+    int nCU = 0;
+    int fallbacks = 0;          // sites in use whose query failed
+};
 
 struct wf_ctx {
     int device = 0;
@@ -146,6 +170,7 @@ struct wf_ctx {
     ScenePlan plan;              // what the uploaded scene runs: written by PlanScene, read by PickWalkKernels / PickStageKernels, the launch sites and wf_queues_alloc
     WalkKernels walk;
     StageKernels stage;
+    StageGrids grids;            // written by PickStageGrids behind PickStageKernels, read by StageGridOf at the launch sites
     // The scratch of wf_trace_shadow_tr_device: the packed shadow-queue items of the call (k_pack_shadow_items), its counter block and —
     // on a scene whose plan routes transmittance through the wavefront (plan.trRoute == 2) — the wavefront's per-item state, index
     // queues and hit records: a call's n has nothing to do with the render's queue size, and the call works without wf_queues_alloc, so
@@ -1467,6 +1492,17 @@ WF_MAT_TYPES(WF_MAT_DECL)
 #define WF_MAT_NEE_ROW(n) {wf_launch_mat_nee_##n##_0, wf_launch_mat_nee_##n##_1},
 static const MatShadeFn kMatShade[WF_MAT_NTYPES][4] = {{}, WF_MAT_TYPES(WF_MAT_SHADE_ROW)};   // [type][shade variant]; row 0: WF_MAT_INTERFACE has no kernel
 static const MatNeeFn kMatNee[WF_MAT_NTYPES][2] = {{}, WF_MAT_TYPES(WF_MAT_NEE_ROW)};         // [type][rare lights]
+// ... and the launchers' siblings, which answer for their units' kernels: resident workgroups per CU (STAGE GRIDS)
+using MatResidentFn = int (*)(int *);
+extern "C" {
+#define WF_MAT_RESIDENT_DECL(n) int wf_resident_mat_shade_##n##_0(int *); int wf_resident_mat_shade_##n##_1(int *); int wf_resident_mat_shade_##n##_2(int *); \
+                                int wf_resident_mat_shade_##n##_3(int *); int wf_resident_mat_nee_##n##_0(int *); int wf_resident_mat_nee_##n##_1(int *);
+WF_MAT_TYPES(WF_MAT_RESIDENT_DECL)
+}
+#define WF_MAT_SHADE_RESIDENT_ROW(n) {wf_resident_mat_shade_##n##_0, wf_resident_mat_shade_##n##_1, wf_resident_mat_shade_##n##_2, wf_resident_mat_shade_##n##_3},
+#define WF_MAT_NEE_RESIDENT_ROW(n) {wf_resident_mat_nee_##n##_0, wf_resident_mat_nee_##n##_1},
+static const MatResidentFn kMatShadeResident[WF_MAT_NTYPES][4] = {{}, WF_MAT_TYPES(WF_MAT_SHADE_RESIDENT_ROW)};
+static const MatResidentFn kMatNeeResident[WF_MAT_NTYPES][2] = {{}, WF_MAT_TYPES(WF_MAT_NEE_RESIDENT_ROW)};
 // bytes of one NeeItem's BxDF (wf_kernels.h) -> 16-byte planes of the record between the two kernels (wf_mat.hip: NeeIO)
 template <int MAT> constexpr int NeePlanesOf() { return 10 + (int)((sizeof(typename MatBxDF<MAT>::T) + 15) / 16); }
 static int NeePlanes(int m) {
@@ -1779,6 +1815,77 @@ static void PickStageKernels(wf_ctx *ctx) {
     k.traceOneRandom[1] = k_trace_one_random<true>; k.traceOneRandom[0] = k_trace_one_random<false>;
     for (int t = 1; t < WF_MAT_NTYPES; ++t) { k.shade[t] = kMatShade[t][p.shadeVariant[t]]; k.nee[t] = kMatNee[t][p.rareLights]; }
 }
+// ---- STAGE GRIDS: the resident workgroups of the kernels PickStageKernels chose and of those the pass names itself, asked once per
+// process, device and kernel (the answer is a property of the code object and the chip).  Only the kernels this scene launches are
+// asked about: a query loads the kernel's code object.  A query that fails — see DESIGN 8 on occupancy queries behind torch's
+// initialisation — fails nothing: its error is taken off the thread's state, the site keeps the fixed bound, and "stage_grid_fallbacks"
+// of wf_ctx_query counts it.  (Failures are not cached: the next upload asks again.)
+static int ResidentPerCU(int device, const void *key, int block, MatResidentFn sibling) {
+    static std::mutex mutex;
+    static std::map<std::pair<int, const void *>, int> known;
+    std::lock_guard<std::mutex> lock(mutex);
+    const auto it = known.find({device, key});
+    if (it != known.end()) return it->second;
+    int perCU = 0;
+    const hipError_t e = sibling ? (hipError_t)sibling(&perCU) : hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, key, block, 0);
+    if (e != hipSuccess || perCU < 1) { (void)hipGetLastError(); return 0; }
+    known[{device, key}] = perCU;
+    return perCU;
+}
+static void PickStageGrids(wf_ctx *ctx, const Switches &sw) {
+    const ScenePlan &p = ctx->plan;
+    const SceneView &sv = ctx->svHost;
+    const StageKernels &k = ctx->stage;
+    StageGrids g;
+    g.rounds = sw.stageRounds;
+    g.cap = sw.stageGridCap;
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, ctx->device) == hipSuccess) g.nCU = prop.multiProcessorCount;
+    else (void)hipGetLastError();
+    // a site the scene launches `kernel` at (or, for a material kernel, the kernel `sibling` answers for)
+    auto use = [&](int site, bool launched, auto kernel, int block = BLOCK, bool spillRows = false, MatResidentFn sibling = nullptr) {
+        if (!launched) return;
+        StageGrids::Site &s = g.site[site];
+        s.used = true;
+        s.block = block;
+        s.spillRows = spillRows;
+        if (g.rounds > 0 && g.nCU > 0) s.perCU = ResidentPerCU(ctx->device, sibling ? (const void *)sibling : (const void *)kernel, block, sibling);
+        if (g.rounds > 0 && s.perCU == 0) ++g.fallbacks;
+    };
+    // (the condition under which wf_queues_alloc allocates ws.sampleTops)
+    use(SITE_SAMPLE_TOPS, sv.sampler.type == WF_SAMPLER_ZSOBOL && 2 * sv.sampler.nBase4Digits <= 32 && !sw.noSampleTops && !sv.haveSubsurface, k_sample_tops);
+    use(SITE_CAMERA_RAYS, true, k.genCameraRays);
+    use(SITE_RAY_SAMPLES, true, k_gen_ray_samples);
+    use(SITE_ROUTE_HITS, p.fastOk, k.routeHits, k.routeBlock);
+    use(SITE_RESOLVE_MIX, p.fastOk && sv.haveMix, k.resolveMix);
+    use(SITE_INTERSECT_CLOSEST, !p.fastOk, k.intersectClosest[0], BLOCK, true);
+    use(SITE_MEDIUM_SAMPLE, sv.haveMedia, k.mediumSample);
+    use(SITE_MEDIUM_ROUTE, sv.haveMedia, k.mediumRoute);
+    use(SITE_MEDIUM_SCATTER, sv.haveMedia, k.mediumScatter);
+    use(SITE_TR_BEGIN, p.trRoute == 2, k_tr_begin);
+    use(SITE_TR_SEGMENT, p.trRoute == 2, k.trSegment);
+    use(SITE_SHADOW_TR, p.trRoute == 0, k.shadowTr[p.haveAnimated], BLOCK, true);
+    use(SITE_HANDLE_ESCAPED, sv.nInfiniteLights > 0, k.handleEscaped);
+    use(SITE_HANDLE_EMISSIVE, true, k_handle_emissive);
+    use(SITE_INTERSECT_SHADOW, !p.fastOk && !sv.haveMedia, k.intersectShadow[0], BLOCK, true);
+    use(SITE_SUBSURFACE_PROBE, sv.haveSubsurface, k_subsurface_probe);
+    use(SITE_INTERSECT_ONE_RANDOM, sv.haveSubsurface, k.intersectOneRandom, BLOCK, true);
+    use(SITE_SUBSURFACE_SCATTER, sv.haveSubsurface, k_subsurface_scatter);
+    for (int t = 1; t < WF_MAT_NTYPES; ++t) {
+        use(SITE_SHADE0 + t, p.matPresent[t], (const void *)nullptr, BLOCK, false, kMatShadeResident[t][p.shadeVariant[t]]);
+        use(SITE_NEE0 + t, p.matPresent[t], (const void *)nullptr, BLOCK, false, kMatNeeResident[t][p.rareLights]);
+    }
+    ctx->grids = g;
+}
+// The workgroups of a launch at `site` over at most n items (StageGrid, wf_plan.h).  `asPicked` = false: the launch is not of the kernel
+// PickStageGrids asked about (a counting pass's walk) and takes the fixed bound.
+static int StageGridOf(const wf_ctx *ctx, int site, int n, bool asPicked = true) {
+    const StageGrids &g = ctx->grids;
+    const StageGrids::Site &s = g.site[site];
+    const int grid = StageGrid(n, s.block > 0 ? s.block : BLOCK, asPicked ? s.perCU : 0, g.nCU, g.rounds, g.cap);
+    return s.spillRows || !asPicked ? std::min(grid, MAX_GRID) : grid;
+}
+static_assert(STAGE_GRID_BOUND == MAX_GRID, "the fixed bound of StageGrid is this unit's MAX_GRID");
 
 extern "C" {
 
@@ -2039,7 +2146,7 @@ static int UploadTables(wf_ctx *ctx, const wf_scene_desc *d, const Switches &sw)
     return 0;
 }
 // ... then the traversal stacks, the production trees and the kernels that walk them
-static int UploadTraversal(wf_ctx *ctx, const FastTrees &trees) {
+static int UploadTraversal(wf_ctx *ctx, const FastTrees &trees, const Switches &sw) {
     const ScenePlan &plan = ctx->plan;
     int e = 0;
     if ((e = devAlloc(ctx, &ctx->stackSpill, (size_t)plan.spillRows * MAX_GRID * BLOCK))) return e;
@@ -2056,6 +2163,7 @@ static int UploadTraversal(wf_ctx *ctx, const FastTrees &trees) {
     }
     if ((e = PickWalkKernels(ctx))) return e;
     PickStageKernels(ctx);
+    PickStageGrids(ctx, sw);
     if ((e = devAlloc(ctx, &ctx->probeCursor, (size_t)1))) return e;
     // the walk on stream3 pushes into spill rows of its own: a column is indexed by the global thread, which both walks have
     if (FrameOverlapScene(ctx) && (e = devAlloc(ctx, &ctx->stackSpill2, (size_t)plan.spillRows * MAX_GRID * BLOCK))) return e;
@@ -2112,6 +2220,7 @@ int wf_scene_upload(wf_ctx *ctx, const wf_scene_desc *d) {
             ctx->fast = FastBVH{};
             ctx->walk = WalkKernels{};
             ctx->stage = StageKernels{};
+            ctx->grids = StageGrids{};
             ctx->plan = ScenePlan{};
             ctx->stackSpill = ctx->stackSpill2 = ctx->dbgWords = nullptr;
             ctx->probeCursor = nullptr;
@@ -2119,7 +2228,7 @@ int wf_scene_upload(wf_ctx *ctx, const wf_scene_desc *d) {
     } rollback{ctx, ctx->allocs.size()};
     ctx->plan = plan;
     int e;
-    if ((e = UploadTables(ctx, d, sw)) || (e = UploadTraversal(ctx, trees)) || (e = UploadFilmAndView(ctx, d))) return e;
+    if ((e = UploadTables(ctx, d, sw)) || (e = UploadTraversal(ctx, trees, sw)) || (e = UploadFilmAndView(ctx, d))) return e;
     rollback.done = true;
     ctx->sceneLoaded = true;
     return 0;
@@ -2133,6 +2242,26 @@ int wf_ctx_query(wf_ctx *ctx, const char *key, int64_t *value) {
     else if (k == "frame_overlap_mode") *value = ctx->frameOverlap;
     else if (k == "skip_last_samples") *value = SkipLastSamples(ctx);
     else if (k == "pixels_per_pass") *value = ctx->queuesAllocated ? ctx->ws.pixelsPerPass : 0;   // the rays a band holds per sample index (wf_camera_rays_device's n_max)
+    else if (k == "stage_rounds") *value = ctx->grids.rounds;
+    else if (k == "stage_grid_cap") *value = ctx->grids.cap;
+    else if (k == "stage_grid_fallbacks") *value = ctx->grids.fallbacks;
+    else if (k == "stage_grid_sites") *value = SITE_COUNT;
+    else if (k.compare(0, 6, "stage_") == 0 && k.find_first_of("0123456789") != std::string::npos && k.find_first_not_of("0123456789", k.find_first_of("0123456789")) == std::string::npos) {
+        // per launch site of the render pass (StageSite's order; -1: the scene launches nothing there): "stage_grid_<site>" the workgroups
+        // of its launches, "stage_need_<site>" one workgroup per `block` items of the full queue, "stage_resident_<site>" the workgroups
+        // the chip keeps resident of its kernel (0: not known, the site keeps the fixed bound)
+        const size_t digits = k.find_first_of("0123456789");
+        const std::string what = k.substr(0, digits);
+        const int site = atoi(k.c_str() + digits);
+        if (site < 0 || site >= SITE_COUNT || (what != "stage_grid_" && what != "stage_need_" && what != "stage_resident_")) return fail(-1, "wf_ctx_query: unknown key '%s'", key);
+        const StageGrids::Site &s = ctx->grids.site[site];
+        const int n = site == SITE_SAMPLE_TOPS ? 5 * ctx->ws.pixelsPerPass : ctx->maxQueueSize;
+        if (!s.used || (site == SITE_SAMPLE_TOPS && ctx->queuesAllocated && !ctx->ws.sampleTops)) *value = -1;
+        else if (what == "stage_resident_") *value = (int64_t)s.perCU * ctx->grids.nCU;
+        else if (!ctx->queuesAllocated) *value = 0;
+        else if (what == "stage_grid_") *value = StageGridOf(ctx, site, n);
+        else *value = (n + s.block - 1) / s.block;
+    }
     else return fail(-1, "wf_ctx_query: unknown key '%s'", key);
     return 0;
 }
@@ -2283,10 +2412,10 @@ int wf_reset_stage_queues(wf_ctx *ctx, int depth) {
 static int GenCameraRays(wf_ctx *ctx, int y0, int sample_index, bool countStats) {
     if (int e = checkReady(ctx)) return e;
     ctx->passY0 = y0;
-    if (ctx->ws.sampleTops) LAUNCH("Sampler index prefixes", k_sample_tops, gridFor(5 * ctx->ws.pixelsPerPass), ctx->svHost, ctx->ws, y0, 0);
+    if (ctx->ws.sampleTops) LAUNCH("Sampler index prefixes", k_sample_tops, StageGridOf(ctx, SITE_SAMPLE_TOPS, 5 * ctx->ws.pixelsPerPass), ctx->svHost, ctx->ws, y0, 0);
     if (ctx->svHost.camera.type == WF_CAMERA_REALISTIC)  // rays blocked by the lenses leave no queue entry: the kernel appends
         LAUNCH("Reset ray queue", k_reset, 1, ctx->ws, 1u << CNT_RAY0, -1, 0);
-    LAUNCH("Generate camera rays", ctx->stage.genCameraRays, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, y0, sample_index, ctx->passStep, ctx->passSamples);
+    LAUNCH("Generate camera rays", ctx->stage.genCameraRays, StageGridOf(ctx, SITE_CAMERA_RAYS, ctx->maxQueueSize), ctx->svHost, ctx->ws, y0, sample_index, ctx->passStep, ctx->passSamples);
     if (countStats) LAUNCH("Update camera ray stats", k_reset, 1, ctx->ws, 0u, STAT_CAMERA, CNT_RAY0);
     return 0;
 }
@@ -2296,8 +2425,8 @@ int wf_gen_ray_samples(wf_ctx *ctx, int depth, int sample_index) {
     // the pixel-only digits of the sample-index permutation, once per pixel and dimension instead of once per ray
     // (needs the band of the pass: the y0 of the last wf_gen_camera_rays)
     const bool tops = ctx->ws.sampleTops != nullptr && ctx->passY0 != INT_MIN;
-    if (tops) LAUNCH("Sampler index prefixes", k_sample_tops, gridFor(5 * ctx->ws.pixelsPerPass), ctx->svHost, ctx->ws, ctx->passY0, 6 + 7 * depth);
-    LAUNCH("Generate ray samples - ZSobolSampler", k_gen_ray_samples, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1, sample_index, ctx->passStep,
+    if (tops) LAUNCH("Sampler index prefixes", k_sample_tops, StageGridOf(ctx, SITE_SAMPLE_TOPS, 5 * ctx->ws.pixelsPerPass), ctx->svHost, ctx->ws, ctx->passY0, 6 + 7 * depth);
+    LAUNCH("Generate ray samples - ZSobolSampler", k_gen_ray_samples, StageGridOf(ctx, SITE_RAY_SAMPLES, ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1, sample_index, ctx->passStep,
            tops ? depth : -1);
     return 0;
 }
@@ -2343,25 +2472,25 @@ int wf_intersect_closest(wf_ctx *ctx, int depth) {
             ctx->retracePending = true;
         }
         const int rb = ctx->stage.routeBlock;
-        LAUNCHB_ON(ctx->stream, "Route hits", ctx->stage.routeHits, std::min(MAX_GRID, std::max(1, (ctx->maxQueueSize + rb - 1) / rb)), rb, ctx->svHost, ctx->ws, depth & 1);
+        LAUNCHB_ON(ctx->stream, "Route hits", ctx->stage.routeHits, StageGridOf(ctx, SITE_ROUTE_HITS, ctx->maxQueueSize), rb, ctx->svHost, ctx->ws, depth & 1);
         if (ctx->retracePending) {
             if (ctx->deferJoin) return 0;   // the fused pass joins after its sample-generation launch (JoinRetrace)
             if (int e = JoinRetrace(ctx)) return e;
         } else if (!RetraceInline(ctx->plan.genMode))
             LAUNCH("Intersect closest: near-tie re-trace", k_closest_retrace, 128, ctx->svHost, ctx->ws, depth & 1, ctx->stackSpill);
-        if (ctx->svHost.haveMix) LAUNCH("Resolve MixMaterial hits", ctx->stage.resolveMix, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
+        if (ctx->svHost.haveMix) LAUNCH("Resolve MixMaterial hits", ctx->stage.resolveMix, StageGridOf(ctx, SITE_RESOLVE_MIX, ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
     } else
-        LAUNCH("Intersect closest", ctx->stage.intersectClosest[ctx->countTraversal], gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1, ctx->stackSpill);
+        LAUNCH("Intersect closest", ctx->stage.intersectClosest[ctx->countTraversal], StageGridOf(ctx, SITE_INTERSECT_CLOSEST, ctx->maxQueueSize, !ctx->countTraversal), ctx->svHost, ctx->ws, depth & 1, ctx->stackSpill);
     return 0;
 }
 // SampleMediumInteraction (wavefront/media.cpp:22-257): K5, then K6 for the Henyey-Greenstein phase function
 int wf_medium_sample(wf_ctx *ctx, int depth) {
     if (int e = checkReady(ctx)) return e;
     if (!ctx->svHost.haveMedia) return 0;
-    LAUNCH("Sample medium interaction", ctx->stage.mediumSample, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
-    LAUNCH("Sample medium interaction: route surface hits", ctx->stage.mediumRoute, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
+    LAUNCH("Sample medium interaction", ctx->stage.mediumSample, StageGridOf(ctx, SITE_MEDIUM_SAMPLE, ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
+    LAUNCH("Sample medium interaction: route surface hits", ctx->stage.mediumRoute, StageGridOf(ctx, SITE_MEDIUM_ROUTE, ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
     if (depth == ctx->maxDepth) return 0;
-    LAUNCH("Sample direct/indirect - Henyey-Greenstein", ctx->stage.mediumScatter, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
+    LAUNCH("Sample direct/indirect - Henyey-Greenstein", ctx->stage.mediumScatter, StageGridOf(ctx, SITE_MEDIUM_SCATTER, ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
     return 0;
 }
 // The transmittance stage's launches over `ws` (n items) by `route` (ScenePlan::trRoute): 2 the wavefront (see k_tr_begin), 1 the per-lane
@@ -2371,16 +2500,16 @@ struct TrNames { const char *reset, *begin, *trace, *segment, *rest, *perLane; }
 static void LaunchTransmittance(wf_ctx *ctx, const WorkState &ws, int n, int route, bool timed, const TrNames &names) {
     if (route == 2) {
         LAUNCH(names.reset, k_reset, 1, ws, (1u << CNT_TR0) | (1u << CNT_TR1), -1, 0);
-        LAUNCH(names.begin, k_tr_begin, gridFor(n), ctx->svHost, ws);
+        LAUNCH(names.begin, k_tr_begin, StageGridOf(ctx, SITE_TR_BEGIN, n), ctx->svHost, ws);
         for (int seg = 0; seg < WF_TR_SEGMENTS; ++seg) {
             const int cur = seg & 1;
             LAUNCHT(names.trace, ctx->walk.trTrace, ctx->walk.grid, ctx->svHost, ws, ctx->fast, cur, ctx->spillArea());
-            LAUNCH(names.segment, ctx->stage.trSegment, gridFor(n), ctx->svHost, ws, cur);
+            LAUNCH(names.segment, ctx->stage.trSegment, StageGridOf(ctx, SITE_TR_SEGMENT, n), ctx->svHost, ws, cur);
             LAUNCH(names.reset, k_reset, 1, ws, 1u << (CNT_TR0 + cur), -1, 0);
         }
         LAUNCH(names.rest, ctx->stage.trRest, 128, ctx->svHost, ws, WF_TR_SEGMENTS & 1, ctx->stackSpill);
     } else if (route == 1) LAUNCHT(names.perLane, ctx->stage.shadowTrFast, ctx->walk.grid, ctx->svHost, ws, ctx->fast, ctx->spillArea());
-    else LAUNCH(names.perLane, ctx->stage.shadowTr[timed], gridFor(n), ctx->svHost, ws, ctx->stackSpill);
+    else LAUNCH(names.perLane, ctx->stage.shadowTr[timed], StageGridOf(ctx, SITE_SHADOW_TR, n, ctx->plan.trRoute == 0 && timed == ctx->plan.haveAnimated), ctx->svHost, ws, ctx->stackSpill);
 }
 // TraceShadowRays with media: IntersectShadowTr (wavefront/aggregate.cpp:70-88, intersect.h:165-274)
 int wf_intersect_shadow_tr(wf_ctx *ctx, int depth) {
@@ -2395,16 +2524,16 @@ int wf_intersect_shadow_tr(wf_ctx *ctx, int depth) {
 int wf_handle_escaped(wf_ctx *ctx, int depth) {
     if (int e = checkReady(ctx)) return e;
     if (ctx->svHost.nInfiniteLights == 0) return 0;  // escapedRayQueue == nullptr (integrator.cpp:496-497)
-    LAUNCH("Handle escaped rays", ctx->stage.handleEscaped, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
+    LAUNCH("Handle escaped rays", ctx->stage.handleEscaped, StageGridOf(ctx, SITE_HANDLE_ESCAPED, ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
     return 0;
 }
 int wf_handle_emissive(wf_ctx *ctx, int depth) {
     if (int e = checkReady(ctx)) return e;
-    LAUNCH("Handle emitters hit by indirect rays", k_handle_emissive, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
+    LAUNCH("Handle emitters hit by indirect rays", k_handle_emissive, StageGridOf(ctx, SITE_HANDLE_EMISSIVE, ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
     return 0;
 }
 static int EvalMaterial(wf_ctx *ctx, int material_type, int depth) {
-    const int g = gridFor(ctx->maxQueueSize), cur = depth & 1;
+    const int cur = depth & 1;
     static const char *names[WF_MAT_NTYPES] = {"", "DiffuseMaterial + BxDF eval (Basic tex)", "ConductorMaterial + BxDF eval (Basic tex)",
                                                "DielectricMaterial + BxDF eval (Basic tex)", "ThinDielectricMaterial + BxDF eval (Basic tex)",
                                                "DiffuseTransmissionMaterial + BxDF eval (Basic tex)", "CoatedDiffuseMaterial + BxDF eval (Basic tex)",
@@ -2413,12 +2542,12 @@ static int EvalMaterial(wf_ctx *ctx, int material_type, int depth) {
     if (material_type == WF_MAT_INTERFACE) return 0;
     if (material_type < 0 || material_type >= WF_MAT_NTYPES) return fail(-1, "material type %d has no HIP kernel", material_type);
     // the two halves (wf_kernels.h MatShade / MatNee; the items' NeeItems stay in ws.neeRec between them), in the plan's variants (shadeVariant, rareLights)
-    { Prof prof_(ctx, names[material_type]); ctx->stage.shade[material_type](ctx->stream, g, &ctx->svHost, &ctx->ws, cur); }
+    { Prof prof_(ctx, names[material_type]); ctx->stage.shade[material_type](ctx->stream, StageGridOf(ctx, SITE_SHADE0 + material_type, ctx->maxQueueSize), &ctx->svHost, &ctx->ws, cur); }
     static const char *neeNames[WF_MAT_NTYPES] = {"", "DiffuseMaterial: next-event estimation", "ConductorMaterial: next-event estimation", "DielectricMaterial: next-event estimation",
                                                   "ThinDielectricMaterial: next-event estimation", "DiffuseTransmissionMaterial: next-event estimation",
                                                   "CoatedDiffuseMaterial: next-event estimation", "CoatedConductorMaterial: next-event estimation",
                                                   "SubsurfaceMaterial: next-event estimation", "HairMaterial: next-event estimation", "MeasuredMaterial: next-event estimation"};
-    { Prof prof_(ctx, neeNames[material_type]); ctx->stage.nee[material_type](ctx->stream, g, &ctx->svHost, &ctx->ws); }
+    { Prof prof_(ctx, neeNames[material_type]); ctx->stage.nee[material_type](ctx->stream, StageGridOf(ctx, SITE_NEE0 + material_type, ctx->maxQueueSize), &ctx->svHost, &ctx->ws); }
     return 0;
 }
 int wf_eval_material(wf_ctx *ctx, int material_type, int depth) {
@@ -2452,7 +2581,7 @@ static int ShadowStage(wf_ctx *ctx, int depth, hipStream_t strm, int *spill) {
         if (k.shadowGen)
             LAUNCHT_ON(strm, "Intersect shadow: rays that met a general primitive", k.shadowGen, k.gridShadowGen, ctx->svHost, ws, ctx->fast, area, (int *)nullptr, ctx->plan.cursorChunkShadow, (const int *)ws.deferQ);
     } else
-        LAUNCH_ON(strm, "Intersect shadow", ctx->stage.intersectShadow[ctx->countTraversal], gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, spill);
+        LAUNCH_ON(strm, "Intersect shadow", ctx->stage.intersectShadow[ctx->countTraversal], StageGridOf(ctx, SITE_INTERSECT_SHADOW, ctx->maxQueueSize, !ctx->countTraversal), ctx->svHost, ctx->ws, spill);
     // "Reset shadowRayQueue": stats->shadowRays[depth] += size; Reset (integrator.cpp:581-585)
     LAUNCH_ON(strm, "Reset shadowRayQueue", k_reset, 1, ctx->ws, (1u << CNT_SHADOW) | (1u << CNT_CURSOR_SHADOW) | (1u << CNT_DEFER_SHADOW), STAT_SHADOW + statDepth(depth), CNT_SHADOW);
     ctx->cursorDirty[1] = false;
@@ -2486,20 +2615,20 @@ int wf_subsurface_probe(wf_ctx *ctx, int depth) {
     if (int e = checkReady(ctx)) return e;
     if (!ctx->svHost.haveSubsurface) return 0;
     (void)depth;
-    LAUNCH("Get BSSRDF and enqueue probe ray", k_subsurface_probe, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws);
+    LAUNCH("Get BSSRDF and enqueue probe ray", k_subsurface_probe, StageGridOf(ctx, SITE_SUBSURFACE_PROBE, ctx->maxQueueSize), ctx->svHost, ctx->ws);
     return 0;
 }
 int wf_intersect_one_random(wf_ctx *ctx) {
     if (int e = checkReady(ctx)) return e;
     if (!ctx->svHost.haveSubsurface) return 0;
     // reference-order walk (the chain of probe hits is a dependent sequence per item; the subsurface path is a side path)
-    LAUNCH("Intersect one random (subsurface probe)", ctx->stage.intersectOneRandom, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, ctx->stackSpill);
+    LAUNCH("Intersect one random (subsurface probe)", ctx->stage.intersectOneRandom, StageGridOf(ctx, SITE_INTERSECT_ONE_RANDOM, ctx->maxQueueSize), ctx->svHost, ctx->ws, ctx->stackSpill);
     return 0;
 }
 int wf_subsurface_scatter(wf_ctx *ctx, int depth) {
     if (int e = checkReady(ctx)) return e;
     if (!ctx->svHost.haveSubsurface) return 0;
-    LAUNCH("Handle out-scattering after SSS", k_subsurface_scatter, gridFor(ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
+    LAUNCH("Handle out-scattering after SSS", k_subsurface_scatter, StageGridOf(ctx, SITE_SUBSURFACE_SCATTER, ctx->maxQueueSize), ctx->svHost, ctx->ws, depth & 1);
     return 0;
 }
 int wf_update_film(wf_ctx *ctx) {

@@ -165,6 +165,11 @@ __global__ void __launch_bounds__(MBLOCK, VARIANT <= 1 ? WF_SHADE_WAVES_LEAN : W
 extern "C" void WF_CAT4(wf_launch_mat_shade_, WF_MAT_INSTANCE, _, WF_MAT_TEXCTX)(hipStream_t stream, int grid, const SceneView *sv, const WorkState *ws, int cur) {
     hipLaunchKernelGGL((k_mat_shade<WF_MAT_INSTANCE, WF_MAT_TEXCTX>), dim3(grid), dim3(MBLOCK), 0, stream, sv->self, *ws, cur);
 }
+// ... and the launcher's sibling: the workgroups of this unit's kernel one CU keeps resident (its registers, its LDS, MBLOCK threads),
+// for the grid of the launch above (wf_backend.hip: STAGE GRIDS).  Returns the hipError_t of the query.
+extern "C" int WF_CAT4(wf_resident_mat_shade_, WF_MAT_INSTANCE, _, WF_MAT_TEXCTX)(int *perCU) {
+    return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(perCU, (const void *)k_mat_shade<WF_MAT_INSTANCE, WF_MAT_TEXCTX>, MBLOCK, 0);
+}
 #else
 template <int MAT, bool RARE>
 __global__ void __launch_bounds__(MBLOCK, WF_NEE_WAVES) k_mat_nee(const SceneView *__restrict__ svp, WorkState ws) {
@@ -186,5 +191,9 @@ __global__ void __launch_bounds__(MBLOCK, WF_NEE_WAVES) k_mat_nee(const SceneVie
 // WF_MAT_TEXCTX = 0: the common light types; 1: + the rarely used ones (the portal infinite light's out-of-line samplers)
 extern "C" void WF_CAT4(wf_launch_mat_nee_, WF_MAT_INSTANCE, _, WF_MAT_TEXCTX)(hipStream_t stream, int grid, const SceneView *sv, const WorkState *ws) {
     hipLaunchKernelGGL((k_mat_nee<WF_MAT_INSTANCE, (WF_MAT_TEXCTX != 0)>), dim3(grid), dim3(MBLOCK), 0, stream, sv->self, *ws);
+}
+// (the launcher's sibling, as for the shade kernels)
+extern "C" int WF_CAT4(wf_resident_mat_nee_, WF_MAT_INSTANCE, _, WF_MAT_TEXCTX)(int *perCU) {
+    return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(perCU, (const void *)k_mat_nee<WF_MAT_INSTANCE, (WF_MAT_TEXCTX != 0)>, MBLOCK, 0);
 }
 #endif

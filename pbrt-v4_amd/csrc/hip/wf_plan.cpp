@@ -339,6 +339,13 @@ bool wf::planning::PlanValue(const ScenePlan &plan, const char *key, int64_t *va
     else if (k == "camera_anim") *value = plan.cameraAnim;   // k_gen_camera_rays<ANIM>
     else if (k == "route_variant") *value = plan.routeVariant;   // 0 k_route_hits<false>, 1 <true>, 2 <true, true>
     else if (TypeKey(k, "shade_variant_") >= 0) *value = plan.shadeVariant[TypeKey(k, "shade_variant_")];   // k_mat_shade's variant for material type t
+    else if (k.compare(0, 11, "stage_grid:") == 0) {
+        // the grid rule itself (StageGrid, wf_plan.h), whatever the scene: "stage_grid:<n_max>:<block>:<per CU>:<CUs>:<rounds>:<cap>"
+        long long n = 0;
+        int block = 0, perCU = 0, nCU = 0, rounds = 0, cap = 0, used = 0;
+        if (sscanf(k.c_str() + 11, "%lld:%d:%d:%d:%d:%d%n", &n, &block, &perCU, &nCU, &rounds, &cap, &used) != 6 || k.size() != (size_t)(11 + used) || n < 0 || block < 1) return false;
+        *value = StageGrid(n, block, perCU, nCU, rounds, cap);
+    }
     else return false;
     return true;
 }

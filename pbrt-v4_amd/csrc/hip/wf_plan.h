@@ -15,6 +15,21 @@ namespace wf { namespace planning __attribute__((visibility("hidden"))) {
 // the message of wf_last_error (per thread); returns `code`, or -1 for 0
 int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 
+// STAGE GRIDS.  A stage kernel is a grid-stride loop whose workgroups all run the same number of iterations, so a launch
+// proceeds in rounds of `perCU * nCU` workgroups — as many as the chip keeps resident of that kernel — and a grid that is no whole
+// number of rounds leaves part of the chip idle through its last one.  The workgroups of a launch over at most nMax items:
+//   min(ceil(nMax / block), rounds * perCU * nCU)     rounds > 0 and the kernel's occupancy is known (perCU > 0)
+//   min(ceil(nMax / block), STAGE_GRID_BOUND)         otherwise: the fixed bound of every round before this rule
+// and in both cases at most `cap`, if one is set.  Never less than one workgroup.
+constexpr int STAGE_GRID_BOUND = 256 * 8;    // 256 CUs x up to 8 resident 256-thread workgroups (wf_backend.hip: MAX_GRID)
+constexpr int STAGE_ROUNDS_DEFAULT = 4;     // chosen from {1, 2, 4} on the flagship: profiles/stage_rounds_parent_vs_change.txt
+inline int StageGrid(int64_t nMax, int block, int perCU, int nCU, int rounds, int cap) {
+    const int64_t need = std::max<int64_t>(1, (nMax + block - 1) / std::max(1, block));
+    int64_t most = rounds > 0 && perCU > 0 && nCU > 0 ? (int64_t)rounds * perCU * nCU : (int64_t)STAGE_GRID_BOUND;
+    if (cap > 0) most = std::min<int64_t>(most, cap);
+    return (int)std::min(need, most);
+}
+
 // The environment switches of context creation, scene upload (tree building included) and queue allocation, read in one place.  Each of those three calls takes a
 // fresh copy when it runs (the tests set switches between calls); the code they steer sees values, not the environment.
 struct Switches {
@@ -33,6 +48,8 @@ struct Switches {
     bool noSampleTops = false;    // WF_NO_SAMPLE_TOPS (set to anything)
     int trWavefront = -1;         // WF_TR_WAVEFRONT=1 | 0 forces / forbids the transmittance wavefront; -1 (unset): by the scene (ScenePlan::trRoute)
     int frameOverlap = 1;         // WF_FRAME_OVERLAP: 0 | 1 | 2 (wf_ctx::frameOverlap)
+    int stageRounds = STAGE_ROUNDS_DEFAULT;   // WF_STAGE_ROUNDS: 0 | 1 .. 16, the stage kernels' grids in whole resident rounds (StageGrid); 0: the fixed bound only
+    int stageGridCap = 0;         // WF_STAGE_GRID_CAP=<workgroups> (tests): no stage grid above this many workgroups, so that a tiny scene runs many grid-stride iterations; 0: none
     bool samplesShaded = true;    // WF_SAMPLES_SHADED=0
     bool traceLaunch = false;     // WF_TRACE_LAUNCH (set to anything)
     bool scratchPrime = true;     // WF_SCRATCH_PRIME=0
@@ -62,6 +79,8 @@ struct Switches {
         s.noSampleTops = isSet("WF_NO_SAMPLE_TOPS");
         s.trWavefront = number("WF_TR_WAVEFRONT", -1);
         s.frameOverlap = std::min(2, std::max(0, number("WF_FRAME_OVERLAP", 1)));
+        s.stageRounds = std::min(16, std::max(0, number("WF_STAGE_ROUNDS", STAGE_ROUNDS_DEFAULT)));
+        s.stageGridCap = std::max(0, number("WF_STAGE_GRID_CAP", 0));
         s.samplesShaded = on("WF_SAMPLES_SHADED");
         s.traceLaunch = isSet("WF_TRACE_LAUNCH");
         s.scratchPrime = on("WF_SCRATCH_PRIME");
