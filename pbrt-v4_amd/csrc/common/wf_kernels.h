@@ -1263,6 +1263,132 @@ struct NeeItem {
     BxDF bxdf{};           // after Regularize()
 };
 
+// ---- the lean shade kernels' PLANNED LOADS (device, WF_DEV_LEAN).  MatShade's own text reads each operand where it needs it:
+// matQ -> meta / hit -> hitInst / triMesh -> meshes[] -> ShadeTri -> the instance's rows (twice) -> material -> o / d ..., each behind a
+// full wait of its own, and beta / r_u / lambda / the samples below a conditional store the compiler does not hoist loads over: 20-25
+// exposed round trips per item at three waves per SIMD.  Every one of those addresses is known once i, prim, inst and pixelIndex are, so
+// the lean kernels fetch an item's inputs in fronts — loads issued together, waited for once:
+//   A  i = matQ[qi]                       B  meta, hit, hitInst, o, d, beta, r_u, mixMat          (need i)
+//   C  triMesh, the ShadeTri record (or the index triple), the instance's rows, lambda, lambdaPdf, samples0, samples1   (need prim, inst, pixelIndex)
+//   D  meshes[meshId] (+ the indexed tables' vertex data, WF_SHADE_TRIS=0)                        E  the material record
+// all through the global address space (a table pointer loaded from the view is a generic pointer: flat loads, both wait counters).  An
+// invalid lane, a top-level hit (inst = -1) and a scene without instances / mix materials issue no load for what they do not have.
+// The arithmetic is MatShade's: only when and how its operands arrive differs.
+// 16 bytes of a record through the global address space, as one register quad ...
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(WF_NO_GPTR)
+typedef float GQuad __attribute__((ext_vector_type(4)));
+WF_HD GQuad GlobalQuad(const void *p) { return *(const WF_GLOBAL_AS GQuad *)p; }
+// ... and the end of a front for it: a quad loaded under a condition passes this point whole.  (Without it the values a branch loaded are
+// copied out of their quads at the END OF THE BRANCH — a wait inside the branch, before the loads behind it are issued: the front in pieces.)
+WF_HD void LandQuad(GQuad &v) { asm volatile("" : "+v"(v)); }
+#else
+struct GQuad { float x, y, z, w; };
+WF_HD GQuad GlobalQuad(const void *p) { GQuad v; __builtin_memcpy(&v, p, sizeof v); return v; }
+WF_HD void LandQuad(GQuad &) {}
+#endif
+WF_HD F4 toF4(GQuad v) { return F4{v.x, v.y, v.z, v.w}; }
+WF_HD int GlobalInt(const int32_t *p) { return *(const WF_GLOBAL_AS int32_t *)p; }
+// What is needed late — beta, r_u, the samples, the wavelengths: 96 B per lane, live across the whole interaction / texture / BxDF code if
+// they stay in registers (the diffuse kernel has 167 of its 168) — is parked in LDS: planes of 16-byte columns, one column per lane, written
+// when the front lands and read back at the use.  A lane touches its own column only: no barrier.  (volatile: the store is not forwarded to
+// the load, which would keep the value in registers after all.)
+constexpr int MAT_BLOCK = 256;   // threads per workgroup of the material kernels (wf_mat.hip MBLOCK): the columns of a parked plane
+struct ShadeLate {
+    enum { BETA, R_U, S0, S1, LAMBDA, LAMBDA_PDF, META, RAY, NPLANES };   // (RAY: time, etaScale)
+#if defined(__HIP_DEVICE_COMPILE__) && defined(WF_LEAN)
+    typedef float V4 __attribute__((ext_vector_type(4)));
+    typedef __attribute__((address_space(3))) volatile V4 *Col;
+    Col col;   // this lane's column of plane 0; plane p lies p * MAT_BLOCK columns on: one address register and an immediate offset
+    __device__ __attribute__((always_inline)) void Open() {
+        __shared__ V4 park[NPLANES][MAT_BLOCK];
+        col = (Col)&park[0][threadIdx.x];
+        // (opaque to the optimiser: hoisted out of the item loop, every plane's address became a loop-invariant register of its own)
+        asm volatile("" : "+v"(col));
+    }
+    __device__ __attribute__((always_inline)) void Put(int plane, F4 v) { col[plane * MAT_BLOCK] = V4{v.x, v.y, v.z, v.w}; }
+    __device__ __attribute__((always_inline)) F4 Get(int plane) const { const V4 v = col[plane * MAT_BLOCK]; return F4{v.x, v.y, v.z, v.w}; }
+#else
+    F4 v[NPLANES];
+    WF_HD void Open() {}
+    WF_HD void Put(int plane, F4 x) { v[plane] = x; }
+    WF_HD F4 Get(int plane) const { return v[plane]; }
+#endif
+};
+struct ShadeInputs {   // (no default values: every field is assigned by the fetch, so that each stays a value of its own in registers)
+    int i, prim, inst, mixMat, meshId;
+    I4 meta;
+    F4 hit, o, d;
+    wf_mesh mesh;                 // the fields the shade code reads: flags, material, the media, first_s / first_vertex
+    V3 p0, p1, p2;                // the triangle's vertex data as TriangleInteraction gathers it
+    V2 uv0, uv1, uv2;
+    N3 n0, n1, n2;
+    float m[4][4], mInv[3][4];    // inst >= 0: render_from_instance, rows 0-3 of m and 0-2 of mInv (what InstanceInteraction / InstanceWo read)
+};
+template <int MAT>
+WF_HD void FetchShadeInputs(const SceneView &sv, const WorkState &ws, const RayQueueV &q, int qi, ShadeInputs *in, ShadeLate *late) {
+    // A
+    const int i = ws.matQ[MAT][qi];
+    in->i = i;
+    // B
+    in->meta = q.meta[i];
+    in->hit = ws.hit[i];
+    in->inst = -1;
+    if (sv.nInstances > 0) in->inst = ws.hitInst[i];
+    in->o = q.o[i]; in->d = q.d[i];
+    const F4 beta = q.beta[i], r_u = q.r_u[i];
+    in->mixMat = 0;
+    if (sv.haveMix) in->mixMat = ws.mixMat[i];
+    // C
+    const int prim = (int)FloatToBits(in->hit.x), pix = in->meta.x, inst = in->inst;
+    in->prim = prim;
+    in->meshId = sv.triMesh[prim];
+    const F4 lambda = ws.lambda[pix], lambdaPdf = ws.lambdaPdf[pix], s0 = ws.samples0[pix], s1 = ws.samples1[pix];
+    const ShadeTri *const stp = (const ShadeTri *)sv.shadeTris;
+    // (what a lane does not load stays unassigned: it is not read either)
+    GQuad t[6], xm[4], xi[3];
+    int v0, v1, v2;
+    if (stp != nullptr) {
+        for (int k = 0; k < 6; ++k) t[k] = GlobalQuad((const char *)(stp + prim) + 16 * k);
+    } else { v0 = sv.triIndices[3 * (size_t)prim]; v1 = sv.triIndices[3 * (size_t)prim + 1]; v2 = sv.triIndices[3 * (size_t)prim + 2]; }
+    if (inst >= 0) {
+        const wf_transform *const x = &((const wf_instance *)sv.instances + inst)->render_from_instance;
+        for (int r = 0; r < 4; ++r) xm[r] = GlobalQuad(x->m[r]);
+        for (int r = 0; r < 3; ++r) xi[r] = GlobalQuad(x->mInv[r]);
+    }
+    for (int k = 0; k < 6; ++k) LandQuad(t[k]);
+    for (int r = 0; r < 4; ++r) LandQuad(xm[r]);
+    for (int r = 0; r < 3; ++r) LandQuad(xi[r]);
+    for (int r = 0; r < 4; ++r) { in->m[r][0] = xm[r].x; in->m[r][1] = xm[r].y; in->m[r][2] = xm[r].z; in->m[r][3] = xm[r].w; }
+    for (int r = 0; r < 3; ++r) { in->mInv[r][0] = xi[r].x; in->mInv[r][1] = xi[r].y; in->mInv[r][2] = xi[r].z; in->mInv[r][3] = xi[r].w; }
+    // D
+    {
+        const wf_mesh *const mp = (const wf_mesh *)sv.meshes + in->meshId;
+        static_assert(sizeof(wf_mesh) == 48 && sizeof(wf_instance) % 16 == 0 && sizeof(ShadeTri) == 96, "records read 16 bytes at a time");
+        GQuad w[3];
+        for (int k = 0; k < 3; ++k) w[k] = GlobalQuad((const char *)mp + 16 * k);
+        __builtin_memcpy(&in->mesh, w, sizeof(wf_mesh));
+    }
+    late->Put(ShadeLate::BETA, beta); late->Put(ShadeLate::R_U, r_u);
+    late->Put(ShadeLate::LAMBDA, lambda); late->Put(ShadeLate::LAMBDA_PDF, lambdaPdf);
+    late->Put(ShadeLate::S0, s0); late->Put(ShadeLate::S1, s1);
+    late->Put(ShadeLate::META, F4{BitsToFloat((uint32_t)in->meta.x), BitsToFloat((uint32_t)in->meta.y), BitsToFloat((uint32_t)in->meta.z), BitsToFloat((uint32_t)in->meta.w)});
+    late->Put(ShadeLate::RAY, F4{in->o.w, in->d.w, 0.f, 0.f});
+    const int flags = in->mesh.flags;
+    in->uv0 = V2{0, 0}; in->uv1 = V2{1, 0}; in->uv2 = V2{1, 1};
+    in->n0 = in->n1 = in->n2 = N3{0, 0, 0};
+    if (stp != nullptr) {
+        // ShadeTri: float p[9], n[9], uv[6]
+        in->p0 = V3{t[0].x, t[0].y, t[0].z}; in->p1 = V3{t[0].w, t[1].x, t[1].y}; in->p2 = V3{t[1].z, t[1].w, t[2].x};
+        if (flags & WF_MESH_HAS_N) { in->n0 = N3{t[2].y, t[2].z, t[2].w}; in->n1 = N3{t[3].x, t[3].y, t[3].z}; in->n2 = N3{t[3].w, t[4].x, t[4].y}; }
+        if (flags & WF_MESH_HAS_UV) { in->uv0 = V2{t[4].z, t[4].w}; in->uv1 = V2{t[5].x, t[5].y}; in->uv2 = V2{t[5].z, t[5].w}; }
+    } else {
+        // the indexed tables (WF_SHADE_TRIS=0): one more front, behind the index triple and the mesh's flags
+        in->p0 = LoadP(sv, v0); in->p1 = LoadP(sv, v1); in->p2 = LoadP(sv, v2);
+        if (flags & WF_MESH_HAS_UV) { in->uv0 = LoadUV(sv, v0); in->uv1 = LoadUV(sv, v1); in->uv2 = LoadUV(sv, v2); }
+        if (flags & WF_MESH_HAS_N) { in->n0 = LoadN(sv, v0); in->n1 = LoadN(sv, v1); in->n2 = LoadN(sv, v2); }
+    }
+}
+
 // TEXCTX = false: the scene has neither footprint-dependent textures nor displacement, so the differentials and
 // the bump-mapping block (whose only consumers those are) are compiled out — a separate kernel variant, because
 // their registers cost the common case ~25 % (35 spilled VGPRs in the diffuse kernel).
@@ -1284,6 +1410,9 @@ WF_HD void MatShade(const SceneView &sv, const WorkState &ws, int cur, int qi, b
     // `valid` = this thread has an item.  The queue push goes through BlockAlloc, which every thread of
     // the workgroup must reach: control flow below is flattened into the flag pushRay.
     using BxDF = typename MatBxDF<MAT>::T;
+    // the planned loads (FetchShadeInputs above): the lean device kernels, except the two that pay for them in resources — thin dielectric
+    // without footprint (106 -> 132 VGPRs: its fourth wave) and hair without footprint (336 -> 384 B of scratch) — which keep this text's own loads
+    constexpr bool FRONTS = WF_DEV_LEAN && !(VARIANT == 0 && (MAT == WF_MAT_THIN_DIELECTRIC || MAT == WF_MAT_HAIR));
     const RayQueueV &q = ws.rq[cur];
     const RayQueueV &nq = ws.rq[cur ^ 1];
     bool pushRay = false;
@@ -1298,31 +1427,45 @@ WF_HD void MatShade(const SceneView &sv, const WorkState &ws, int cur, int qi, b
     if (!valid && shadowIdle) qi = ws.counters[(CNT_MAT0 + MAT) * CNT_STRIDE] - 1;
 #endif
     if (valid || shadowIdle) {
-        int i = ws.matQ[MAT][qi];
-        I4 meta = q.meta[i];
+        // (a lean device kernel: the item's inputs arrive in planned fronts, FetchShadeInputs above; everywhere else they are read where
+        //  they are needed)
+        ShadeInputs in;
+        ShadeLate late;
+        if constexpr (FRONTS) { late.Open(); FetchShadeInputs<MAT>(sv, ws, q, qi, &in, &late); }
+        int i = FRONTS ? in.i : ws.matQ[MAT][qi];
+        I4 meta = FRONTS ? in.meta : q.meta[i];
         pixelIndex = meta.x;
         depth = meta.y;
         bool anyNonSpecularBounces0 = meta.z & RAYFLAG_ANY_NONSPECULAR;
-        F4 h = ws.hit[i];
+        F4 h = FRONTS ? in.hit : ws.hit[i];
         int prim = (int)FloatToBits(h.x);
-        const int inst = HitInst(sv, ws, i);
+        const int inst = FRONTS ? in.inst : HitInst(sv, ws, i);
         SurfIntr si;
-        {
+        V3 woLean{0, 0, 0};
+        if constexpr (FRONTS) {
+            TriangleInteractionOf(sv, prim, in.meshId, in.mesh, in.p0, in.p1, in.p2, in.uv0, in.uv1, in.uv2, in.n0, in.n1, in.n2, h.y, h.z, h.w, &si);
+            if (inst >= 0) InstanceInteraction(in.m, in.mInv, &si);
+            // intr.wo, while the rows are at hand (the same values as below: IntrWo's triangle cases — no call, no second read of the matrices)
+            woLean = V3{-in.d.x, -in.d.y, -in.d.z};
+            if (!(sv.haveMedia && meta.w >= 0)) woLean = inst >= 0 ? InstanceWo(in.m, in.mInv, woLean) : Normalize(woLean);
+        } else {
             V3 ro{0, 0, 0}, rd{0, 0, 0};   // only a curve's interaction needs the ray that found it
             if (sv.haveCurves) { F4 o4 = q.o[i], d4 = q.d[i]; ro = V3{o4.x, o4.y, o4.z}; rd = V3{d4.x, d4.y, d4.z}; }
             HitInteraction<!WF_DEV_LEAN, ANIM, ANIM>(sv, prim, inst, h.y, h.z, h.w, &si, ro, rd, q.o[i].w);   // (incl. alpha-textured curves and animated instances)
         }
-        const wf_mesh &mesh = sv.meshes[si.mesh];
+        const wf_mesh &mesh = FRONTS ? in.mesh : sv.meshes[si.mesh];
         int matId = mesh.material;
-        if (sv.haveMix && sv.materials[matId].type == WF_MAT_MIX) matId = ws.mixMat[i];
+        if constexpr (FRONTS) { if (sv.haveMix && GlobalInt(&sv.materials[matId].type) == WF_MAT_MIX) matId = in.mixMat; }
+        else if (sv.haveMix && sv.materials[matId].type == WF_MAT_MIX) matId = ws.mixMat[i];
         const wf_material &mat = sv.materials[matId];
-        F4 o4 = q.o[i], d4 = q.d[i];
+        F4 o4 = FRONTS ? in.o : q.o[i], d4 = FRONTS ? in.d : q.d[i];
         time = o4.w;
         float etaScale0 = d4.w;
         // intr.wo: the Interaction constructor normalises it (interaction.h:40-43), also for unit-length ray.d;
         // items enqueued by the medium stage carry -ray.d as it is (media.cpp:240)
         V3 wo{-d4.x, -d4.y, -d4.z};
-        if (!(sv.haveMedia && meta.w >= 0)) wo = IntrWo<!WF_DEV_LEAN, ANIM>(sv, prim, inst, wo, time);
+        if constexpr (FRONTS) wo = woLean;
+        else if (!(sv.haveMedia && meta.w >= 0)) wo = IntrWo<!WF_DEV_LEAN, ANIM>(sv, prim, inst, wo, time);
         // differentials of position and (u, v) at the intersection (surfscatter.cpp:73-104)
         TexCtx tc;
         tc.p = si.pi.mid(); tc.n = si.n; tc.uv = si.uv;
@@ -1390,7 +1533,12 @@ WF_HD void MatShade(const SceneView &sv, const WorkState &ws, int cur, int qi, b
             ns = FaceForward(ns, si.n);
         }
         }
-        Wavelengths lambda = LoadLambda(ws, pixelIndex);
+        Wavelengths lambda;
+        if constexpr (FRONTS) {
+            const F4 l = late.Get(ShadeLate::LAMBDA), lp = late.Get(ShadeLate::LAMBDA_PDF);
+            lambda.lambda[0] = l.x; lambda.lambda[1] = l.y; lambda.lambda[2] = l.z; lambda.lambda[3] = l.w;
+            lambda.pdf[0] = lp.x; lambda.pdf[1] = lp.y; lambda.pdf[2] = lp.z; lambda.pdf[3] = lp.w;
+        } else lambda = LoadLambda(ws, pixelIndex);
         BxDF bxdf = MatBxDF<MAT>::Get(sv, mat, lambda, tc);
         BSDF<BxDF> bsdf(ns, dpdus, bxdf);
         if (live && lambda.SecondaryTerminated()) StoreLambda(ws, pixelIndex, lambda);
@@ -1423,10 +1571,23 @@ WF_HD void MatShade(const SceneView &sv, const WorkState &ws, int cur, int qi, b
             ws.vsAlbedo[pixelIndex] = toF4(albedo);
         }
 
-        S4 wbeta = toS4(q.beta[i]), wr_u = toS4(q.r_u[i]);
-        F4 s0 = ws.samples0[pixelIndex], s1 = ws.samples1[pixelIndex];
+        S4 wbeta = S4c(0.f), wr_u = S4c(0.f);
+        F4 s0, s1;
+        if constexpr (FRONTS) { s0 = late.Get(ShadeLate::S0); s1 = late.Get(ShadeLate::S1); }
+        else { wbeta = toS4(q.beta[i]); wr_u = toS4(q.r_u[i]); s0 = ws.samples0[pixelIndex]; s1 = ws.samples1[pixelIndex]; }
         // Sample BSDF and enqueue indirect ray
         BSDFSample bs = bsdf.Sample_f(wo, s0.w, V2{s1.x, s1.y});
+        if constexpr (FRONTS) {
+            // (lean: what the rest needs of the item comes back from its parked columns HERE — none of it occupies a register across
+            //  the BSDF sample)
+            wbeta = toS4(late.Get(ShadeLate::BETA)); wr_u = toS4(late.Get(ShadeLate::R_U));
+            s0 = late.Get(ShadeLate::S0); s1 = late.Get(ShadeLate::S1);
+            const F4 mb = late.Get(ShadeLate::META), ry = late.Get(ShadeLate::RAY);
+            meta = I4{(int)FloatToBits(mb.x), (int)FloatToBits(mb.y), (int)FloatToBits(mb.z), (int)FloatToBits(mb.w)};
+            pixelIndex = meta.x; depth = meta.y;
+            anyNonSpecularBounces0 = meta.z & RAYFLAG_ANY_NONSPECULAR;
+            time = ry.x; etaScale0 = ry.y;
+        }
         if (bs.valid) {
             V3 wi = bs.wi;
             S4 beta = wbeta * bs.f * AbsDot(wi, ns) / bs.pdf;
@@ -1483,6 +1644,8 @@ WF_HD void MatShade(const SceneView &sv, const WorkState &ws, int cur, int qi, b
             out->mediumOutside = transition ? mesh.medium_outside : meta.w;
         }
         out->beta = wbeta; out->r_u = wr_u;
+        if constexpr (FRONTS) { const F4 l = late.Get(ShadeLate::LAMBDA); out->lambda[0] = l.x; out->lambda[1] = l.y; out->lambda[2] = l.z; out->lambda[3] = l.w; }   // (the wavelengths themselves never change)
+        else
         for (int k = 0; k < 4; ++k) out->lambda[k] = lambda.lambda[k];
         out->bxdf = bsdf.bxdf;
     }

@@ -1231,6 +1231,106 @@ WF_HD void TriangleInteraction(const SceneView &sv, int tri, float b0, float b1,
     }
 }
 
+// The same from vertex data the caller holds — the lean shade kernels' planned loads (wf_kernels.h FetchShadeInputs): p, uv and n as the
+// function above gathers them (the defaults where the mesh has no (u, v) / no normals), `mesh` with at least flags, first_s and
+// first_vertex.  KEEP IN STEP with the function above from its `duv02` line on: the same operations in the same order.
+WF_HD void TriangleInteractionOf(const SceneView &sv, int tri, int meshId, const wf_mesh &mesh, V3 p0, V3 p1, V3 p2, V2 uv0, V2 uv1, V2 uv2, N3 n0, N3 n1, N3 n2,
+                                 float b0, float b1, float b2, SurfIntr *si) {
+    const auto v = sv.triIndices + 3 * (size_t)tri;   // (read for the "S" tangents only)
+    si->mesh = meshId;
+    V2 duv02{uv0.x - uv2.x, uv0.y - uv2.y}, duv12{uv1.x - uv2.x, uv1.y - uv2.y};
+    V3 dp02 = p0 - p2, dp12 = p1 - p2;
+    float determinant = DifferenceOfProducts(duv02.x, duv12.y, duv02.y, duv12.x);
+    V3 dpdu{0, 0, 0}, dpdv{0, 0, 0};
+    bool degenerateUV = abs(determinant) < 1e-9f;
+    if (!degenerateUV) {
+        float invdet = 1 / determinant;
+        dpdu = DifferenceOfProductsV(duv12.y, dp02, duv02.y, dp12) * invdet;
+        dpdv = DifferenceOfProductsV(duv02.x, dp12, duv12.x, dp02) * invdet;
+    }
+    if (degenerateUV || LengthSquared(Cross(dpdu, dpdv)) == 0) {
+        V3 ng = Cross(p2 - p0, p1 - p0);
+        if (LengthSquared(ng) == 0) {
+            // Cross(Vector3<double>, Vector3<double>) — the double DifferenceOfProducts, util/math.h:569
+            V3 a = p2 - p0, b = p1 - p0;
+            double ax = a.x, ay = a.y, az = a.z, bx = b.x, by = b.y, bz = b.z;
+            auto dop = [](double a, double b, double c, double d) {
+                double cd = c * d;
+                double r = ::fma(a, b, -cd);
+                double e = ::fma(-c, d, cd);
+                return r + e;
+            };
+            ng = V3{(float)dop(ay, bz, az, by), (float)dop(az, bx, ax, bz), (float)dop(ax, by, ay, bx)};
+        }
+        CoordinateSystem(Normalize(ng), &dpdu, &dpdv);
+    }
+    V3 pHit = b0 * p0 + b1 * p1 + b2 * p2;
+    V2 uvHit{b0 * uv0.x + b1 * uv1.x + b2 * uv2.x, b0 * uv0.y + b1 * uv1.y + b2 * uv2.y};
+    bool flipNormal = (mesh.flags & WF_MESH_FLIP_NORMAL) != 0;
+    V3 pAbsSum = Abs(b0 * p0) + Abs(b1 * p1) + Abs(b2 * p2);
+    V3 pError = gamma(7) * pAbsSum;
+    si->pi = MakeP3i(pHit, pError);
+    si->uv = uvHit;
+    si->dpdu = dpdu;
+    si->dpdv = dpdv;
+    si->dndu = si->dndv = N3{0, 0, 0};
+    // SurfaceInteraction ctor (interaction.h:164-183) computes n from dpdu x dpdv and flips it; the
+    // triangle then overrides n and shading.n (shapes.h:936-938)
+    N3 n = toN(Normalize(Cross(dp02, dp12)));
+    if (flipNormal) n = -n;
+    si->n = n;
+    si->ns = n;
+    si->dpdus = dpdu;
+    si->dpdvs = dpdv;
+    si->dndus = si->dndvs = N3{0, 0, 0};
+    if (mesh.flags & (WF_MESH_HAS_N | WF_MESH_HAS_S)) {   // shapes.h:940: mesh->n || mesh->s
+        const bool hasN = mesh.flags & WF_MESH_HAS_N;
+        N3 ns = si->n;
+        if (hasN) {
+            ns = b0 * n0 + b1 * n1 + b2 * n2;
+            ns = LengthSquared(ns) > 0 ? Normalize(ns) : si->n;
+        }
+        V3 ss = si->dpdu;
+        if (mesh.flags & WF_MESH_HAS_S) {   // the interpolated "S" tangent (shapes.h:951-959)
+            ss = b0 * LoadS(sv, mesh, v[0]) + b1 * LoadS(sv, mesh, v[1]) + b2 * LoadS(sv, mesh, v[2]);
+            if (LengthSquared(ss) == 0) ss = si->dpdu;
+        }
+        V3 ts = Cross(ns, ss);
+        if (LengthSquared(ts) > 0) ss = Cross(ts, ns);
+        else CoordinateSystem(toV(ns), &ss, &ts);
+        N3 dndu, dndv;
+        N3 dn1 = n0 - n2, dn2 = n1 - n2;
+        float det2 = DifferenceOfProducts(duv02.x, duv12.y, duv02.y, duv12.x);
+        bool degUV = abs(det2) < 1e-9;  // double comparison in the reference (shapes.h:984)
+        if (!hasN) dndu = dndv = N3{0, 0, 0};   // shapes.h:1003-1004
+        else if (degUV) {
+            V3 dn = Cross(toV(n2 - n0), toV(n1 - n0));
+            if (LengthSquared(dn) == 0) dndu = dndv = N3{0, 0, 0};
+            else {
+                V3 dnu, dnv;
+                CoordinateSystem(dn, &dnu, &dnv);
+                dndu = toN(dnu);
+                dndv = toN(dnv);
+            }
+        } else {
+            float invDet = 1 / det2;
+            dndu = DifferenceOfProductsN(duv12.y, dn1, duv02.y, dn2) * invDet;
+            dndv = DifferenceOfProductsN(duv02.x, dn2, duv12.x, dn1) * invDet;
+        }
+        // SetShadingGeometry(ns, ss, ts, dndu, dndv, true), interaction.h:194-214
+        si->ns = ns;
+        si->n = FaceForward(si->n, si->ns);
+        si->dpdus = ss;
+        si->dpdvs = ts;
+        si->dndus = dndu;
+        si->dndvs = dndv;
+        while (LengthSquared(si->dpdus) > 1e16f || LengthSquared(si->dpdvs) > 1e16f) {
+            si->dpdus = si->dpdus / 1e8f;
+            si->dpdvs = si->dpdvs / 1e8f;
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // Triangle sampling (shapes.h:845-880, 1013-1180)
 WF_HD float TriangleArea(V3 p0, V3 p1, V3 p2) { return 0.5f * Length(Cross(p1 - p0, p2 - p0)); }
@@ -1648,6 +1748,25 @@ WF_HD void InstanceInteraction(const wf_instance *in, SurfIntr *si) {
     r.mesh = si->mesh;
     *si = r;
 }
+// ... and from rows of m (0-3) and mInv (0-2) the caller holds (the lean shade kernels' planned loads): the function above, KEEP IN STEP
+WF_HD void InstanceInteraction(const float (*m)[4], const float (*mi)[4], SurfIntr *si) {
+    SurfIntr r;
+    r.pi = XfP3i(m, si->pi);
+    r.n = Normalize(XfNormal3(mi, si->n));
+    r.uv = si->uv;
+    r.dpdu = XfVector3(m, si->dpdu);
+    r.dpdv = XfVector3(m, si->dpdv);
+    r.dndu = XfNormal3(mi, si->dndu);
+    r.dndv = XfNormal3(mi, si->dndv);
+    r.ns = Normalize(XfNormal3(mi, si->ns));
+    r.dpdus = XfVector3(m, si->dpdus);
+    r.dpdvs = XfVector3(m, si->dpdvs);
+    r.dndus = XfNormal3(mi, si->dndus);
+    r.dndvs = XfNormal3(mi, si->dndvs);
+    r.ns = FaceForward(r.ns, r.n);
+    r.mesh = si->mesh;
+    *si = r;
+}
 WF_NI void InstanceInteractionP(const wf_instance *in, SurfIntr *si) { InstanceInteraction(in, si); }
 WF_NI void InstanceWoP(const wf_instance *in, float x, float y, float z, float *ox, float *oy, float *oz) {
     // the instance-space interaction's wo = Normalize(-ApplyInverse(ray.d)) (interaction.h:40-43), transformed back and
@@ -1655,6 +1774,8 @@ WF_NI void InstanceWoP(const wf_instance *in, float x, float y, float z, float *
     V3 w = Normalize(XfVector3(in->render_from_instance.m, Normalize(XfVector3(in->render_from_instance.mInv, V3{x, y, z}))));
     *ox = w.x; *oy = w.y; *oz = w.z;
 }
+// (InstanceWoP in line, on rows the caller holds)
+WF_HD V3 InstanceWo(const float (*m)[4], const float (*mi)[4], V3 minusD) { return Normalize(XfVector3(m, Normalize(XfVector3(mi, minusD)))); }
 // GENERAL = false (the default in a lean unit, WF_DEV_LEAN): the scene has triangles only — the quadric / patch / curve callees are not
 // reachable from the caller (see wf_scene.h "LEAN DEVICE VARIANTS")
 template <bool GENERAL = !WF_DEV_LEAN, bool ANIM = false>

@@ -2242,6 +2242,7 @@ int wf_ctx_query(wf_ctx *ctx, const char *key, int64_t *value) {
     else if (k == "frame_overlap_mode") *value = ctx->frameOverlap;
     else if (k == "skip_last_samples") *value = SkipLastSamples(ctx);
     else if (k == "pixels_per_pass") *value = ctx->queuesAllocated ? ctx->ws.pixelsPerPass : 0;   // the rays a band holds per sample index (wf_camera_rays_device's n_max)
+    else if (k == "shade_tris") *value = (const ShadeTri *)ctx->svHost.shadeTris != nullptr;   // the de-indexed vertex records are uploaded (0: WF_SHADE_TRIS=0, the indexed tables only)
     else if (k == "stage_rounds") *value = ctx->grids.rounds;
     else if (k == "stage_grid_cap") *value = ctx->grids.cap;
     else if (k == "stage_grid_fallbacks") *value = ctx->grids.fallbacks;

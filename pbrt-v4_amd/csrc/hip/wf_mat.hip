@@ -21,7 +21,7 @@
 
 using namespace wf;
 
-constexpr int MBLOCK = 256;
+constexpr int MBLOCK = MAT_BLOCK;   // (256; also the columns of the lean shade kernels' LDS planes, wf_kernels.h ShadeLate)
 
 // minimum waves per SIMD (the register budget: 2 -> 256 VGPRs, 3 -> 168, 4 -> 128).  The one-kernel stage of rounds 1-4, measured per material on the spec
 // scene, 2 vs 3 waves: diffuse 24.1 -> 22.7 ms per 16 spp, conductor 6.27 -> 6.40, coated diffuse 17.4 -> 20.2 (its stochastic walks spill).
