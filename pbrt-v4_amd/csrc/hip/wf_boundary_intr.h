@@ -1,6 +1,6 @@
 // wf_boundary_intr.h — the launchers of wf_boundary_intr.hip: the two kernels behind wf_hit_interaction_device and
 // wf_camera_rays_device (include/wf_abi.h).  The kernels live in a unit of their own so that no kernel of wf_backend.hip shares a
-// device code object with them; wf_backend.hip holds the entry points (argument checks, the context's stream, the profile bracket).
+// device code object with them; wf_boundary.hip holds the entry points (argument checks, the context's stream, the profile bracket).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

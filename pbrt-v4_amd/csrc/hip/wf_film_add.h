@@ -33,7 +33,7 @@ WF_HD bool ClaimPixel(int32_t *stamp, int32_t epoch) {
 
 // The epoch of the call after the one of epoch `last` (0: none yet).  Epochs run 1 .. INT32_MAX and then over again from 1; *clear says
 // that the stamps must be zeroed before this call's items, or a pixel last stamped in the earlier cycle's call of the same number would
-// reject its first item.  The entry point's bookkeeping (wf_backend.hip); the host program walks it across the wrap.
+// reject its first item.  The entry point's bookkeeping (wf_boundary.hip); the host program walks it across the wrap.
 inline int32_t NextEpoch(int32_t last, bool *clear) {
     *clear = last == INT32_MAX;
     return *clear ? 1 : last + 1;

@@ -1,7 +1,7 @@
 // wf_film_add.hip — Film::AddSample on a caller's device items (gfx950): the kernel behind wf_film_add_samples_device.  One item per
 // lane, 256-thread blocks; the per-item arithmetic is wf_film_add.h's (the render's, operation for operation: -ffp-contract=off).  A unit
-// of its own: its kernels share no device code object with the render's.  The C ABI entry point is in wf_backend.hip, where wf_ctx
-// lives; it calls the launcher below.
+// of its own: its kernels share no device code object with the render's.  The C ABI entry point is in wf_boundary.hip; it calls the
+// launcher below.
 //   loads per item   8 bytes of pixel, 16 each of L4 / lambda4 / lambda_pdf4, 4 of filter weight; one returning 4-byte atomic on the
 //                    pixel's stamp; the film record as two 16-byte loads and two 16-byte stores
 // In camera order neighbouring lanes touch neighbouring 32-byte records, so nothing is staged through LDS.

@@ -1,7 +1,7 @@
 // wf_film_develop.hip — the film's GetImage step on the device (gfx950): from the accumulators wf_update_film leaves in HBM to the final
 // float32 [H][W][C] image in a caller-owned device buffer.  One pixel per lane, 256-thread blocks; the per-pixel arithmetic is
 // wf_film_develop.h's, the restatement of image_io.cpp's host loops (bit-identical: -ffp-contract=off, IEEE division and sqrt).
-// The C ABI entry points (wf_film_develop_device, ...) are in wf_backend.hip, where wf_ctx lives; they call the launchers below.
+// The C ABI entry points (wf_film_develop_device, ...) are in wf_results.hip; they call the launchers below.
 #include <hip/hip_runtime.h>
 #include "wf_film_develop.h"
 

@@ -1,7 +1,7 @@
 // wf_plan.h — what libwfhip.so decides about a scene on the host before anything is uploaded: the environment switches (Switches), the
 // scene's plan (ScenePlan, PlanScene) and the production traversal layout as it is built (FastTrees, BuildFastBVH).  The definitions are
 // plain C++ without a HIP call — wf_plan.cpp, wf_fastbvh_build.cpp — so they are compiled once, not per pass of the kernel unit, and a
-// stand-alone host program can link them (tools/plan_dump.cpp).  wf_backend.hip includes this for what the upload and the queries use.
+// stand-alone host program can link them (tools/plan_dump.cpp).  wf_ctx.h includes this for the upload, the queries and the boundary calls.
 #pragma once
 #include <cstdint>
 #include <cstdlib>
@@ -21,7 +21,7 @@ int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 //   min(ceil(nMax / block), rounds * perCU * nCU)     rounds > 0 and the kernel's occupancy is known (perCU > 0)
 //   min(ceil(nMax / block), STAGE_GRID_BOUND)         otherwise: the fixed bound of every round before this rule
 // and in both cases at most `cap`, if one is set.  Never less than one workgroup.
-constexpr int STAGE_GRID_BOUND = 256 * 8;    // 256 CUs x up to 8 resident 256-thread workgroups (wf_backend.hip: MAX_GRID)
+constexpr int STAGE_GRID_BOUND = 256 * 8;    // 256 CUs x up to 8 resident 256-thread workgroups (wf_ctx.h: MAX_GRID)
 constexpr int STAGE_ROUNDS_DEFAULT = 4;     // chosen from {1, 2, 4} on the flagship: profiles/stage_rounds_parent_vs_change.txt
 inline int StageGrid(int64_t nMax, int block, int perCU, int nCU, int rounds, int cap) {
     const int64_t need = std::max<int64_t>(1, (nMax + block - 1) / std::max(1, block));

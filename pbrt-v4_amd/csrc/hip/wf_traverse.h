@@ -1,4 +1,4 @@
-// wf_traverse.h — the production BVH traversal for CDNA4 (device only; included by wf_backend.hip).  The records it walks (QNode, LeafTri,
+// wf_traverse.h — the production BVH traversal for CDNA4 (device only; included through wf_ctx.h, walked by wf_backend.hip).  The records it walks (QNode, LeafTri,
 // FastBVH, FastDef, SubEntry) are declared in common/wf_fastbvh.h, which the host-only tree builder (wf_fastbvh_build.cpp) shares.
 //
 // The reference-order walk in common/wf_shapes.h (BVHIntersectClosest/Any) visits one 32-byte

@@ -149,7 +149,7 @@ MultiDeviceRenderer::MultiDeviceRenderer(const SceneTables &tables, const std::v
     if (n < 1) throw SceneError("Fatal: MultiDeviceRenderer: no devices");
     renderers.resize(n, nullptr);
     // every context is created on the thread that will drive it later?  Not needed: the C ABI makes the context's device current in the
-    // calling thread at every entry (wf_backend.hip: useDevice).  The uploads run concurrently, one thread per device.
+    // calling thread at every entry (wf_ctx.h: useDevice).  The uploads run concurrently, one thread per device.
     std::vector<std::thread> th;
     std::vector<std::string> err(n);
     for (int k = 0; k < n; ++k)
