@@ -842,6 +842,56 @@ int wf_camera_samples_device(wf_ctx *ctx, int y0, int sample_index, int n_max,
 int wf_film_add_samples_device(wf_ctx *ctx, int n, const int32_t *n_device /* may be NULL */, const int32_t *pixel_xy /* [n][2] */,
                                const float *L4 /* [n][4] */, const float *lambda4 /* [n][4] */, const float *lambda_pdf4 /* [n][4] */,
                                const float *filter_weight /* [n] */, uint32_t *rejected_device /* may be NULL */);
+/* The scene's LIGHTS on a caller's DEVICE items: the light half of next-event estimation and the emission of a ray's end, computed by the
+   render's own functions (the light samplers, SampleLi, PDF_Li, L, Le of every light type) — with them a caller's integrator writes direct
+   lighting, emission and their MIS weights against the lights the render uses.  The BSDF is the caller's.  Both calls take the planes
+   wf_hit_interaction_device writes (planes_f [WF_INTR_FPLANES][n][4], planes_i [WF_INTR_IPLANES][n][4], plane stride n), so its output
+   feeds them as it is; a caller with points of its own fabricates the planes it needs: pi lower = pi upper = p and n = ns = 0 is the
+   reference's context of a point in a medium.  Both are launched on the context's stream (wf_stream) and NOT synchronised; every
+   argument is checked before anything is launched (4-float arrays and planes are aligned to 16 bytes, side and n_device to 4; all
+   device pointers of the context's device; n <= 0 touches nothing); n_device is NULL or a device word: min(n, *n_device) rows are
+   processed and the rows after them are not written.  They need an uploaded scene, no queues, and touch none of the render's queues,
+   pixel state or statistics.  The kernels' variants are the scene's ("light_sample_rare", "light_emitted_variant", wf_ctx_query).
+
+   wf_light_sample_device: "sample light" of surfscatter.cpp:251-327 without the BSDF — lightSampler.Sample(ctx, uc), light.SampleLi(ctx,
+   u, lambda, true) and the shadow ray intr.SpawnRayTo(ls.pLight).
+     reads    planes_f 0, 1 (pi), 2 (n | time), 3 (ns), 4 (wo);  planes_i 0 (.z / .w: medium inside / outside), 1 (.y: valid)
+              lambda4[i] = the four wavelengths;  u4[i] = {uc, u[0], u[1], unused}: the layout of the render's first sample quad
+              side[i] (side may be NULL: all 0) = which LightSampleContext the light sees:  0 the position interval pi;  +1 the point
+              OffsetRayOrigin(pi, n, wo);  -1 the point OffsetRayOrigin(pi, n, -wo).  The render's rule (surfscatter.cpp:256-261): a BSDF
+              that reflects and does not transmit takes +1, one that reflects AND transmits takes -1, anything else (transmission only)
+              keeps the interval — the reference's own quirk, reproduced.  Any other value is read as 0.
+     writes   shadow_rays8[i] = {o, d (NOT normalised: the ray ends at the light at t = 1), tMax = 1 - ShadowEpsilon, the interaction's
+              time}: a ray of wf_trace_any_device_t / wf_trace_shadow_tr_device.  The ray always leaves from pi, whatever side[i] says.
+              L4[i] = ls.L;  wi_pdf4[i] = {ls.wi, ls.pdf: the PDF of the direction alone}
+              light4[i] = {the light's id or -1, the bits of the sampler's PMF of it, flags (bit 0: a delta light), the shadow ray's
+              medium: Dot(d, n) > 0 ? medium outside : medium inside, -1 in a scene without media}
+     A row is usable when the render would go on to its BSDF: a light was chosen, its sample is valid, carries radiance and has a
+     non-zero PDF.  Every other row (valid != 1 included) is L4 = 0, wi_pdf4 = 0, a zero ray and medium -1; its light id and PMF are
+     still the sampler's (-1 and 0 when no light was chosen or the row is not valid).  The PMF and the PDF are handed out separately,
+     because the render groups their product both ways: (r_l * pmf) * pdf for an escaped ray, r * (pmf * pdf) for an emitter and for NEE.
+
+   wf_light_emitted_device: the emission at the end of the rays rays8 (o, d, tMax, time as wf_trace_closest_device_t reads them) whose
+   hits are the planes — HandleEscapedRays / HandleEmissiveIntersection (wavefront/integrator.cpp:495-573) without the path state.
+     reads    rays8 (o, d);  planes_f 0, 1 (pi | uv), 2 (n), 4 (wo);  planes_i 0 (.y: area light), 1 (.y: valid);  lambda4
+              prev_planes_f (may be NULL) = planes 0 - 3 [4][n][4] of the vertex the ray LEFT: the LightSampleContext the render keeps
+              with the ray, as it is (no side offset).  The planes of wf_hit_interaction_device for that vertex serve unchanged.
+     writes   Le4[i] and pmf_pdf4[i] = {pmf, pdf, 0, 0}:
+              a hit (valid = 1) on an emitter (area light >= 0), for infinite_index = 0 only: Le = light.L(pi's midpoint, n, uv, wo);
+                 with prev, and where Le is not black: pmf = lightSampler.PMF(prev, light), pdf = light.PDF_Li(prev, -wo, true)
+              a miss (valid = 0): Le = Le of the scene's infinite light number infinite_index along the ray; with prev, and where Le
+                 is not black: pmf = lightSampler.PMF(prev, light), pdf = light.PDF_Li(prev, d, true)
+              everything else is zero.
+     A caller loops infinite_index over 0 .. "infinite_lights" - 1 (wf_ctx_query) and adds the Le4; the loop usually runs once.  A scene
+     without infinite lights accepts index 0 (misses give zeros); any other index out of range is an argument error.
+   A light under an animated transformation takes its start transformation, and an emitter is never an animated primitive or part of an
+   object instance, as in the render. */
+int wf_light_sample_device(wf_ctx *ctx, int n, const int32_t *n_device /* may be NULL */, const float *planes_f, const int32_t *planes_i,
+                           const float *lambda4 /* [n][4] */, const float *u4 /* [n][4] */, const int32_t *side /* [n], may be NULL */,
+                           float *shadow_rays8 /* [n][8] */, float *L4 /* [n][4] */, float *wi_pdf4 /* [n][4] */, int32_t *light4 /* [n][4] */);
+int wf_light_emitted_device(wf_ctx *ctx, int n, const int32_t *n_device /* may be NULL */, const float *rays8 /* [n][8] */, const float *planes_f,
+                            const int32_t *planes_i, const float *lambda4 /* [n][4] */, int infinite_index,
+                            const float *prev_planes_f /* [4][n][4], may be NULL */, float *Le4 /* [n][4] */, float *pmf_pdf4 /* [n][4] */);
 int wf_device_alloc(wf_ctx *ctx, uint64_t nbytes, void **dptr);
 int wf_device_free(wf_ctx *ctx, void *dptr);
 int wf_device_upload(wf_ctx *ctx, void *dst_device, const void *src_host, uint64_t nbytes);
@@ -925,6 +975,9 @@ int wf_debug_counters(wf_ctx *ctx, uint64_t out[4], int reset);
    production closest-hit walk: 0 triangles only, 1 general primitives or object instances, 2 animated primitives), "shade_variant_<material type>"
    (the type's shade kernel: 0 / 1 lean without / with texture footprints, 2 general, 3 general + visible surface, moving camera, animated
    primitives or alpha-textured curves; the variants agree bit for bit),
+   "light_sample_rare" (the kernel of wf_light_sample_device: 1 = the one that samples every light type, chosen as "rare_lights" is),
+   "light_emitted_variant" (the kernel of wf_light_emitted_device: bit 0 portal infinite lights are reachable, bit 1 an emitter's alpha
+   texture), "lights" / "infinite_lights" (the sizes of the scene's light table and of its list of infinite lights),
    "pixels_per_pass" (the pixels of one band of wf_queues_alloc, 0 before it: the least n_max of wf_camera_rays_device),
    "stage_rounds" / "stage_grid_cap" (WF_STAGE_ROUNDS, WF_STAGE_GRID_CAP as the upload read them: the stage kernels' grids are
    min(one workgroup per block of the full queue, rounds x the workgroups the chip keeps resident of the kernel), at most the cap),

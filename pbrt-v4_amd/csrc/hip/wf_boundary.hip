@@ -2,7 +2,7 @@
 // samples, in device buffers (wf_*_device) or host arrays (wf_trace_*_host), through the walks and stages of the uploaded scene, and the
 // plain device-memory calls.  No kernel lives here: the walks are wf_backend.hip's, launched through the pointers PickWalkKernels /
 // PickStageKernels left in the context (ctx->walk, ctx->stage), and the boundary's own kernels are behind the launchers of
-// wf_boundary_intr.hip and wf_film_add.hip — so an edit to a call's argument checks leaves every device code object as it was.
+// wf_boundary_intr.hip, wf_film_add.hip and wf_boundary_light.hip — so an edit to a call's argument checks leaves every device code object as it was.
 // (A .hip unit for the LAUNCH* macros of wf_ctx.h; its device pass has nothing to emit.)
 #include "wf_ctx.h"
 
@@ -163,6 +163,66 @@ int wf_film_add_samples_device(wf_ctx *ctx, int n, const int32_t *n_device, cons
     Prof prof_(ctx, "Add film samples (device items)");
     const int e = filmadd::LaunchFilmAdd(ctx->stream, ctx->svDev, a);
     if (e) return fail(e, "%s: the launch failed: %s", fn, hipGetErrorString((hipError_t)e));
+    return 0;
+}
+// The scene's lights on a caller's device items (kernels and launchers: wf_boundary_light.hip).  Everything is checked before anything is
+// launched; the calls read the uploaded scene and the caller's buffers, nothing of the render's state.
+static const char *FirstNull(std::initializer_list<std::pair<const char *, const void *>> ps) {
+    for (const auto &p : ps) if (!p.second) return p.first;
+    return nullptr;
+}
+static const char *FirstMisaligned(std::initializer_list<std::pair<const char *, const void *>> ps, uintptr_t mask) {
+    for (const auto &p : ps) if ((uintptr_t)p.second & mask) return p.first;
+    return nullptr;
+}
+int wf_light_sample_device(wf_ctx *ctx, int n, const int32_t *n_device, const float *planes_f, const int32_t *planes_i, const float *lambda4, const float *u4,
+                           const int32_t *side, float *shadow_rays8, float *L4, float *wi_pdf4, int32_t *light4) {
+    const char *fn = "wf_light_sample_device";
+    if (!ctx) return fail(-1, "%s: null context", fn);
+    if (!ctx->sceneLoaded) return fail(-1, "%s: no scene uploaded", fn);
+    if (n < 0) return fail(-1, "%s: n = %d", fn, n);
+    if (n == 0) return 0;
+    if (n > (1 << 30)) return fail(-1, "%s: n = %d is more than 2^30 items", fn, n);
+    if (const char *w = FirstNull({{"planes_f", planes_f}, {"planes_i", planes_i}, {"lambda4", lambda4}, {"u4", u4}, {"shadow_rays8", shadow_rays8}, {"L4", L4},
+                                   {"wi_pdf4", wi_pdf4}, {"light4", light4}}))
+        return fail(-1, "%s: null %s", fn, w);
+    if (const char *w = FirstMisaligned({{"planes_f", planes_f}, {"planes_i", planes_i}, {"lambda4", lambda4}, {"u4", u4}, {"shadow_rays8", shadow_rays8}, {"L4", L4},
+                                         {"wi_pdf4", wi_pdf4}, {"light4", light4}}, 15u))
+        return fail(-1, "%s: %s is not aligned to 16 bytes (planes and rows are read and written 16 bytes at a time)", fn, w);
+    if (const char *w = FirstMisaligned({{"side", side}, {"n_device", n_device}}, 3u)) return fail(-1, "%s: %s is not aligned to 4 bytes", fn, w);
+    useDevice(ctx);
+    blight::SampleArgs a;
+    a.n = n; a.nDevice = n_device; a.planesF = planes_f; a.planesI = planes_i; a.lambda4 = lambda4; a.u4 = u4; a.side = side;
+    a.rays8 = shadow_rays8; a.L4 = L4; a.wiPdf4 = wi_pdf4; a.light4 = light4;
+    Prof prof_(ctx, "Sample lights (device items)");
+    const int e = blight::LaunchLightSample(ctx->stream, ctx->plan.rareLights, ctx->svDev, a);
+    if (e) return fail(e, "%s: the launch failed: %s", fn, hipGetErrorString((hipError_t)e));
+    return 0;
+}
+int wf_light_emitted_device(wf_ctx *ctx, int n, const int32_t *n_device, const float *rays8, const float *planes_f, const int32_t *planes_i, const float *lambda4,
+                            int infinite_index, const float *prev_planes_f, float *Le4, float *pmf_pdf4) {
+    const char *fn = "wf_light_emitted_device";
+    if (!ctx) return fail(-1, "%s: null context", fn);
+    if (!ctx->sceneLoaded) return fail(-1, "%s: no scene uploaded", fn);
+    if (n < 0) return fail(-1, "%s: n = %d", fn, n);
+    // (a scene without infinite lights accepts index 0: its misses are black)
+    if (infinite_index < 0 || infinite_index >= std::max(1, ctx->plan.nInfiniteLights))
+        return fail(-1, "%s: infinite_index %d, the scene has %d infinite lights", fn, infinite_index, ctx->plan.nInfiniteLights);
+    if (n == 0) return 0;
+    if (n > (1 << 30)) return fail(-1, "%s: n = %d is more than 2^30 items", fn, n);
+    if (const char *w = FirstNull({{"rays8", rays8}, {"planes_f", planes_f}, {"planes_i", planes_i}, {"lambda4", lambda4}, {"Le4", Le4}, {"pmf_pdf4", pmf_pdf4}}))
+        return fail(-1, "%s: null %s", fn, w);
+    if (const char *w = FirstMisaligned({{"rays8", rays8}, {"planes_f", planes_f}, {"planes_i", planes_i}, {"lambda4", lambda4}, {"prev_planes_f", prev_planes_f},
+                                         {"Le4", Le4}, {"pmf_pdf4", pmf_pdf4}}, 15u))
+        return fail(-1, "%s: %s is not aligned to 16 bytes (rays, planes and rows are read and written 16 bytes at a time)", fn, w);
+    if ((uintptr_t)n_device & 3u) return fail(-1, "%s: n_device is not aligned to 4 bytes", fn);
+    useDevice(ctx);
+    blight::EmittedArgs a;
+    a.n = n; a.infiniteIndex = infinite_index; a.nDevice = n_device; a.rays8 = rays8; a.planesF = planes_f; a.planesI = planes_i; a.lambda4 = lambda4;
+    a.prevF = prev_planes_f; a.Le4 = Le4; a.pmfPdf4 = pmf_pdf4;
+    Prof prof_(ctx, "Emitted radiance (device items)");
+    const int e = blight::LaunchLightEmitted(ctx->stream, ctx->plan.emittedVariant, ctx->svDev, a);
+    if (e) return fail(e, "%s: the launch failed: %s", fn, e < 0 ? "the library holds no kernel for the scene's light_emitted_variant" : hipGetErrorString((hipError_t)e));
     return 0;
 }
 // room for n items in ctx->trScratch, the wavefront's arrays among them if the scene's plan routes through it.  Growth waits for the

@@ -29,6 +29,7 @@
 #include "wf_film_develop.h"
 #include "wf_boundary_intr.h"
 #include "wf_film_add.h"
+#include "wf_boundary_light.h"
 
 using namespace wf;
 using namespace wf::planning;

@@ -202,11 +202,17 @@ static void ClassifyScene(const wf_scene_desc *d, const Switches &sw, ScenePlan 
     // 214 VGPRs) and emitters with an alpha texture (the texture-graph evaluator): LightSampleLi<RARE>, AreaLightL<ALPHA> (wf_lights.h)
     // (WF_RARE_LIGHTS=1 forces both: the RARE kernels are supersets, they sample every light type)
     if (sw.rareLights) plan->rareLights = plan->portalLights = true;
+    bool emitterAlpha = sw.rareLights;
     for (int i = 0; i < d->n_lights; ++i) {
         const wf_light &l = d->lights[i];
         if (l.type == WF_LIGHT_PORTAL_INFINITE) plan->rareLights = plan->portalLights = true;
         if (l.type == WF_LIGHT_DIFFUSE_AREA && (l.tri >= d->n_triangles || l.alpha_tex_plus1 != 0)) plan->rareLights = true;
+        if (l.type == WF_LIGHT_DIFFUSE_AREA && l.alpha_tex_plus1 != 0) emitterAlpha = true;
     }
+    // the emission kernel of the device-buffer boundary (ScenePlan::emittedVariant)
+    plan->emittedVariant = EmittedVariant(plan->portalLights, emitterAlpha, plan->rareLights);
+    plan->nLights = d->n_lights;
+    plan->nInfiniteLights = d->n_infinite_lights;
     for (int i = 0; i < d->n_quadrics; ++i) {
         if (d->meshes[d->quadrics[i].mesh].alpha_tex >= 0) plan->haveQuadricAlpha = true;
         if (d->quadrics[i].type == WF_QUADRIC_CURVE) plan->haveCurves = true;
@@ -335,7 +341,11 @@ bool wf::planning::PlanValue(const ScenePlan &plan, const char *key, int64_t *va
     else if (k == "instances") *value = plan.nInstances;
     else if (k == "nested_animated") *value = plan.nestedAnimated;
     else if (k == "intr_variant") *value = plan.intrVariant;   // k_hit_interaction<GENERAL, CURVE_ALPHA, ANIM> (IntrVariant, wf_plan.h)
-    else if (k == "tr_route") *value = plan.trRoute;   // -1 no media, 0 k_shadow_tr, 1 k_shadow_tr_fast, 2 the transmittance wavefront
+    else if (k == "light_sample_rare") *value = plan.rareLights;          // k_light_sample<RARE> (wf_boundary_light.hip)
+    else if (k == "light_emitted_variant") *value = plan.emittedVariant;  // k_light_emitted<PORTAL, ALPHA, AREA_RARE> (EmittedVariant, wf_plan.h)
+    else if (k == "lights") *value = plan.nLights;
+    else if (k == "infinite_lights") *value = plan.nInfiniteLights;
+    else if (k == "tr_route") *value = plan.trRoute;  // -1 no media, 0 k_shadow_tr, 1 k_shadow_tr_fast, 2 the transmittance wavefront
     else if (k == "camera_anim") *value = plan.cameraAnim;   // k_gen_camera_rays<ANIM>
     else if (k == "route_variant") *value = plan.routeVariant;   // 0 k_route_hits<false>, 1 <true>, 2 <true, true>
     else if (TypeKey(k, "shade_variant_") >= 0) *value = plan.shadeVariant[TypeKey(k, "shade_variant_")];   // k_mat_shade's variant for material type t

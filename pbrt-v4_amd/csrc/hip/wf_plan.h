@@ -144,7 +144,17 @@ struct ScenePlan {
     // encodes it: GENERAL — the scene has quadrics / patches / curves; CURVE_ALPHA — one of its curves carries an alpha texture; ANIM — it
     // has animated primitives (nested placements included).  0: the lean triangle kernel.
     int intrVariant = 0;
+    // The kernels of wf_light_sample_device / wf_light_emitted_device (wf_boundary_light.hip): k_light_sample<RARE> follows rareLights
+    // (k_mat_nee's predicate); k_light_emitted<PORTAL, ALPHA, AREA_RARE> is encoded as EmittedVariant() below: PORTAL — portalLights
+    // (LightLe<RARE>), ALPHA — an emitter carries an alpha texture (AreaLightL<ALPHA>), AREA_RARE — rareLights (the PDF of an emitter that
+    // is not a triangle).  WF_RARE_LIGHTS=1 forces the general ones.
+    int emittedVariant = 0;
+    int nLights = 0, nInfiniteLights = 0;   // the sizes of the light table and of the list of infinite lights ("lights", "infinite_lights")
 };
+constexpr int EMITTED_PORTAL = 1, EMITTED_ALPHA = 2, EMITTED_AREA_RARE = 4;
+constexpr int EmittedVariant(bool portal, bool alpha, bool areaRare) {
+    return (portal ? EMITTED_PORTAL : 0) | (alpha ? EMITTED_ALPHA : 0) | (areaRare ? EMITTED_AREA_RARE : 0);
+}
 // The encoding of ScenePlan::intrVariant ("intr_variant"): the one place it is written down — the planner builds the value with it, the
 // launcher of wf_boundary_intr.hip switches on it.  CURVE_ALPHA exists only with GENERAL (a curve is a general primitive).
 constexpr int INTR_GENERAL = 1, INTR_CURVE_ALPHA = 2, INTR_ANIM = 4;

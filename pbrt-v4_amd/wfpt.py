@@ -76,7 +76,7 @@ ABI_SYMBOLS = [
     "wf_trace_closest_device_t", "wf_trace_any_device_t", "wf_trace_shadow_tr_device", "wf_trace_one_random_device",
     "wf_film_spectral_upload", "wf_film_gbuffer_upload", "wf_film_channel_count", "wf_film_develop_device", "wf_film_develop_rgb_device",
     "wf_hit_interaction_device", "wf_camera_rays_device",
-    "wf_camera_samples_device", "wf_film_add_samples_device",
+    "wf_camera_samples_device", "wf_film_add_samples_device", "wf_light_sample_device", "wf_light_emitted_device",
 ]
 # the planes of wf_hit_interaction_device (include/wf_abi.h): WF_INTR_FPLANES float planes, WF_INTR_IPLANES int planes, 4 words per item each
 INTR_FPLANES = 11
@@ -566,6 +566,100 @@ class Scene:
         hits = self.trace_device(rays)
         r = self.interactions_device(rays, hits)
         r.update(rays8=rays, pixel_xy=pix, lambda4=lam, hits=hits)
+        return r
+
+    @staticmethod
+    def _planes(it, what):
+        """(planes_f, planes_i, n) of an interactions_device dict, or of a (planes_f [11, n, 4], planes_i [2, n, 4]) pair a caller made"""
+        import torch
+        F, I = (it["planes_f"], it["planes_i"]) if isinstance(it, dict) else it
+        if not (isinstance(F, torch.Tensor) and isinstance(I, torch.Tensor) and F.dtype == torch.float32 and I.dtype == torch.int32 and F.dim() == 3
+                and I.dim() == 3 and F.shape[0] == INTR_FPLANES and I.shape[0] == INTR_IPLANES and F.shape[2] == 4 and I.shape[2] == 4
+                and F.shape[1] == I.shape[1]):
+            raise WfError("%s: it is the dict of interactions_device, or (planes_f float32 [%d, n, 4], planes_i int32 [%d, n, 4])" % (what, INTR_FPLANES, INTR_IPLANES))
+        return F, I, F.shape[1]
+
+    @staticmethod
+    def _count_arg(n_device, what):
+        import torch
+        if n_device is not None and not (isinstance(n_device, torch.Tensor) and n_device.numel() == 1 and n_device.dtype == torch.int32):
+            raise WfError("%s: n_device is an int32 tensor of one element" % what)
+        return n_device
+
+    def sample_lights_device(self, it, lambda4, u4, side=None, n_device=None, out=None):
+        """wf_light_sample_device: the light half of next-event estimation for n device items, by the render's own light sampler and
+        lights.  it: the dict of interactions_device / first_hit (or its two plane tensors); lambda4 float32 [n, 4]; u4 float32 [n, 4]
+        rows {uc, u[0], u[1], unused}; side int32 [n] (None: all 0): 0 the light sees the position interval, +1 the point offset along
+        wo (a BSDF that only reflects), -1 the point offset against wo (one that reflects and transmits).  Returns a dict of views:
+        "shadow_rays8" float32 [n, 8] (ready for trace_device(any_hit=True) / trace_shadow_tr_device; d is not normalised), "L" float32
+        [n, 4], "wi" float32 [n, 3], "pdf" float32 [n] (of the direction), "pmf" float32 [n] (of the light), "light" int32 [n] (-1:
+        none), "flags" int32 [n] (bit 0: a delta light), "medium" int32 [n], and the tensors themselves as "L4", "wi_pdf4", "light4".
+        A row the render would not take to its BSDF has L = 0, pdf = 0 and a zero ray.  n_device: an int32 tensor of one element;
+        only the first min(n, n_device) rows are written.  out: the dict of an earlier call with the same n, written into again."""
+        import torch
+        _, hip = libs()
+        F, I, n = self._planes(it, "sample_lights_device")
+        self._as(lambda4, torch.float32, 4, "sample_lights_device lambda4")
+        self._as(u4, torch.float32, 4, "sample_lights_device u4")
+        if side is not None:
+            self._as(side, torch.int32, 0, "sample_lights_device side")
+        if any(t.shape[0] != n for t in (lambda4, u4) + ((side,) if side is not None else ())):
+            raise WfError("sample_lights_device: the arrays hold different numbers of items")
+        self._count_arg(n_device, "sample_lights_device")
+        dev = F.device
+        if out is None:
+            rays = torch.empty((n, 8), dtype=torch.float32, device=dev)
+            L4 = torch.empty((n, 4), dtype=torch.float32, device=dev)
+            wp = torch.empty((n, 4), dtype=torch.float32, device=dev)
+            li = torch.empty((n, 4), dtype=torch.int32, device=dev)
+        else:
+            rays, L4, wp, li = out["shadow_rays8"], out["L4"], out["wi_pdf4"], out["light4"]
+            if rays.shape != (n, 8) or L4.shape != (n, 4) or wp.shape != (n, 4) or li.shape != (n, 4):
+                raise WfError("sample_lights_device: out is the dict of a call with the same number of items")
+        r = {"shadow_rays8": rays, "L4": L4, "wi_pdf4": wp, "light4": li, "L": L4, "wi": wp[:, :3], "pdf": wp[:, 3], "light": li[:, 0],
+             "pmf": li[:, 1].view(torch.float32), "flags": li[:, 2], "medium": li[:, 3]}
+        if n == 0:
+            return r
+        ts = [F, I, lambda4, u4, rays, L4, wp, li] + [t for t in (side, n_device) if t is not None]
+        self._device_call("wf_light_sample_device", hip.wf_light_sample_device, [C.c_void_p, C.c_int] + [C.c_void_p] * 10, ts, n,
+                          n_device.data_ptr() if n_device is not None else None, F.data_ptr(), I.data_ptr(), lambda4.data_ptr(), u4.data_ptr(),
+                          side.data_ptr() if side is not None else None, rays.data_ptr(), L4.data_ptr(), wp.data_ptr(), li.data_ptr())
+        return r
+
+    def emitted_device(self, rays8, it, lambda4, infinite_index=0, prev=None, out=None, n_device=None):
+        """wf_light_emitted_device: the emission at the end of n device rays — rays8 float32 [n, 8], `it` the interactions of their hits
+        (as sample_lights_device takes them), lambda4 float32 [n, 4].  A hit row on an emitter gets the emitter's radiance towards the
+        ray's origin (for infinite_index 0 only), a miss row the radiance of the scene's infinite light number infinite_index
+        (query("infinite_lights") of them: sum the calls).  prev: the interactions of the vertices the rays LEFT (a dict of
+        interactions_device, or a float32 [>= 4, n, 4] tensor of planes 0 - 3): with it the rows also get the light sampler's
+        probability of the light and the PDF of the ray's direction, both as seen from that vertex — the two factors of the MIS
+        weight.  Returns a dict of views: "Le" float32 [n, 4], "pmf" float32 [n], "pdf" float32 [n], and "Le4", "pmf_pdf4"."""
+        import torch
+        _, hip = libs()
+        self._as(rays8, torch.float32, 8, "emitted_device rays8")
+        F, I, n = self._planes(it, "emitted_device")
+        self._as(lambda4, torch.float32, 4, "emitted_device lambda4")
+        if rays8.shape[0] != n or lambda4.shape[0] != n:
+            raise WfError("emitted_device: the arrays hold different numbers of items")
+        P = None
+        if prev is not None:
+            P = prev["planes_f"] if isinstance(prev, dict) else prev
+            if not (isinstance(P, torch.Tensor) and P.dtype == torch.float32 and P.dim() == 3 and P.shape[0] >= 4 and P.shape[1] == n and P.shape[2] == 4):
+                raise WfError("emitted_device: prev is a dict of interactions_device or a float32 [>= 4, n, 4] tensor of planes")
+        self._count_arg(n_device, "emitted_device")
+        if out is None:
+            Le = torch.empty((n, 4), dtype=torch.float32, device=F.device)
+            pp = torch.empty((n, 4), dtype=torch.float32, device=F.device)
+        else:
+            Le, pp = out["Le4"], out["pmf_pdf4"]
+            if Le.shape != (n, 4) or pp.shape != (n, 4):
+                raise WfError("emitted_device: out is the dict of a call with the same number of items")
+        r = {"Le4": Le, "pmf_pdf4": pp, "Le": Le, "pmf": pp[:, 0], "pdf": pp[:, 1]}
+        ts = [rays8, F, I, lambda4, Le, pp] + [t for t in (P, n_device) if t is not None]
+        # (n = 0 still goes through: the index is checked)
+        self._device_call("wf_light_emitted_device", hip.wf_light_emitted_device, [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 3, ts, n,
+                          n_device.data_ptr() if n_device is not None else None, rays8.data_ptr(), F.data_ptr(), I.data_ptr(), lambda4.data_ptr(), int(infinite_index),
+                          P.data_ptr() if P is not None else None, Le.data_ptr(), pp.data_ptr())
         return r
 
     def bounds(self):

@@ -1,0 +1,144 @@
+"""wf_light_sample_device and wf_light_emitted_device without a GPU: declared, exported, listed, refusing a null context by name, bound by
+Scene, planned per scene — and the per-row bodies their kernels run (pbrt-v4_amd/csrc/hip/wf_boundary_light.h), compiled for the host
+as the stand-alone program tools/light_sample_check.cpp, against a direct composition of the render's own light functions on the light
+tables of eleven scenes: every output word equal, also under the address and undefined-behaviour sanitizers."""
+import ctypes as C
+import json
+import os
+import re
+import subprocess
+
+import pytest
+
+from conftest import GOLDEN, ROOT
+from test_abi import declared
+
+NEW_ABI = ["wf_light_sample_device", "wf_light_emitted_device"]
+SRC = os.path.join(ROOT, "pbrt-v4_amd")
+FIXTURES = ["cornell64", "materials_lights", "materials_lights_power", "envmap", "lights_extra", "portal_light", "portal_uniform", "quadrics",
+            "bilinear_lights", "arealight_image", "arealight_alpha"]
+ROWS = 20000
+
+
+def test_new_symbols_declared_exported_and_listed(wfpt):
+    _, hip = wfpt.libs()
+    abi = declared("wf_abi.h")
+    for name in NEW_ABI:
+        assert name in abi and name in wfpt.ABI_SYMBOLS and hasattr(hip, name), name
+    assert sorted(wfpt.ABI_SYMBOLS) == abi
+    hip.wf_abi_version.restype = C.c_int
+    assert hip.wf_abi_version() == 12
+    assert re.search(r"#define\s+WF_ABI_VERSION\s+12\b", open(os.path.join(ROOT, "include", "wf_abi.h")).read())
+
+
+def test_null_context_is_refused_by_name_before_anything_else(wfpt):
+    _, hip = wfpt.libs()
+    f = hip.wf_light_sample_device
+    f.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 10
+    g = hip.wf_light_emitted_device
+    g.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 3
+    for n in (0, -3, 16):
+        assert f(None, n, *[None] * 10) != 0
+        assert b"wf_light_sample_device: null context" in hip.wf_last_error()
+        assert g(None, n, None, None, None, None, None, 0, None, None, None) != 0
+        assert b"wf_light_emitted_device: null context" in hip.wf_last_error()
+
+
+def test_scene_binds_the_two_calls(wfpt):
+    for name in ("sample_lights_device", "emitted_device"):
+        assert callable(getattr(wfpt.Scene, name))
+
+
+@pytest.mark.parametrize("name, rare, emitted, lights, infinite", [
+    ("cornell64", 0, 0, 2, 0), ("envmap", 0, 0, 1, 1), ("portal_light", 1, 5, 2, 1), ("quadrics", 1, 4, 4, 1), ("arealight_alpha", 1, 6, 8, 0)])
+def test_the_plan_picks_the_kernels_from_the_scenes_lights(wfpt, name, rare, emitted, lights, infinite, monkeypatch):
+    """light_sample_rare follows rare_lights; light_emitted_variant: bit 0 a portal light, bit 1 an emitter's alpha texture, bit 2 an
+    emitter that is not a triangle (or either of the others); WF_RARE_LIGHTS=1 forces the general kernels"""
+    monkeypatch.delenv("WF_RARE_LIGHTS", raising=False)
+    s = wfpt.Scene(path=os.path.join(GOLDEN, name + ".pbrt"), spp=1)
+    assert s.plan("light_sample_rare") == s.plan("rare_lights") == rare
+    assert s.plan("light_emitted_variant") == emitted
+    assert (s.plan("lights"), s.plan("infinite_lights")) == (lights, infinite)
+    monkeypatch.setenv("WF_RARE_LIGHTS", "1")
+    assert s.plan("light_sample_rare") == 1 and s.plan("light_emitted_variant") == 7
+    s.close()
+
+
+@pytest.fixture(scope="module")
+def check_program(built):
+    """pbrt-v4_amd/_build/light_sample_check: part of the Makefile's `all` (an up-to-date build makes this a no-op)"""
+    subprocess.run(["make", "-C", SRC, "_build/light_sample_check"], check=True, capture_output=True)
+    return os.path.join(SRC, "_build", "light_sample_check")
+
+
+def _assert_clean(p, name):
+    assert p.returncode == 0, p.stdout + p.stderr
+    r = json.loads(p.stdout.strip().splitlines()[-1])
+    assert r["rows"] == ROWS and r["mismatches"] == 0, r
+    assert r["lights_chosen"] > ROWS // 2 and r["usable"] > 0, r            # the rows reach the lights
+    if name != "lights_extra":                                               # (five delta lights: nothing emits towards a ray)
+        assert r["emitting"] > 0 and r["with_pdf"] > 0, r
+    return r
+
+
+@pytest.mark.parametrize("name", FIXTURES)
+def test_per_row_bodies_match_the_renders_light_functions(check_program, name):
+    """SampleRequest / SampleFinish / EmittedItem against SampleLightDirect<true>, SpawnRayTo, LightSamplerPMF, LightPDF_Li, LightLe and
+    AreaLightL called directly: 20 000 rows per call, every side, misses and invalid rows between hits, every infinite index, with and
+    without the previous vertex — 0 mismatches"""
+    _assert_clean(subprocess.run([check_program, "--self", os.path.join(GOLDEN, name + ".pbrt"), str(ROWS)], capture_output=True, text=True), name)
+
+
+@pytest.fixture(scope="module")
+def sanitized_program(built, tmp_path_factory):
+    """the same program with the host units it links, every one compiled by g++ with -fsanitize=address,undefined: a plain executable
+    with both runtimes linked in, so it neither needs one preloaded nor minds what else a process here has preloaded"""
+    out = str(tmp_path_factory.mktemp("light_sample_check_san"))
+    san = "-g -fsanitize=address,undefined -fno-sanitize-recover=undefined -static-libasan -static-libubsan"
+    subprocess.run(["make", "-C", SRC, "-j8", "OUT=" + out, "CXX=g++", "CXXFLAGS=-std=c++17 -O1 -mfma -ffp-contract=off -fPIC -pthread -I ../include",
+                    "SAN=" + san, os.path.join(out, "light_sample_check")], check=True, capture_output=True)
+    return os.path.join(out, "light_sample_check")
+
+
+@pytest.mark.parametrize("name", ["materials_lights", "portal_light"])
+def test_per_row_bodies_under_the_sanitizers(sanitized_program, name):
+    p = subprocess.run([sanitized_program, "--datadir", os.path.join(SRC, "data"), "--self", os.path.join(GOLDEN, name + ".pbrt"), str(ROWS)],
+                       capture_output=True, text=True)
+    _assert_clean(p, name)
+    assert "runtime error" not in p.stderr and "AddressSanitizer" not in p.stderr, p.stderr
+
+
+def test_eval_answers_with_the_direct_composition(check_program, tmp_path):
+    """--eval, the expected-output side of the GPU tests: one hand-made row of each call on cornell64 — a point under the ceiling light
+    is given the light, a usable ray that ends on it and the reciprocal of the light count as PMF bits of a float; a miss gets nothing"""
+    import numpy as np
+    n = 2
+    pf = np.zeros((11, n, 4), np.float32)
+    pi = np.zeros((2, n, 4), np.int32)
+    # rendering space has the camera (2.78 2.73 -8) at its origin: the light's centre (2.78 5.486 2.795) is straight above this point
+    pf[0, :, :3] = pf[1, :, :3] = (0.0, 0.0, 10.795)
+    pf[2, :, :3] = pf[3, :, :3] = (0, 1, 0)
+    pf[2, :, 3] = 0.25
+    pf[4, :, :3] = (0, 1, 0)
+    pi[0] = -1
+    pi[1, 0, 1] = 1                                                           # row 0 a hit, row 1 a miss
+    lam = np.tile(np.array([450, 520, 590, 660], np.float32), (n, 1))
+    u4 = np.full((n, 4), 0.5, np.float32)
+    side = np.array([1, 1], np.int32)
+    head = np.array([0x4c534331, 0, n, 0, 1, 0, 0, 0], np.int32)
+    a, b = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
+    with open(a, "wb") as f:
+        for x in (head, pf, pi, lam, u4, side):
+            f.write(x.tobytes())
+    subprocess.run([check_program, "--eval", os.path.join(GOLDEN, "cornell64.pbrt"), a, b], check=True)
+    raw = open(b, "rb").read()
+    assert len(raw) == n * (32 + 16 + 16 + 16)
+    rays = np.frombuffer(raw, np.float32, n * 8).reshape(n, 8)
+    L = np.frombuffer(raw, np.float32, n * 4, n * 32).reshape(n, 4)
+    wp = np.frombuffer(raw, np.float32, n * 4, n * 48).reshape(n, 4)
+    light = np.frombuffer(raw, np.int32, n * 4, n * 64).reshape(n, 4)
+    assert light[0, 0] in (0, 1) and light[0, 3] == -1 and light[0, 1:2].view(np.float32)[0] > 0
+    assert (L[0] > 0).all() and wp[0, 3] > 0 and wp[0, 1] > 0.9              # the light is above
+    assert rays[0, 6] == np.float32(1) - np.float32(0.0001) and rays[0, 7] == np.float32(0.25)
+    assert abs(np.linalg.norm(rays[0, 3:6]) - 1) > 1e-3                       # d is not normalised: it ends at the light
+    assert not rays[1].any() and not L[1].any() and not wp[1].any() and tuple(light[1]) == (-1, 0, 0, -1)
