@@ -844,7 +844,8 @@ int wf_film_add_samples_device(wf_ctx *ctx, int n, const int32_t *n_device /* ma
                                const float *filter_weight /* [n] */, uint32_t *rejected_device /* may be NULL */);
 /* The scene's LIGHTS on a caller's DEVICE items: the light half of next-event estimation and the emission of a ray's end, computed by the
    render's own functions (the light samplers, SampleLi, PDF_Li, L, Le of every light type) — with them a caller's integrator writes direct
-   lighting, emission and their MIS weights against the lights the render uses.  The BSDF is the caller's.  Both calls take the planes
+   lighting, emission and their MIS weights against the lights the render uses.  The BSDF is the caller's own, or the scene's
+   (wf_bsdf_make_device / wf_bsdf_eval_device below, which also answer `side`).  Both calls take the planes
    wf_hit_interaction_device writes (planes_f [WF_INTR_FPLANES][n][4], planes_i [WF_INTR_IPLANES][n][4], plane stride n), so its output
    feeds them as it is; a caller with points of its own fabricates the planes it needs: pi lower = pi upper = p and n = ns = 0 is the
    reference's context of a point in a medium.  Both are launched on the context's stream (wf_stream) and NOT synchronised; every
@@ -892,6 +893,72 @@ int wf_light_sample_device(wf_ctx *ctx, int n, const int32_t *n_device /* may be
 int wf_light_emitted_device(wf_ctx *ctx, int n, const int32_t *n_device /* may be NULL */, const float *rays8 /* [n][8] */, const float *planes_f,
                             const int32_t *planes_i, const float *lambda4 /* [n][4] */, int infinite_index,
                             const float *prev_planes_f /* [4][n][4], may be NULL */, float *Le4 /* [n][4] */, float *pmf_pdf4 /* [n][4] */);
+/* The scene's BSDFs on a caller's DEVICE items: the material half of a path vertex, computed by the render's own functions — the texture
+   graphs, normal and bump maps, the MixMaterial choice, every material type's GetBxDF and BSDF::f / PDF / Sample_f.  With them and the
+   calls above a caller writes a complete path tracer against the render's own scene.  Both calls take the planes
+   wf_hit_interaction_device writes (planes_f [WF_INTR_FPLANES][n][4], planes_i [WF_INTR_IPLANES][n][4], plane stride n).  Both are
+   launched on the context's stream (wf_stream) and NOT synchronised; every argument is checked before anything is launched (planes,
+   records and 4-float arrays are aligned to 16 bytes, regularize and n_device to 4; all device pointers of the context's device; n < 0
+   is an argument error, n = 0 touches nothing); n_device is NULL or a device word: min(n, *n_device) rows are processed, every one of
+   them is written exactly once per call as whole 16-byte stores, and the rows after them are not written.  They need an uploaded scene,
+   no queues, and touch none of the render's queues, pixel state or statistics.  A call is one type-independent launch plus one launch
+   per material type the scene holds ("material_types", wf_ctx_query: bit t = wf_material_type t).
+
+   wf_bsdf_make_device: EvaluateMaterialAndBSDF (surfscatter.cpp:57-145) from the texture context to bsdf.Regularize() —
+     1  the MixMaterial resolve (intersect.h:92-97, materials.h:284-294); its hash takes wo = -d of rays8 as the ray carries it, not
+        normalised, which is why the ray is an input
+     2  the TextureEvalContext from planes 0, 1, 2: pi's midpoint, (u, v), n
+     3  the footprint: Approximate_dp_dxy at the row's time and the (u, v) differentials from planes 5, 6, unless the scene disables
+        texture filtering — with the wavefront path's quirks: ctx.dpdx = ctx.dpdy = 0, and n = 0 for the displacement lookups
+     4  the normal map or the bump map (planes 3 and 7 - 10)     5  the material's GetBxDF
+     6  bsdf.Regularize() where regularize[i] != 0 (regularize may be NULL: nowhere).  The render's rule is "the scene's regularize
+        option is set and the path has had a non-specular bounce": the path is the caller's, so the flag is.
+     reads    rays8 (d);  planes_f 0 - 10;  planes_i 0 (.x: material), 1 (.y: valid);  lambda4[i] = the four wavelengths
+     writes   bsdf4[i] = { the BxDFFlags (bit 0 reflection, 1 transmission, 2 diffuse, 3 glossy, 4 specular) | bit 8 when GetBxDF
+                             terminated the secondary wavelengths (a dispersive dielectric: spectrally varying eta),
+                           the side for wf_light_sample_device (surfscatter.cpp:256-261): +1 a BSDF that reflects and does not
+                             transmit, -1 one that does both, 0 one that only transmits — and 0 for a BSDF that is specular only,
+                             whose vertex takes no light sample at all,
+                           the material id after the mix resolve,   the material's wf_material_type }
+              bsdf_rec = WF_BSDF_PLANES planes of stride n, OPAQUE to the caller and valid for this context and scene only: a header
+                         {type, flags, material, 0}, the final shading normal, the final shading dpdu, the BxDF's numbers.
+                         ONE plane of it is the caller's to read: plane 1, {the final ns, 0} — the shading normal after the normal or
+                         bump map.  The render's LightSampleContext carries THAT normal (surfscatter.cpp:251-255 builds it from the
+                         BSDF's frame), for the light sample of this vertex and, kept with the indirect ray, for the MIS weights at
+                         the next one: a caller who wants the render's light samples copies its xyz over plane 3 of the planes_f it
+                         hands wf_light_sample_device / wf_light_emitted_device (prev_planes_f), on the rows with a BSDF.
+     When bit 8 is set the caller does to ITS wavelength PDFs (lambda_pdf4 of wf_camera_samples_device) what
+     SampledWavelengths::TerminateSecondary does: if pdf[1], pdf[2] and pdf[3] are not all zero already, pdf[1] = pdf[2] = pdf[3] = 0
+     and pdf[0] = pdf[0] / 4 (one fp32 division); if they are, nothing.  The wavelengths themselves stay.
+     A row without a BSDF — valid != 1, an interface surface (material -1), a material id outside the scene's table — is all zeros in
+     both outputs (type 0): a stale buffer does not walk the tables.
+
+   wf_bsdf_eval_device: BSDF<BxDF> rebuilt from the record, with wo from plane 4.  At least one of wi4 and u4 is given; the outputs
+   of an absent half may be NULL and are not written.
+     wi4[i] = {wi, unused}:             f4[i] = bsdf.f(wo, wi);   pdf4[i] = {bsdf.PDF(wo, wi), AbsDot(wi, ns), 0, 0}
+     u4[i] = {uc, u[0], u[1], unused}:  bs = bsdf.Sample_f(wo, uc, u), radiance transport, every lobe —
+              sample_f4[i]   = bs.f
+              sample_pdf4[i] = {bs.pdf, the PDF the render divides r_u by (bsdf.PDF(wo, bs.wi) where bs.pdfIsProportional — the
+                                layered types —, else bs.pdf), AbsDot(bs.wi, ns), bs.eta}
+              sample_i4[i]   = {1, the sample's BxDFFlags, the next ray's medium (Dot(wi, n) > 0 ? medium outside : medium inside of
+                                planes_i; -1 in a scene without media), pdfIsProportional}
+              next_rays8[i]  = {OffsetRayOrigin(pi, n, wi), wi, tMax = infinity, the row's time}: a ray of wf_trace_closest_device_t
+              An invalid sample is zeros in all four.
+     The cosines and the divisor are handed out because a caller's own Dot would not reproduce the device's rounding; with them
+     beta = f * cos / pdf, r_l = r_u / pdf_mis and etaScale * eta^2 are single fp32 operations the caller does, equal to the render's.
+     A row whose record names no BSDF of this scene (type 0, or a header that does not agree with the scene's material table) is zeros.
+     The kernels never follow an address read from the record, and the scene's tables are indexed by the header only after it is checked.
+   NOT here: importance transport (TransportMode::Importance); rho / the GBuffer's albedo; the BSSRDF — a subsurface material's row is
+   its dielectric boundary, a transmitted sample says so in its flags and the caller has no SampleSubsurface to continue it with;
+   Russian roulette, which is the caller's. */
+#define WF_BSDF_PLANES 10
+int wf_bsdf_make_device(wf_ctx *ctx, int n, const int32_t *n_device /* may be NULL */, const float *rays8 /* [n][8] */, const float *planes_f,
+                        const int32_t *planes_i, const float *lambda4 /* [n][4] */, const int32_t *regularize /* [n], may be NULL: none */,
+                        float *bsdf_rec /* [WF_BSDF_PLANES][n][4] */, int32_t *bsdf4 /* [n][4] */);
+int wf_bsdf_eval_device(wf_ctx *ctx, int n, const int32_t *n_device /* may be NULL */, const float *bsdf_rec, const float *planes_f,
+                        const int32_t *planes_i, const float *wi4 /* [n][4], may be NULL */, const float *u4 /* [n][4], may be NULL */,
+                        float *f4, float *pdf4,                                                    /* the wi half */
+                        float *next_rays8, float *sample_f4, float *sample_pdf4, int32_t *sample_i4 /* the u half */);
 int wf_device_alloc(wf_ctx *ctx, uint64_t nbytes, void **dptr);
 int wf_device_free(wf_ctx *ctx, void *dptr);
 int wf_device_upload(wf_ctx *ctx, void *dst_device, const void *src_host, uint64_t nbytes);

@@ -2,9 +2,10 @@
 // samples, in device buffers (wf_*_device) or host arrays (wf_trace_*_host), through the walks and stages of the uploaded scene, and the
 // plain device-memory calls.  No kernel lives here: the walks are wf_backend.hip's, launched through the pointers PickWalkKernels /
 // PickStageKernels left in the context (ctx->walk, ctx->stage), and the boundary's own kernels are behind the launchers of
-// wf_boundary_intr.hip, wf_film_add.hip and wf_boundary_light.hip — so an edit to a call's argument checks leaves every device code object as it was.
+// wf_boundary_intr.hip, wf_film_add.hip, wf_boundary_light.hip and wf_boundary_bsdf.hip — so an edit to a call's argument checks leaves every device code object as it was.
 // (A .hip unit for the LAUNCH* macros of wf_ctx.h; its device pass has nothing to emit.)
 #include "wf_ctx.h"
+#include "wf_boundary_bsdf.h"
 
 extern "C" {
 
@@ -223,6 +224,80 @@ int wf_light_emitted_device(wf_ctx *ctx, int n, const int32_t *n_device, const f
     Prof prof_(ctx, "Emitted radiance (device items)");
     const int e = blight::LaunchLightEmitted(ctx->stream, ctx->plan.emittedVariant, ctx->svDev, a);
     if (e) return fail(e, "%s: the launch failed: %s", fn, e < 0 ? "the library holds no kernel for the scene's light_emitted_variant" : hipGetErrorString((hipError_t)e));
+    return 0;
+}
+// The scene's BSDFs on a caller's device items (kernels and launchers: wf_boundary_bsdf.hip, one code object per material type).
+// Everything is checked before anything is launched; the calls read the uploaded scene and the caller's buffers, nothing of the
+// render's state.  A call is the type-independent launch (type 0) and then one launch per material type the scene's plan says is present.
+using BsdfMakeFn = int (*)(void *, const SceneView *, const bbsdf::MakeArgs *);
+using BsdfEvalFn = int (*)(void *, const SceneView *, const bbsdf::EvalArgs *);
+static const BsdfMakeFn kBsdfMake[WF_MAT_NTYPES] = {wf_launch_bsdf_make_0, wf_launch_bsdf_make_1, wf_launch_bsdf_make_2, wf_launch_bsdf_make_3,
+                                                    wf_launch_bsdf_make_4, wf_launch_bsdf_make_5, wf_launch_bsdf_make_6, wf_launch_bsdf_make_7,
+                                                    wf_launch_bsdf_make_8, wf_launch_bsdf_make_9, wf_launch_bsdf_make_10};
+static const BsdfEvalFn kBsdfEval[WF_MAT_NTYPES] = {wf_launch_bsdf_eval_0, wf_launch_bsdf_eval_1, wf_launch_bsdf_eval_2, wf_launch_bsdf_eval_3,
+                                                    wf_launch_bsdf_eval_4, wf_launch_bsdf_eval_5, wf_launch_bsdf_eval_6, wf_launch_bsdf_eval_7,
+                                                    wf_launch_bsdf_eval_8, wf_launch_bsdf_eval_9, wf_launch_bsdf_eval_10};
+int wf_bsdf_make_device(wf_ctx *ctx, int n, const int32_t *n_device, const float *rays8, const float *planes_f, const int32_t *planes_i, const float *lambda4,
+                        const int32_t *regularize, float *bsdf_rec, int32_t *bsdf4) {
+    const char *fn = "wf_bsdf_make_device";
+    if (!ctx) return fail(-1, "%s: null context", fn);
+    if (!ctx->sceneLoaded) return fail(-1, "%s: no scene uploaded", fn);
+    if (n < 0) return fail(-1, "%s: n = %d", fn, n);
+    if (n == 0) return 0;
+    if (n > (1 << 30)) return fail(-1, "%s: n = %d is more than 2^30 items", fn, n);
+    if (const char *w = FirstNull({{"rays8", rays8}, {"planes_f", planes_f}, {"planes_i", planes_i}, {"lambda4", lambda4}, {"bsdf_rec", bsdf_rec}, {"bsdf4", bsdf4}}))
+        return fail(-1, "%s: null %s", fn, w);
+    if (const char *w = FirstMisaligned({{"rays8", rays8}, {"planes_f", planes_f}, {"planes_i", planes_i}, {"lambda4", lambda4}, {"bsdf_rec", bsdf_rec}, {"bsdf4", bsdf4}}, 15u))
+        return fail(-1, "%s: %s is not aligned to 16 bytes (rays, planes, records and rows are read and written 16 bytes at a time)", fn, w);
+    if (const char *w = FirstMisaligned({{"regularize", regularize}, {"n_device", n_device}}, 3u)) return fail(-1, "%s: %s is not aligned to 4 bytes", fn, w);
+    useDevice(ctx);
+    if ((size_t)n > ctx->bsdfRouteCap) {
+        // (the outgrown array is not freed here: launches of earlier calls may still read it; it goes with the context)
+        const size_t cap = std::max((size_t)n, 2 * ctx->bsdfRouteCap);
+        int32_t *route = nullptr;
+        if (int e = devAlloc(ctx, &route, cap)) return e;
+        ctx->bsdfRoute = route; ctx->bsdfRouteCap = cap;
+    }
+    bbsdf::MakeArgs a;
+    a.n = n; a.nMaterials = ctx->plan.nMaterials; a.cameraAnim = ctx->plan.cameraAnim; a.nDevice = n_device; a.rays8 = rays8; a.planesF = planes_f;
+    a.lambda4 = lambda4; a.planesI = planes_i; a.regularize = regularize; a.route = ctx->bsdfRoute; a.rec = bsdf_rec; a.bsdf4 = bsdf4;
+    Prof prof_(ctx, "Make BSDFs (device items)");
+    for (int t = 0; t < WF_MAT_NTYPES; ++t) {
+        if (t != 0 && !ctx->plan.matPresent[t]) continue;
+        if (const int e = kBsdfMake[t](ctx->stream, ctx->svDev, &a)) return fail(e, "%s: the launch for material type %d failed: %s", fn, t, hipGetErrorString((hipError_t)e));
+    }
+    return 0;
+}
+int wf_bsdf_eval_device(wf_ctx *ctx, int n, const int32_t *n_device, const float *bsdf_rec, const float *planes_f, const int32_t *planes_i, const float *wi4,
+                        const float *u4, float *f4, float *pdf4, float *next_rays8, float *sample_f4, float *sample_pdf4, int32_t *sample_i4) {
+    const char *fn = "wf_bsdf_eval_device";
+    if (!ctx) return fail(-1, "%s: null context", fn);
+    if (!ctx->sceneLoaded) return fail(-1, "%s: no scene uploaded", fn);
+    if (n < 0) return fail(-1, "%s: n = %d", fn, n);
+    if (!wi4 && !u4) return fail(-1, "%s: neither wi4 nor u4 is given", fn);
+    if (n == 0) return 0;
+    if (n > (1 << 30)) return fail(-1, "%s: n = %d is more than 2^30 items", fn, n);
+    if (const char *w = FirstNull({{"bsdf_rec", bsdf_rec}, {"planes_f", planes_f}, {"planes_i", planes_i}})) return fail(-1, "%s: null %s", fn, w);
+    if (wi4) if (const char *w = FirstNull({{"f4", f4}, {"pdf4", pdf4}})) return fail(-1, "%s: wi4 is given and %s is null", fn, w);
+    if (u4)
+        if (const char *w = FirstNull({{"next_rays8", next_rays8}, {"sample_f4", sample_f4}, {"sample_pdf4", sample_pdf4}, {"sample_i4", sample_i4}}))
+            return fail(-1, "%s: u4 is given and %s is null", fn, w);
+    // (the outputs of an absent half are not written: they are not looked at either)
+    if (!wi4) f4 = pdf4 = nullptr;
+    if (!u4) { next_rays8 = sample_f4 = sample_pdf4 = nullptr; sample_i4 = nullptr; }
+    if (const char *w = FirstMisaligned({{"bsdf_rec", bsdf_rec}, {"planes_f", planes_f}, {"planes_i", planes_i}, {"wi4", wi4}, {"u4", u4}, {"f4", f4}, {"pdf4", pdf4},
+                                         {"next_rays8", next_rays8}, {"sample_f4", sample_f4}, {"sample_pdf4", sample_pdf4}, {"sample_i4", sample_i4}}, 15u))
+        return fail(-1, "%s: %s is not aligned to 16 bytes (records, planes and rows are read and written 16 bytes at a time)", fn, w);
+    if ((uintptr_t)n_device & 3u) return fail(-1, "%s: n_device is not aligned to 4 bytes", fn);
+    useDevice(ctx);
+    bbsdf::EvalArgs a;
+    a.n = n; a.nMaterials = ctx->plan.nMaterials; a.nDevice = n_device; a.rec = bsdf_rec; a.planesF = planes_f; a.planesI = planes_i; a.wi4 = wi4; a.u4 = u4;
+    a.f4 = f4; a.pdf4 = pdf4; a.nextRays8 = next_rays8; a.sampleF4 = sample_f4; a.samplePdf4 = sample_pdf4; a.sampleI4 = sample_i4;
+    Prof prof_(ctx, "Evaluate BSDFs (device items)");
+    for (int t = 0; t < WF_MAT_NTYPES; ++t) {
+        if (t != 0 && !ctx->plan.matPresent[t]) continue;
+        if (const int e = kBsdfEval[t](ctx->stream, ctx->svDev, &a)) return fail(e, "%s: the launch for material type %d failed: %s", fn, t, hipGetErrorString((hipError_t)e));
+    }
     return 0;
 }
 // room for n items in ctx->trScratch, the wavefront's arrays among them if the scene's plan routes through it.  Growth waits for the

@@ -197,6 +197,8 @@ struct wf_ctx {
     unsigned long long *developNaN = nullptr;   // wf_film_develop_*_device's NaN counter (allocated by the first call that asks for the count)
     int32_t *filmStamps = nullptr;   // wf_film_add_samples_device: per film pixel, the epoch of the last call that added to it (allocated by the scene's first call)
     int32_t filmEpoch = 0;           // ... the last call's epoch, 1 .. INT32_MAX (then the stamps are zeroed and the epochs start over)
+    int32_t *bsdfRoute = nullptr;    // wf_bsdf_make_device: per row, the material the routing pass resolved (-1: no BSDF), read by the types' launches of the same call
+    size_t bsdfRouteCap = 0;         // ... its rows (grown by doubling; an outgrown array stays in `allocs`: launches in flight may still read it)
     int W = 0, H = 0;
     int maxDepth = 5;
     float sceneBounds[6] = {};

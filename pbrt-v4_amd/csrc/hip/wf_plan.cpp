@@ -213,6 +213,7 @@ static void ClassifyScene(const wf_scene_desc *d, const Switches &sw, ScenePlan 
     plan->emittedVariant = EmittedVariant(plan->portalLights, emitterAlpha, plan->rareLights);
     plan->nLights = d->n_lights;
     plan->nInfiniteLights = d->n_infinite_lights;
+    plan->nMaterials = d->n_materials;
     for (int i = 0; i < d->n_quadrics; ++i) {
         if (d->meshes[d->quadrics[i].mesh].alpha_tex >= 0) plan->haveQuadricAlpha = true;
         if (d->quadrics[i].type == WF_QUADRIC_CURVE) plan->haveCurves = true;
@@ -345,6 +346,8 @@ bool wf::planning::PlanValue(const ScenePlan &plan, const char *key, int64_t *va
     else if (k == "light_emitted_variant") *value = plan.emittedVariant;  // k_light_emitted<PORTAL, ALPHA, AREA_RARE> (EmittedVariant, wf_plan.h)
     else if (k == "lights") *value = plan.nLights;
     else if (k == "infinite_lights") *value = plan.nInfiniteLights;
+    else if (k == "bsdf_planes") *value = WF_BSDF_PLANES;          // the planes of a wf_bsdf_make_device record
+    else if (k == "material_types") *value = plan.matTypeMask;     // bit t: the scene holds a material of type t — the k_bsdf_make / k_bsdf_eval launches of a call (wf_boundary_bsdf.hip)
     else if (k == "tr_route") *value = plan.trRoute;  // -1 no media, 0 k_shadow_tr, 1 k_shadow_tr_fast, 2 the transmittance wavefront
     else if (k == "camera_anim") *value = plan.cameraAnim;   // k_gen_camera_rays<ANIM>
     else if (k == "route_variant") *value = plan.routeVariant;   // 0 k_route_hits<false>, 1 <true>, 2 <true, true>

@@ -150,6 +150,7 @@ struct ScenePlan {
     // is not a triangle).  WF_RARE_LIGHTS=1 forces the general ones.
     int emittedVariant = 0;
     int nLights = 0, nInfiniteLights = 0;   // the sizes of the light table and of the list of infinite lights ("lights", "infinite_lights")
+    int nMaterials = 0;                     // the size of the material table: what wf_bsdf_make_device / wf_bsdf_eval_device check a row's material id against
 };
 constexpr int EMITTED_PORTAL = 1, EMITTED_ALPHA = 2, EMITTED_AREA_RARE = 4;
 constexpr int EmittedVariant(bool portal, bool alpha, bool areaRare) {

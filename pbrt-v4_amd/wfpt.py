@@ -77,7 +77,11 @@ ABI_SYMBOLS = [
     "wf_film_spectral_upload", "wf_film_gbuffer_upload", "wf_film_channel_count", "wf_film_develop_device", "wf_film_develop_rgb_device",
     "wf_hit_interaction_device", "wf_camera_rays_device",
     "wf_camera_samples_device", "wf_film_add_samples_device", "wf_light_sample_device", "wf_light_emitted_device",
+    "wf_bsdf_make_device", "wf_bsdf_eval_device",
 ]
+# the planes of a wf_bsdf_make_device record (include/wf_abi.h: WF_BSDF_PLANES), and the bit of bsdf4 word 0 beside the BxDFFlags
+BSDF_PLANES = 10
+BSDF_TERMINATED = 1 << 8
 # the planes of wf_hit_interaction_device (include/wf_abi.h): WF_INTR_FPLANES float planes, WF_INTR_IPLANES int planes, 4 words per item each
 INTR_FPLANES = 11
 INTR_IPLANES = 2
@@ -660,6 +664,100 @@ class Scene:
         self._device_call("wf_light_emitted_device", hip.wf_light_emitted_device, [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 3, ts, n,
                           n_device.data_ptr() if n_device is not None else None, rays8.data_ptr(), F.data_ptr(), I.data_ptr(), lambda4.data_ptr(), int(infinite_index),
                           P.data_ptr() if P is not None else None, Le.data_ptr(), pp.data_ptr())
+        return r
+
+    def bsdf_device(self, rays8, it, lambda4, regularize=None, n_device=None):
+        """wf_bsdf_make_device: the scene's BSDF at n device vertices — the MixMaterial choice, the textures, the normal or bump map and
+        the material's BxDF, by the render's own functions.  rays8 float32 [n, 8]: the rays that found the hits (the mix choice hashes
+        their direction); it: the dict of interactions_device / first_hit (or its two plane tensors); lambda4 float32 [n, 4];
+        regularize int32 [n] (None: nowhere): non-zero where the caller's path has had a non-specular bounce and the scene regularises.
+        Returns a dict: "rec" float32 [10, n, 4], opaque, for bsdf_eval_device; "bsdf4" int32 [n, 4] and its views "flags" (the
+        BxDFFlags: 1 reflection, 2 transmission, 4 diffuse, 8 glossy, 16 specular), "side" (what sample_lights_device takes; 0 also
+        where the BSDF is specular only and takes no light sample), "material" (after the mix resolve), "type" (0: the row has no
+        BSDF — a miss, an interface surface — and is all zeros), "terminated" (bool: the material's dispersion terminated the
+        secondary wavelengths — the caller zeroes lambda_pdf4[:, 1:] and divides lambda_pdf4[:, 0] by 4 unless they are zero already)."""
+        import torch
+        _, hip = libs()
+        self._as(rays8, torch.float32, 8, "bsdf_device rays8")
+        F, I, n = self._planes(it, "bsdf_device")
+        self._as(lambda4, torch.float32, 4, "bsdf_device lambda4")
+        if regularize is not None:
+            self._as(regularize, torch.int32, 0, "bsdf_device regularize")
+        if any(t.shape[0] != n for t in (rays8, lambda4) + ((regularize,) if regularize is not None else ())):
+            raise WfError("bsdf_device: the arrays hold different numbers of items")
+        self._count_arg(n_device, "bsdf_device")
+        rec = torch.empty((BSDF_PLANES, n, 4), dtype=torch.float32, device=F.device)
+        b4 = torch.empty((n, 4), dtype=torch.int32, device=F.device)
+        r = {"rec": rec, "bsdf4": b4, "side": b4[:, 1], "material": b4[:, 2], "type": b4[:, 3]}
+        if n > 0:
+            ts = [rays8, F, I, lambda4, rec, b4] + [t for t in (regularize, n_device) if t is not None]
+            self._device_call("wf_bsdf_make_device", hip.wf_bsdf_make_device, [C.c_void_p, C.c_int] + [C.c_void_p] * 8, ts, n,
+                              n_device.data_ptr() if n_device is not None else None, rays8.data_ptr(), F.data_ptr(), I.data_ptr(), lambda4.data_ptr(),
+                              regularize.data_ptr() if regularize is not None else None, rec.data_ptr(), b4.data_ptr())
+        r["flags"] = b4[:, 0] & 0xff
+        r["terminated"] = (b4[:, 0] & BSDF_TERMINATED) != 0
+        r["ns"] = rec[1, :, :3]   # the final shading normal (after the normal / bump map): what light_planes() hands the lights
+        return r
+
+    def light_planes(self, it, bsdf):
+        """The float planes of `it` with the BSDF's final shading normal in plane 3, where the row has a BSDF: the LightSampleContext
+        the render samples its lights from (and keeps with the indirect ray for the MIS weights) carries the shading normal AFTER the
+        normal or bump map, which only bsdf_device knows.  Pass (light_planes(it, bsdf), it["planes_i"]) to sample_lights_device and
+        as `prev` to emitted_device; on a scene without normal and bump maps the planes are equal to it["planes_f"]."""
+        import torch
+        F, _, n = self._planes(it, "light_planes")
+        out = F.clone()
+        live = (bsdf["type"] != 0)[:, None]
+        out[3, :, :3] = torch.where(live, bsdf["rec"][1, :, :3], F[3, :, :3])
+        return out
+
+    def bsdf_eval_device(self, bsdf, it, wi=None, u4=None, n_device=None):
+        """wf_bsdf_eval_device: the BSDFs of bsdf_device (its dict, or the "rec" tensor) evaluated for given directions and / or
+        sampled.  it: the interactions the BSDFs were made from.  wi float32 [n, 4] rows {wi, unused}: "f" float32 [n, 4] = bsdf.f(wo,
+        wi), "pdf" float32 [n] = bsdf.PDF(wo, wi), "cos" float32 [n] = |wi . ns|.  u4 float32 [n, 4] rows {uc, u[0], u[1], unused}:
+        bsdf.Sample_f — "sample_f" float32 [n, 4], "sample_pdf" float32 [n], "pdf_mis" float32 [n] (what the render divides r_u by:
+        the BSDF's PDF where the sample's own is only proportional), "sample_cos" float32 [n], "eta" float32 [n], "sample_valid" /
+        "sample_flags" / "next_medium" / "proportional" int32 [n], "next_rays8" float32 [n, 8] (ready for trace_device).  With these
+        beta = sample_f * sample_cos / sample_pdf, r_l = r_u / pdf_mis and etaScale * eta ** 2 are the render's values.  An invalid
+        sample and a row without a BSDF are zeros.  The tensors themselves: "f4", "pdf4", "sample_f4", "sample_pdf4", "sample_i4"."""
+        import torch
+        _, hip = libs()
+        rec = bsdf["rec"] if isinstance(bsdf, dict) else bsdf
+        F, I, n = self._planes(it, "bsdf_eval_device")
+        if not (isinstance(rec, torch.Tensor) and rec.dtype == torch.float32 and rec.shape == (BSDF_PLANES, n, 4)):
+            raise WfError("bsdf_eval_device: bsdf is the dict of bsdf_device or its float32 [%d, n, 4] record tensor, of the interactions' n" % BSDF_PLANES)
+        if wi is None and u4 is None:
+            raise WfError("bsdf_eval_device: give wi, u4 or both")
+        for t, what in ((wi, "wi"), (u4, "u4")):
+            if t is not None:
+                self._as(t, torch.float32, 4, "bsdf_eval_device " + what)
+                if t.shape[0] != n:
+                    raise WfError("bsdf_eval_device: the arrays hold different numbers of items")
+        self._count_arg(n_device, "bsdf_eval_device")
+        dev = F.device
+        r = {}
+        ts = [rec, F, I]
+        f4 = pdf4 = nxt = sf = sp = si = None
+        if wi is not None:
+            f4 = torch.empty((n, 4), dtype=torch.float32, device=dev)
+            pdf4 = torch.empty((n, 4), dtype=torch.float32, device=dev)
+            r.update(f4=f4, pdf4=pdf4, f=f4, pdf=pdf4[:, 0], cos=pdf4[:, 1])
+            ts += [wi, f4, pdf4]
+        if u4 is not None:
+            nxt = torch.empty((n, 8), dtype=torch.float32, device=dev)
+            sf = torch.empty((n, 4), dtype=torch.float32, device=dev)
+            sp = torch.empty((n, 4), dtype=torch.float32, device=dev)
+            si = torch.empty((n, 4), dtype=torch.int32, device=dev)
+            r.update(next_rays8=nxt, sample_f4=sf, sample_pdf4=sp, sample_i4=si, sample_f=sf, sample_pdf=sp[:, 0], pdf_mis=sp[:, 1], sample_cos=sp[:, 2],
+                     eta=sp[:, 3], sample_valid=si[:, 0], sample_flags=si[:, 1], next_medium=si[:, 2], proportional=si[:, 3])
+            ts += [u4, nxt, sf, sp, si]
+        if n == 0:
+            return r
+        if n_device is not None:
+            ts.append(n_device)
+        p = lambda t: t.data_ptr() if t is not None else None
+        self._device_call("wf_bsdf_eval_device", hip.wf_bsdf_eval_device, [C.c_void_p, C.c_int] + [C.c_void_p] * 12, ts, n, p(n_device), rec.data_ptr(), F.data_ptr(),
+                          I.data_ptr(), p(wi), p(u4), p(f4), p(pdf4), p(nxt), p(sf), p(sp), p(si))
         return r
 
     def bounds(self):
