@@ -19,7 +19,7 @@
 static std::atomic<unsigned long long> g_pdfTriTests{0};
 #define WF_COUNT_TRI_TESTS (++g_pdfTriTests)
 #include "../../pbrt-v4_amd/csrc/common/wf_kernels.h"
-#include "../../pbrt-v4_amd/csrc/host/scene.h"
+#include "../../tools/check_common.h"
 
 #include <atomic>
 #include <chrono>
@@ -58,53 +58,6 @@ static void AllocRayQueue(RayQueueV *q, int n) {
     q->o = Alloc<F4>(n); q->d = Alloc<F4>(n); q->beta = Alloc<F4>(n); q->r_u = Alloc<F4>(n); q->r_l = Alloc<F4>(n);
     q->ctx0 = Alloc<F4>(n); q->ctx1 = Alloc<F4>(n); q->ctx2 = Alloc<F4>(n); q->meta = Alloc<I4>(n);
 }
-
-SceneView MakeHostView(const wf_scene_desc &d, const uint32_t *sobol) {
-    SceneView sv{};
-    sv.P = d.P; sv.N = d.N; sv.UV = d.UV; sv.S = d.S; sv.triIndices = d.tri_indices; sv.triMesh = d.tri_mesh; sv.meshes = d.meshes;
-    sv.bvhNodes = d.bvh_nodes; sv.bvhPrims = d.bvh_prims; sv.nTriangles = d.n_triangles; sv.nBvhNodes = d.n_bvh_nodes;
-    sv.spectra = d.spectra; sv.spectrumData = d.spectrum_data; sv.textures = d.textures; sv.materials = d.materials;
-    sv.lights = d.lights; sv.infiniteLights = d.infinite_lights; sv.lightBvh = d.light_bvh_nodes; sv.lightXforms = d.light_transforms;
-    sv.nLights = d.n_lights; sv.nInfiniteLights = d.n_infinite_lights; sv.nLightBvhNodes = d.n_light_bvh_nodes; sv.lightSampler = d.light_sampler;
-    for (int i = 0; i < 6; ++i) sv.allLightBounds[i] = d.all_light_bounds[i];
-    sv.camera = d.camera; sv.film = d.film; sv.filter = d.filter; sv.filterData = d.filter_data; sv.sampler = d.sampler;
-    sv.sobol = sobol;
-    sv.powerAlias = d.power_alias;
-    sv.texImages = d.tex_images;
-    sv.imageLights = d.image_lights; sv.tableData = d.table_data; sv.rgb2specCoeffs = d.rgb2spec_coeffs;
-    sv.rgb2specZNodes = d.rgb2spec_znodes;
-    sv.noisePerm = d.noise_perm;
-    sv.csIlluminantOffset = d.cs_illuminant_offset;
-    sv.media = d.media; sv.mediumData = d.medium_data;
-    sv.maxDepth = d.max_depth; sv.regularize = d.regularize; sv.haveMedia = d.have_media; sv.options = d.options;
-    sv.texNeedsFootprint = 0;
-    sv.haveAlpha = 0;
-    for (int i = 0; i < d.n_meshes; ++i)
-        if (d.meshes[i].alpha_tex >= 0) sv.haveAlpha = 1;
-    for (int i = 0; i < d.n_textures; ++i)
-        if (d.textures[i].type >= WF_TEX_FLOAT_IMAGE) sv.texNeedsFootprint = 1;
-    for (int i = 0; i < d.n_materials; ++i)
-        if (d.materials[i].displacement >= 0 || d.materials[i].normalmap >= 0) sv.texNeedsFootprint = 1;
-    sv.matTypeMask = 0;
-    sv.quadrics = d.quadrics; sv.nQuadrics = d.n_quadrics;
-    sv.instances = d.instances; sv.instanceDefs = d.instance_defs; sv.nInstances = d.n_instances;
-    sv.animated = d.animated; sv.haveAnimated = d.n_animated > 0;
-    sv.sobolMatrices = d.sobol_matrices; sv.vdcSobol = d.vdc_sobol; sv.vdcSobolInv = d.vdc_sobol_inv;
-    sv.haltonPrimes = d.halton_primes; sv.haltonPermOffsets = d.halton_perm_offsets; sv.haltonPerms = d.halton_perms;
-    sv.haveMix = 0;
-    sv.haveSubsurface = 0;
-    sv.haveQuadricAlpha = 0;
-    for (int i = 0; i < d.n_quadrics; ++i) if (d.meshes[d.quadrics[i].mesh].alpha_tex >= 0) sv.haveQuadricAlpha = 1;
-    sv.haveCurves = 0;
-    for (int i = 0; i < d.n_quadrics; ++i) if (d.quadrics[i].type == WF_QUADRIC_CURVE) sv.haveCurves = 1;
-    for (int i = 0; i < d.n_materials; ++i) {
-        if (d.materials[i].type == WF_MAT_MIX) sv.haveMix = 1;
-        if (d.materials[i].type == WF_MAT_SUBSURFACE) sv.haveSubsurface = 1;
-        else sv.matTypeMask |= 1 << d.materials[i].type;
-    }
-    return sv;
-}
-
 
 // ---- design study (not a checker): lane utilisation of wave-synchronous traversal schemes ---------------------
 // Walks each ray of a queue the way the production kernel does (pair nodes: both children tested at the parent,
@@ -267,14 +220,7 @@ static void SimulateWave(const std::vector<std::vector<uint8_t>> &ev, int lanes,
 }
 
 static int Main(int argc, char **argv);
-int main(int argc, char **argv) {
-    try {
-        return Main(argc, argv);
-    } catch (const std::exception &e) {
-        fprintf(stderr, "%s\n", e.what());
-        return 1;
-    }
-}
+int main(int argc, char **argv) { return check::Guarded("", [&] { return Main(argc, argv); }); }
 static int Main(int argc, char **argv) {
     RenderOptions opt;
     std::string scenePath, dumpFilm, dataDir, traceRays, traceHits, probeIn, probeOut, dumpStages;
@@ -322,23 +268,11 @@ static int Main(int argc, char **argv) {
         else scenePath = a;
     }
     if (scenePath.empty()) { fprintf(stderr, "usage: wf_cpu [options] scene.pbrt\n"); return 1; }
-    if (dataDir.empty()) {
-        // <repo>/pbrt-v4_amd/data relative to this binary's usual location oracle/_build/wf_cpu
-        std::string self = argv[0];
-        size_t p = self.rfind('/');
-        dataDir = (p == std::string::npos ? std::string(".") : self.substr(0, p)) + "/../../pbrt-v4_amd/data";
-    }
-    SpectralData::Init(dataDir, dataDir + "/cache");
-    ParsedScene parsed;
-    ParseFiles({scenePath}, &opt, &parsed);
-    SceneTables T;
-    BuildSceneTables(parsed, opt, &T);
-    static uint32_t sobol[WF_SOBOL_WORDS];
-    FillSobol2D(sobol);
-    SceneView sv = MakeHostView(T.desc, sobol);
-    sv.self = &sv;
-    static int32_t fatalWord = 0;
-    sv.fatal = &fatalWord;   // RaiseFatal (wf_scene.h): checked at the end of the render
+    check::InitData(dataDir, argv[0], "/../../pbrt-v4_amd/data");   // (the binary's usual location: oracle/_build/wf_cpu)
+    check::HostScene scene(scenePath, &opt);
+    const SceneTables &T = scene.T;
+    const SceneView &sv = scene.sv;
+    const int32_t &fatalWord = scene.fatalWord;   // RaiseFatal (wf_scene.h): checked at the end of the render
 
     // sampler probe: in = n x {px, py, sampleIndex} int32 -> out = n x ndims floats (Get1D from startDim)
     if (!probeIn.empty()) {

@@ -1702,17 +1702,15 @@ int wf_sync(wf_ctx *ctx) {
 void *wf_stream(wf_ctx *ctx) { return ctx ? (void *)ctx->stream : nullptr; }
 
 // The first step of the upload after PlanScene: the description's tables, the ones derived from them, and the scalars of SceneView.
-static int UploadTables(wf_ctx *ctx, const wf_scene_desc *d, const Switches &sw) {
-    SceneView &sv = ctx->svHost;
-    const ScenePlan &plan = ctx->plan;
-    int e = 0;
-    if ((e = devUpload(ctx, &sv.P, d->P, (size_t)3 * d->n_vertices))) return e;
-    if ((e = devUpload(ctx, &sv.N, d->N, (size_t)3 * d->n_vertices))) return e;
-    if ((e = devUpload(ctx, &sv.UV, d->UV, (size_t)2 * d->n_vertices))) return e;
-    if (d->n_tangents > 0 && (e = devUpload(ctx, &sv.S, d->S, (size_t)3 * d->n_tangents))) return e;
-    if ((e = devUpload(ctx, &sv.triIndices, d->tri_indices, (size_t)3 * d->n_triangles))) return e;
-    if ((e = devUpload(ctx, &sv.triMesh, d->tri_mesh, (size_t)d->n_triangles + d->n_quadrics))) return e;
+// The tables that are copies of the description's arrays are the list WF_SCENE_TABLES (csrc/common/wf_scene_view.h), uploaded in its
+// order; the tables with a condition or a derivation of their own are the Upload_<member> steps here, run where the list marks them.
+static int Upload_S(wf_ctx *ctx, const wf_scene_desc *d, const Switches &) {
+    // (null in a scene without shading tangents)
+    return d->n_tangents > 0 ? devUpload(ctx, &ctx->svHost.S, d->S, (size_t)3 * d->n_tangents) : 0;
+}
+static int Upload_shadeTris(wf_ctx *ctx, const wf_scene_desc *d, const Switches &sw) {
     // the de-indexed per-triangle vertex records of the material stage (wf_scene.h ShadeTri); WF_SHADE_TRIS=0: the indexed tables only
+    SceneView &sv = ctx->svHost;
     sv.shadeTris = nullptr;
     if (d->n_triangles > 0 && sw.shadeTris) {
         std::vector<ShadeTri> st((size_t)d->n_triangles);
@@ -1728,112 +1726,71 @@ static int UploadTables(wf_ctx *ctx, const wf_scene_desc *d, const Switches &sw)
             st[t] = r;
         }
         const ShadeTri *dst = nullptr;
-        if ((e = devUpload(ctx, &dst, st.data(), st.size()))) return e;
+        if (int e = devUpload(ctx, &dst, st.data(), st.size())) return e;
         HIPCHK(hipStreamSynchronize(ctx->stream));   // (the staging vector dies here)
         sv.shadeTris = dst;
     }
-    if ((e = devUpload(ctx, &sv.quadrics, d->quadrics, (size_t)d->n_quadrics))) return e;
-    if ((e = devUpload(ctx, &sv.sobolMatrices, d->sobol_matrices, d->sobol_matrices ? (size_t)1024 * 52 : (size_t)0)) ||
-        (e = devUpload(ctx, &sv.vdcSobol, d->vdc_sobol, d->vdc_sobol ? (size_t)25 * 52 : (size_t)0)) ||
-        (e = devUpload(ctx, &sv.vdcSobolInv, d->vdc_sobol_inv, d->vdc_sobol_inv ? (size_t)26 * 52 : (size_t)0)))
-        return e;
-    if ((e = devUpload(ctx, &sv.haltonPrimes, d->halton_primes, d->halton_primes ? (size_t)1000 : (size_t)0))) return e;
-    if ((e = devUpload(ctx, &sv.haltonPermOffsets, d->halton_perm_offsets, d->halton_perm_offsets ? (size_t)1000 : (size_t)0))) return e;
-    if ((e = devUpload(ctx, &sv.haltonPerms, d->halton_perms, (size_t)d->n_halton_perms))) return e;
-    sv.nQuadrics = d->n_quadrics;
-    if ((e = devUpload(ctx, &sv.meshes, d->meshes, (size_t)d->n_meshes))) return e;
-    if ((e = devUpload(ctx, &sv.bvhNodes, d->bvh_nodes, (size_t)d->n_bvh_nodes))) return e;
-    if ((e = devUpload(ctx, &sv.bvhPrims, d->bvh_prims, (size_t)plan.nBvhPrims))) return e;
-    if ((e = devUpload(ctx, &sv.instances, d->instances, (size_t)d->n_instances))) return e;
-    if ((e = devUpload(ctx, &sv.instanceDefs, d->instance_defs, (size_t)d->n_instance_defs))) return e;
-    sv.nInstances = plan.nInstances;
-    if ((e = devUpload(ctx, &sv.animated, d->animated, (size_t)d->n_animated))) return e;
-    sv.haveAnimated = plan.haveAnimated;
-    sv.nTriangles = d->n_triangles;
-    sv.nBvhNodes = d->n_bvh_nodes;
-    if ((e = devUpload(ctx, &sv.spectra, d->spectra, (size_t)d->n_spectra))) return e;
-    if ((e = devUpload(ctx, &sv.spectrumData, d->spectrum_data, (size_t)d->n_spectrum_floats))) return e;
-    if ((e = devUpload(ctx, &sv.textures, d->textures, (size_t)d->n_textures))) return e;
-    if ((e = devUpload(ctx, &sv.materials, d->materials, (size_t)d->n_materials))) return e;
-    if ((e = devUpload(ctx, &sv.lights, d->lights, (size_t)d->n_lights))) return e;
-    if ((e = devUpload(ctx, &sv.infiniteLights, d->infinite_lights, (size_t)d->n_infinite_lights))) return e;
-    if ((e = devUpload(ctx, &sv.lightBvh, d->light_bvh_nodes, (size_t)d->n_light_bvh_nodes))) return e;
-    {
-        // the light BVH's nodes with their per-node constants expanded (wf_lights.h ExpandLightNode: the reference's own expressions, evaluated
-        // once here instead of at every visit of every descent)
-        std::vector<wf::LightNodeX> xs((size_t)d->n_light_bvh_nodes);
-        for (int i = 0; i < d->n_light_bvh_nodes; ++i) xs[i] = wf::ExpandLightNode(d->all_light_bounds, d->light_bvh_nodes[i]);
-        if ((e = devUpload(ctx, &sv.lightBvhX, xs.data(), xs.size()))) return e;
-    }
-    if ((e = devUpload(ctx, &sv.lightXforms, d->light_transforms, (size_t)d->n_light_transforms))) return e;
-    if ((e = devUpload(ctx, &sv.powerAlias, d->power_alias, d->light_sampler == WF_LS_POWER ? (size_t)3 * d->n_lights : (size_t)0))) return e;
-    if ((e = devUpload(ctx, &sv.imageLights, d->image_lights, (size_t)d->n_image_lights))) return e;
-    if ((e = devUpload(ctx, &sv.texImages, d->tex_images, (size_t)d->n_tex_images))) return e;
-    if ((e = devUpload(ctx, &sv.tableData, d->table_data, (size_t)d->n_table_floats))) return e;
-    if ((e = devUpload(ctx, &sv.rgb2specCoeffs, d->rgb2spec_coeffs, d->rgb2spec_coeffs ? (size_t)3 * 64 * 64 * 64 * 3 : (size_t)0))) return e;
-    if ((e = devUpload(ctx, &sv.rgb2specZNodes, d->rgb2spec_znodes, (size_t)64))) return e;
-    if ((e = devUpload(ctx, &sv.noisePerm, d->noise_perm, d->noise_perm ? (size_t)512 : (size_t)0))) return e;
-    sv.csIlluminantOffset = d->cs_illuminant_offset;
-    if ((e = devUpload(ctx, &sv.media, d->media, (size_t)d->n_media))) return e;
-    if ((e = devUpload(ctx, &sv.mediumData, d->medium_data, (size_t)d->n_medium_floats))) return e;
-    {
-        // the corner-packed copies of the GridMedium density grids (SceneView::gridCorners), built on the device from the dense grids
-        // just uploaded.  WF_GRID_CORNERS=0: none (A/B); tables beyond WF_GRID_CORNERS_GB (default 32) gigabytes in all are left out
-        sv.gridCorners = nullptr;
-        sv.gridCornerBase = nullptr;
-        if (d->n_media > 0 && sw.gridCorners) {
-            const double budget = sw.gridCornersGB * 1024.0 * 1024.0 * 1024.0;
-            std::vector<long long> base(d->n_media, -1);
-            size_t total = 0;
+    return 0;
+}
+static int Upload_lightBvhX(wf_ctx *ctx, const wf_scene_desc *d, const Switches &) {
+    // the light BVH's nodes with their per-node constants expanded (wf_lights.h ExpandLightNode: the reference's own expressions, evaluated
+    // once here instead of at every visit of every descent)
+    std::vector<wf::LightNodeX> xs((size_t)d->n_light_bvh_nodes);
+    for (int i = 0; i < d->n_light_bvh_nodes; ++i) xs[i] = wf::ExpandLightNode(d->all_light_bounds, d->light_bvh_nodes[i]);
+    return devUpload(ctx, &ctx->svHost.lightBvhX, xs.data(), xs.size());
+}
+static int Upload_gridCorners(wf_ctx *ctx, const wf_scene_desc *d, const Switches &sw) {
+    // the corner-packed copies of the GridMedium density grids (SceneView::gridCorners), built on the device from the dense grids
+    // just uploaded.  WF_GRID_CORNERS=0: none (A/B); tables beyond WF_GRID_CORNERS_GB (default 32) gigabytes in all are left out
+    SceneView &sv = ctx->svHost;
+    int e = 0;
+    sv.gridCorners = nullptr;
+    sv.gridCornerBase = nullptr;
+    if (d->n_media > 0 && sw.gridCorners) {
+        const double budget = sw.gridCornersGB * 1024.0 * 1024.0 * 1024.0;
+        std::vector<long long> base(d->n_media, -1);
+        size_t total = 0;
+        for (int m = 0; m < d->n_media; ++m) {
+            const wf_medium &M = d->media[m];
+            if (M.type != WF_MEDIUM_GRID || M.density_offset < 0 || M.nx < 1 || M.ny < 1 || M.nz < 1) continue;
+            const size_t cells = wf::GridCornerCells(M.nx, M.ny, M.nz);
+            if ((double)(total + 8 * cells) * sizeof(float) > budget) continue;
+            base[m] = (long long)total;
+            total += 8 * cells;
+        }
+        if (total > 0) {
+            float *corners = nullptr;
+            const long long *dbase = nullptr;
+            if ((e = devAlloc(ctx, &corners, total))) return e;
+            if ((e = devUpload(ctx, &dbase, base.data(), (size_t)d->n_media))) return e;
             for (int m = 0; m < d->n_media; ++m) {
+                if (base[m] < 0) continue;
                 const wf_medium &M = d->media[m];
-                if (M.type != WF_MEDIUM_GRID || M.density_offset < 0 || M.nx < 1 || M.ny < 1 || M.nz < 1) continue;
-                const size_t cells = wf::GridCornerCells(M.nx, M.ny, M.nz);
-                if ((double)(total + 8 * cells) * sizeof(float) > budget) continue;
-                base[m] = (long long)total;
-                total += 8 * cells;
+                const size_t cells = (size_t)(M.nx + 1) * (M.ny + 1) * (M.nz + 1);
+                const int grid = (int)std::min<size_t>((cells + BLOCK - 1) / BLOCK, (size_t)MAX_GRID * 16);
+                LAUNCH("Pack grid corners", k_pack_grid_corners, grid, sv.mediumData + M.density_offset, M.nx, M.ny, M.nz, corners + base[m]);
             }
-            if (total > 0) {
-                float *corners = nullptr;
-                const long long *dbase = nullptr;
-                if ((e = devAlloc(ctx, &corners, total))) return e;
-                if ((e = devUpload(ctx, &dbase, base.data(), (size_t)d->n_media))) return e;
-                for (int m = 0; m < d->n_media; ++m) {
-                    if (base[m] < 0) continue;
-                    const wf_medium &M = d->media[m];
-                    const size_t cells = (size_t)(M.nx + 1) * (M.ny + 1) * (M.nz + 1);
-                    const int grid = (int)std::min<size_t>((cells + BLOCK - 1) / BLOCK, (size_t)MAX_GRID * 16);
-                    LAUNCH("Pack grid corners", k_pack_grid_corners, grid, sv.mediumData + M.density_offset, M.nx, M.ny, M.nz, corners + base[m]);
-                }
-                sv.gridCorners = corners;
-                sv.gridCornerBase = dbase;
-            }
+            sv.gridCorners = corners;
+            sv.gridCornerBase = dbase;
         }
     }
-    sv.nLights = d->n_lights;
-    sv.nInfiniteLights = d->n_infinite_lights;
-    sv.nLightBvhNodes = d->n_light_bvh_nodes;
-    sv.lightSampler = d->light_sampler;
-    for (int i = 0; i < 6; ++i) sv.allLightBounds[i] = d->all_light_bounds[i];
-    sv.camera = d->camera;
-    sv.film = d->film;
-    sv.filter = d->filter;
-    if ((e = devUpload(ctx, &sv.filterData, d->filter_data, (size_t)d->n_filter_floats))) return e;
-    sv.sampler = d->sampler;
+    return 0;
+}
+static int Upload_sobol(wf_ctx *ctx, const wf_scene_desc *, const Switches &) {
     // (filled once per process: uploads of several contexts run on several threads)
     static const std::vector<uint32_t> sobol = [] { std::vector<uint32_t> t(WF_SOBOL_WORDS); FillSobol2D(t.data()); return t; }();
-    if ((e = devUpload(ctx, &sv.sobol, sobol.data(), sobol.size()))) return e;
-    sv.texNeedsFootprint = plan.texNeedsFootprint;
-    sv.haveAlpha = plan.haveAlpha;
-    sv.maxDepth = d->max_depth;
-    sv.regularize = d->regularize;
-    sv.haveMedia = d->have_media;
-    sv.options = d->options;
-    sv.matTypeMask = plan.matTypeMask;
-    sv.haveMix = plan.haveMix;
-    sv.haveSubsurface = plan.haveSubsurface;
-    sv.haveQuadricAlpha = plan.haveQuadricAlpha;
-    sv.haveCurves = plan.haveCurves;
+    return devUpload(ctx, &ctx->svHost.sobol, sobol.data(), sobol.size());
+}
+static int UploadTables(wf_ctx *ctx, const wf_scene_desc *d, const Switches &sw) {
+    SceneView &sv = ctx->svHost;
+    const int64_t nBvhPrims = ctx->plan.nBvhPrims;
+    int e = 0;
+#define UPLOAD(member, table, count) if ((e = devUpload(ctx, &sv.member, d->table, count))) return e;
+#define STEP(member) if ((e = Upload_##member(ctx, d, sw))) return e;
+    WF_SCENE_TABLES(UPLOAD, STEP)
+#undef UPLOAD
+#undef STEP
+    SetSceneScalars(&sv, *d, ctx->plan);
     return 0;
 }
 // ... then the traversal stacks, the production trees and the kernels that walk them

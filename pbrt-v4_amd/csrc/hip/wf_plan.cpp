@@ -158,15 +158,8 @@ static int CheckScene(const wf_scene_desc *d, int64_t counts[4]) {
 }
 // Step 2: what the scene holds, and which variants of the stage and walk kernels that asks for.
 static void ClassifyScene(const wf_scene_desc *d, const Switches &sw, ScenePlan *plan) {
-    plan->nInstances = d->n_instances;
+    static_cast<SceneFacts &>(*plan) = SceneFactsOf(*d);
     plan->nestedAnimated = NestedPlacements(d);
-    plan->haveAnimated = d->n_animated > 0;
-    for (int i = 0; i < d->n_meshes; ++i)
-        if (d->meshes[i].alpha_tex >= 0) plan->haveAlpha = true;
-    for (int i = 0; i < d->n_textures; ++i)
-        if (d->textures[i].type >= WF_TEX_FLOAT_IMAGE) plan->texNeedsFootprint = true;
-    for (int i = 0; i < d->n_materials; ++i)
-        if (d->materials[i].displacement >= 0 || d->materials[i].normalmap >= 0) plan->texNeedsFootprint = true;
     // the lean delta-tracking kernel (k_medium_sample<true>): no procedural cloud, NanoVDB, RGB grid or emissive grid in the scene (WF_MEDIUM_LEAN=0: off)
     plan->mediumLean = d->n_media > 0 && sw.mediumLean;
     for (int m = 0; m < d->n_media; ++m)
@@ -214,17 +207,6 @@ static void ClassifyScene(const wf_scene_desc *d, const Switches &sw, ScenePlan 
     plan->nLights = d->n_lights;
     plan->nInfiniteLights = d->n_infinite_lights;
     plan->nMaterials = d->n_materials;
-    for (int i = 0; i < d->n_quadrics; ++i) {
-        if (d->meshes[d->quadrics[i].mesh].alpha_tex >= 0) plan->haveQuadricAlpha = true;
-        if (d->quadrics[i].type == WF_QUADRIC_CURVE) plan->haveCurves = true;
-    }
-    for (int i = 0; i < d->n_materials; ++i) {
-        const int t = d->materials[i].type;
-        if (t == WF_MAT_MIX) { plan->haveMix = true; continue; }
-        plan->matPresent[t] = true;
-        plan->matTypeMask |= 1 << t;
-        if (t == WF_MAT_SUBSURFACE) plan->haveSubsurface = true;
-    }
     if (d->n_quadrics > 0) plan->genMode = (plan->haveCurves || plan->haveQuadricAlpha) ? 3 : 2;
     {
         // the hit-interaction kernel of the device-buffer boundary (ScenePlan::intrVariant): allocated what the scene can make it reach

@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <vector>
 #include "../common/wf_fastbvh.h"
+#include "../common/wf_scene_view.h"
 
 // (hidden: these names are shared by the library's units, not exported from it)
 namespace wf { namespace planning __attribute__((visibility("hidden"))) {
@@ -95,14 +96,11 @@ struct Switches {
 
 // Everything decided about a scene: a pure function of the description and the switches (PlanScene), made before anything is uploaded.
 // wf_ctx::plan is the one copy; wf_scene_plan_query gives the same answers without a context.
-struct ScenePlan {
-    // what the description holds (the upload copies these into SceneView)
+struct ScenePlan : SceneFacts {
+    // what the description holds: SceneFacts (wf_scene_view.h SceneFactsOf; the upload copies these into SceneView) — nInstances, haveAlpha,
+    // texNeedsFootprint, haveMix, haveSubsurface, haveQuadricAlpha, haveCurves, haveAnimated, matTypeMask, matPresent — and
     int64_t nBvhPrims = 0;       // entries of bvh_prims the trees index (wf_scene_check_instances)
-    int nInstances = 0;
     int nestedAnimated = 0;      // records of `instances` that are nested placements (animated shapes inside instance definitions); such scenes keep the reference-order walks
-    bool haveAlpha = false, texNeedsFootprint = false, haveMix = false, haveSubsurface = false, haveQuadricAlpha = false, haveCurves = false, haveAnimated = false;
-    int matTypeMask = 0;
-    bool matPresent[WF_MAT_NTYPES] = {};
     // the stage kernels' variants
     bool mediumLean = false;     // every medium is homogeneous or a non-emissive uniform grid: k_medium_sample<true>
     bool portalLights = false;   // the scene has a portal infinite light (k_handle_escaped<RARE>)

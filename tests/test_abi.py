@@ -1,16 +1,9 @@
 """The C-ABI libraries load and export every entry point the headers declare (no GPU, no compute calls)."""
 import ctypes
 import os
-import re
 
 from conftest import ROOT
-
-
-def declared(header):
-    text = open(os.path.join(ROOT, "include", header)).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    names = re.findall(r"^\s*(?:const\s+)?[A-Za-z_][\w\s\*]*?\b(wfh?_[a-z0-9_]+)\s*\(", text, flags=re.M)
-    return sorted(set(names))
+from suite_helpers import declared
 
 
 def test_headers_declare_expected_symbols(wfpt):

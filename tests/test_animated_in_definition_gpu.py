@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT, WF_CPU, read_pfm
-from test_gpu_parity import _check_image_vs_oracle_and_reference
+from suite_helpers import _check_image_vs_oracle_and_reference
 
 pytestmark = pytest.mark.gpu
 

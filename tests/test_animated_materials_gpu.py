@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
-from test_gpu_parity import _check_image_vs_oracle_and_reference
+from suite_helpers import _check_image_vs_oracle_and_reference
 
 pytestmark = pytest.mark.gpu
 

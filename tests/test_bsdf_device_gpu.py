@@ -6,14 +6,13 @@ the C ABI (the indirect rays and the shadow queue of depth 0, the pixel radiance
 other shapes of the same input."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from boundary_helpers import (SIDE_OF, Camera, _bits, _np, assert_rows_equal, average, begin_pass, download, emission, eval_on_host, open_scene, queue_size,
+                              renderer_before_torch, same, seeded, shade, stage, tables)  # noqa: F401 (the fixture)
 from conftest import GOLDEN, ROOT
-from test_light_device_gpu import (SIDE_OF, Camera, _bits, _np, average, begin_pass, download, emission, open_scene, queue_size, same, seeded, shade, stage,
-                                   tables)
 
 pytestmark = pytest.mark.gpu
 
@@ -29,27 +28,13 @@ WI_KEYS = ("f4", "pdf4")
 U_KEYS = ("next_rays8", "sample_f4", "sample_pdf4", "sample_i4")
 
 
-@pytest.fixture(scope="module", autouse=True)
-def renderer_before_torch(wfpt):
-    """The library's HIP runtime comes up (a first renderer) before this module imports torch, which brings a runtime of its own: the
-    order every test of the device-buffer calls has (scene first, tensors second), also when this file runs alone."""
-    s = wfpt.Scene(path=os.path.join(GOLDEN, "cornell64.pbrt"), spp=4)
-    s.create_renderer(0)
-    s.close()
-
-
 def eval_host(name, rays, planes_f, planes_i, lam, reg=None, wi=None, u4=None, tmp=None, spp=4):
     """bsdf_check --eval on downloaded inputs -> the expected outputs (numpy); spp: what open_scene opened the scene with"""
     n = planes_f.shape[1]
-    a, b = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
     head = np.array([0x42534431, n, int(reg is not None), int(wi is not None), int(u4 is not None), 0, 0, 0], np.int32)
     parts = [head, rays.astype(np.float32), planes_f.astype(np.float32), planes_i.astype(np.int32), lam.astype(np.float32)]
     parts += [x for x in (None if reg is None else reg.astype(np.int32), wi, u4) if x is not None]
-    with open(a, "wb") as f:
-        for x in parts:
-            f.write(np.ascontiguousarray(x).tobytes())
-    subprocess.run([CHECK, "--spp", str(spp), "--eval", os.path.join(GOLDEN, name + ".pbrt"), a, b], check=True, capture_output=True)
-    raw = open(b, "rb").read()
+    raw = eval_on_host(CHECK, ["--spp", str(spp)], os.path.join(GOLDEN, name + ".pbrt"), parts, tmp)
     off = [0]
 
     def take(dtype, shape):
@@ -64,16 +49,6 @@ def eval_host(name, rays, planes_f, planes_i, lam, reg=None, wi=None, u4=None, t
         out.update(next_rays8=take(np.float32, (n, 8)), sample_f4=take(np.float32, (n, 4)), sample_pdf4=take(np.float32, (n, 4)), sample_i4=take(np.int32, (n, 4)))
     assert off[0] == len(raw)
     return out
-
-
-def assert_equal(got, want, keys, what):
-    for k in keys:
-        g, w = got[k] if isinstance(got[k], np.ndarray) else _np(got[k]), want[k]
-        assert g.shape == w.shape, (what, k, g.shape, w.shape)
-        axis = 1 if g.ndim == 2 else (0, 2)
-        bad = np.nonzero((_bits(g) != _bits(w)).any(axis=axis))[0]
-        first = (g[bad[0]], w[bad[0]]) if bad.size and g.ndim == 2 else (g[:, bad[0]], w[:, bad[0]]) if bad.size else None
-        assert bad.size == 0, "%s: %s differs in %d of %d rows, first row %d: %r" % (what, k, bad.size, g.shape[-2], bad[0], first)
 
 
 def make_and_eval(s, fh, dev, seed=99):
@@ -100,8 +75,8 @@ def test_both_calls_equal_the_host_composition(wfpt, name, tmp_path):
     reg, b, ls, u4, e = make_and_eval(s, fh, dev)
     want = eval_host(name, _np(fh["rays8"]), _np(fh["planes_f"]), _np(fh["planes_i"]), _np(fh["lambda4"]), reg=_np(reg), wi=_np(ls["wi_pdf4"]), u4=_np(u4),
                      tmp=str(tmp_path))
-    assert_equal(b, want, MAKE_KEYS, name + " make")
-    assert_equal(e, want, WI_KEYS + U_KEYS, name + " eval")
+    assert_rows_equal(b, want, MAKE_KEYS, name + " make")
+    assert_rows_equal(e, want, WI_KEYS + U_KEYS, name + " eval")
     b4 = want["bsdf4"]
     # the views name the same words
     assert same(_np(b["flags"]), b4[:, 0] & 0xff) and same(_np(b["side"]), b4[:, 1]) and same(_np(b["material"]), b4[:, 2]) and same(_np(b["type"]), b4[:, 3])

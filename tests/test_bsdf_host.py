@@ -13,7 +13,7 @@ import subprocess
 import pytest
 
 from conftest import GOLDEN, ROOT
-from test_abi import declared
+from suite_helpers import declared
 
 NEW_ABI = ["wf_bsdf_make_device", "wf_bsdf_eval_device"]
 SRC = os.path.join(ROOT, "pbrt-v4_amd")

@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from boundary_helpers import _dev, _launch_names, _rays8, _shadow_rays, _tr_device
 from conftest import GOLDEN, WF_CPU
 
 pytestmark = pytest.mark.gpu
@@ -31,32 +32,10 @@ def _random_rays(n, bounds_lo, bounds_hi, seed):
     return o, d.astype(np.float32), tmax
 
 
-def _shadow_rays(lo, hi, n, seed, n_media):
-    rng = np.random.RandomState(seed)
-    o = rng.uniform(lo, hi, size=(n, 3)).astype(np.float32)
-    to = rng.uniform(lo, hi, size=(n, 3)).astype(np.float32)
-    d = (to - o).astype(np.float32)
-    tmax = np.full(n, 0.9999, dtype=np.float32)
-    medium = rng.randint(-1, n_media, size=n).astype(np.int32)
-    lam = np.sort(rng.uniform(380, 780, size=(n, 4)), axis=1).astype(np.float32)
-    Ld = rng.uniform(0.1, 2, size=(n, 4)).astype(np.float32)
-    ones = np.ones((n, 4), dtype=np.float32)
-    return o, d, tmax, medium, lam, Ld, ones, ones.copy()
-
-
 def _open(wfpt, name):
     s = wfpt.Scene(path=os.path.join(GOLDEN, name + ".pbrt"), spp=4)
     s.create_renderer(0)
     return s
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
-
-
-def _rays8(o, d, tmax, time):
-    return np.concatenate([o, d, tmax[:, None], time[:, None]], axis=1).astype(np.float32)
 
 
 def _closest(wfpt, s, rays8):
@@ -74,10 +53,6 @@ def _same_hits(got, ref):
         assert (got[f].view(np.uint32) == ref[f].view(np.uint32)).all(), f
     # the records of the device calls with times carry no visit counts, on any walk
     assert (got["nodes_visited"] == 0).all() and (got["tris_tested"] == 0).all()
-
-
-def _launch_names(s):
-    return {e["name"] for e in s.profile_report() if e["launches"] > 0}
 
 
 def _untimed_device(wfpt, s, rays7, any_hit):
@@ -253,11 +228,6 @@ def test_anim_fast_switched_off_gives_the_same_records(wfpt, anim_rays, cpu_hits
 
 
 # ---- 4. transmittance -----------------------------------------------------------------------------------------------------------
-def _tr_device(s, rays, time):
-    o, d, tmax, medium, lam, Ld, r_u, r_l = rays
-    return s.trace_shadow_tr_device(_dev(_rays8(o, d, tmax, time)), _dev(medium), _dev(lam), _dev(Ld), _dev(r_u), _dev(r_l)).cpu().numpy()
-
-
 @pytest.mark.parametrize("name", ["media_box", "media_instances"])
 def test_transmittance_on_a_static_scene_is_the_untimed_host_array_call(wfpt, name):
     s = _open(wfpt, name)

@@ -14,6 +14,7 @@ import os
 import numpy as np
 import pytest
 
+from boundary_helpers import _np, open_scene, renderer_before_torch  # noqa: F401 (the fixture)
 from conftest import GOLDEN, read_pfm
 
 pytestmark = pytest.mark.gpu
@@ -25,26 +26,6 @@ REPLAY = {"cornell64": (4, True), "film_sensor_wb": (4, True), "parser_torture":
 DISPERSIVE_SPARES = ["fuzz/s6100015", "fuzz/s400039", "fuzz/s6100011"]
 MEMBERS = (("L", np.float32, 4), ("lambda", np.float32, 4), ("lambda_pdf", np.float32, 4), ("pPixel", np.int32, 2), ("filterWeight", np.float32, 0),
            ("cameraRayWeight", np.float32, 4))
-
-
-@pytest.fixture(scope="module", autouse=True)
-def renderer_before_torch(wfpt):
-    """The library's HIP runtime comes up (a first renderer) before this module imports torch, which brings a runtime of its own: the
-    order every test of the device-buffer calls has (scene first, tensors second), also when this file runs alone."""
-    s = wfpt.Scene(path=os.path.join(GOLDEN, "cornell64.pbrt"), spp=4)
-    s.create_renderer(0)
-    s.close()
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def open_scene(wfpt, name, spp, text=None):
-    s = wfpt.Scene(path=os.path.join(GOLDEN, name + ".pbrt"), spp=spp) if text is None else wfpt.Scene(text=text, spp=spp)
-    s.create_renderer(0, samples_per_pass=1)
-    assert s.query("pixels_per_pass") == s.width * s.height   # the image is one band
-    return s
 
 
 def pixel_state(wfpt, s):

@@ -10,7 +10,7 @@ import subprocess
 import pytest
 
 from conftest import ROOT
-from test_abi import declared
+from suite_helpers import declared
 
 NEW_ABI = ["wf_camera_samples_device", "wf_film_add_samples_device"]
 SRC = os.path.join(ROOT, "pbrt-v4_amd")

@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+from boundary_helpers import _f32_bits as bits
 from conftest import GOLDEN
 
 pytestmark = pytest.mark.gpu
@@ -52,10 +53,6 @@ def _close_scenes():
     for s in _scenes.values():
         s.close()
     _scenes.clear()
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def same_bits(got, want):

@@ -7,7 +7,7 @@ import subprocess
 import pytest
 
 from conftest import GOLDEN, ROOT
-from test_abi import declared
+from suite_helpers import declared
 
 NEW_ABI = ["wf_film_channel_count", "wf_film_develop_device", "wf_film_develop_rgb_device", "wf_film_spectral_upload", "wf_film_gbuffer_upload"]
 NEW_HOST = ["wfh_film_image_device"]

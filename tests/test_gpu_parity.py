@@ -9,28 +9,10 @@ import sys
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT, WF_CPU, image_error, read_pfm, run_wf_cpu
+from conftest import GOLDEN, ROOT, WF_CPU, image_error, read_pfm
+from suite_helpers import REL_TOL, _check_image_vs_oracle_and_reference, _render_both, assert_image_parity, desc_fields
 
 pytestmark = pytest.mark.gpu
-
-# float tolerance for images: the north_star's 1e-3 relative L-inf, measured relative to max(|ref|, 1e-2)
-# (the images' mean is ~0.12-0.2), on EVERY value.  The device evaluates the same float libm as the reference
-# (csrc/common/wf_libm.h), so in practice the images are bit-identical and the ray counts equal.
-REL_TOL = 1e-3
-# What the suite ASSERTS since round 5: every image below is BIT-IDENTICAL with the reference's render (identical == 1.0).  A scene may be
-# excused from that — and then only held to REL_TOL — by an entry here with its reason; the list is empty: nothing is excused.
-NOT_BIT_IDENTICAL = {}
-
-
-def assert_image_parity(name, img, ref):
-    assert img.shape == ref.shape and np.isfinite(img).all(), name
-    rel = image_error(img, ref)
-    identical = float((img.view(np.uint32) == ref.view(np.uint32)).mean())
-    print(name, "max rel", rel.max(), "bit-identical fraction", identical)
-    assert rel.max() <= REL_TOL, (name, rel.max(), (rel > REL_TOL).mean())
-    if name not in NOT_BIT_IDENTICAL:
-        assert identical == 1.0, (name, "bit-identical fraction", identical, "max rel", rel.max())
-
 
 @pytest.fixture(scope="module")
 def cornell(wfpt):
@@ -154,43 +136,10 @@ def test_trace_entry_points_take_ray_times_on_animated_scenes(wfpt, tmp_path):
     assert ((at0["prim"] != got["prim"]) | (at0["t"] != got["t"])).mean() > 0.005
 
 
-def _render_both(scene, path, spp, tmp_path):
-    scene.clear_film()
-    scene.render(0, spp if spp else scene.spp, 1)
-    img = scene.image()
-    out = str(tmp_path / "cpu.pfm")
-    j = run_wf_cpu(path, out, spp)
-    return img, read_pfm(out), j
-
-
 @pytest.mark.parametrize("name", ["cornell64", "blobs_small", "materials_lights", "materials_lights_power", "media_box", "rgbgrid_medium", "tempgrid_medium", "envmap", "textures_bump", "spherical_camera", "image_textures", "alpha_normalmap", "spheres", "quadrics", "lights_extra", "texture_mappings", "textures_extra", "textures_deep", "textures_scale_fold", "tangents_s", "arealight_image", "instances", "subsurface", "blobs_hlbvh", "textures_noise", "cloud_medium", "media_instances", "hair", "measured", "bilinear", "bilinear_lights", "bilinear_emission", "instances_quadrics", "media_preset", "subsurface_named", "arealight_alpha", "png_textures", "textures_ewa", "curves", "realistic_camera", "realistic_camera_star", "portal_light", "portal_uniform", "loopsubdiv", "film_whitebalance", "film_sensor", "film_sensor_wb", "displacement", "plymesh_mixed", "camera_motion", "camera_motion_spherical", "quadrics_alpha", "curves_alpha", "animated", "animated_sss", "animated_tris", "animated_tris_alpha", "face_indices", "goniometric_png",
                                   "cornell64_independent", "cornell64_stratified", "cornell64_paddedsobol", "cornell64_halton", "cornell64_sobol", "cornell64_sobol_owen"])
 def test_image_vs_oracle_and_reference(wfpt, tmp_path, name):
     _check_image_vs_oracle_and_reference(wfpt, tmp_path, name)
-
-
-def _check_image_vs_oracle_and_reference(wfpt, tmp_path, name):
-    path = os.path.join(GOLDEN, name + ".pbrt")
-    spp = 0 if name.startswith("cornell64_") else 4   # the sampler scenes keep their samplers' default sample counts
-    s = wfpt.Scene(path=path, spp=spp)
-    s.create_renderer(0)
-    s.debug_counters(reset=True)
-    img, cpu, j = _render_both(s, path, spp, tmp_path)
-    dbg = s.debug_counters(reset=True)
-    assert dbg["overflow"] == 0
-    if name == "envmap":
-        # the boxes of this scene stand ON the ground quad (coplanar faces): every ray that meets a box bottom is a near-tie,
-        # resolved in reference order inside the walk kernel (RetraceRefOrder) — the path must actually run for the bit-identical
-        # image below to mean something (234 such rays in this render)
-        assert dbg["inline_retraces"] > 0, dbg
-    # integer work: identical ray counts stage by stage
-    st = s.stats()
-    assert st["camera_rays"] == j["camera_rays"]
-    assert s.total_rays() == j["rays"]
-    ref = read_pfm(os.path.join(GOLDEN, name + "_ref.pfm"))  # the reference's own CPU wavefront render
-    assert (cpu.view(np.uint32) == ref.view(np.uint32)).all()  # the port IS the reference, bit for bit
-    s.close()
-    assert_image_parity(name, img, ref)
 
 
 @pytest.mark.parametrize("name", ["spheres", "quadrics", "instances_quadrics", "bilinear", "bilinear_lights", "curves", "arealight_alpha", "media_instances", "instances"])
@@ -798,7 +747,6 @@ def test_device_morton_sort_builds_the_same_hlbvh(wfpt, tmp_path, monkeypatch):
     path = str(tmp_path / "k.pbrt")
     make_scenes.killeroo_like(path, (96, 54), 1)
     text = open(path).read().replace("WorldBegin", 'Accelerator "bvh" "string splitmethod" "hlbvh"\nWorldBegin', 1)
-    from test_host import desc_fields
     def nodes(scene):
         h = desc_fields(wfpt, scene)
         return (np.ctypeslib.as_array((C.c_uint32 * (8 * h.n_bvh_nodes)).from_address(h.bvh_nodes)).copy(),
@@ -837,7 +785,6 @@ def test_device_sah_build_gives_the_host_tree_node_for_node(wfpt, tmp_path, monk
     import ctypes as C
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import make_scenes
-    from test_host import desc_fields, BvhNode
 
     def nodes(scene):
         h = desc_fields(wfpt, scene)

@@ -7,22 +7,9 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT, load_pkg, read_pfm
+from suite_helpers import BvhNode, desc_fields
 
 
-class BvhNode(C.Structure):
-    _fields_ = [("bmin", C.c_float * 3), ("bmax", C.c_float * 3), ("offset", C.c_int32), ("nprims", C.c_uint16), ("axis", C.c_uint8), ("pad", C.c_uint8)]
-
-
-def desc_fields(wfpt, scene):
-    """read the leading integer fields + pointers of wf_scene_desc via ctypes"""
-    host, _ = wfpt.libs()
-    p = host.wfh_scene_desc(scene.h)
-
-    class Head(C.Structure):
-        _fields_ = [("abi_version", C.c_int32), ("n_vertices", C.c_int32), ("n_triangles", C.c_int32), ("n_meshes", C.c_int32),
-                    ("n_bvh_nodes", C.c_int32), ("P", C.c_void_p), ("N", C.c_void_p), ("UV", C.c_void_p), ("tri_indices", C.c_void_p),
-                    ("tri_mesh", C.c_void_p), ("meshes", C.c_void_p), ("bvh_nodes", C.c_void_p), ("bvh_prims", C.c_void_p)]
-    return Head.from_address(p)
 
 
 def test_cornell_tables(wfpt):

@@ -11,6 +11,7 @@ import os
 import numpy as np
 import pytest
 
+from boundary_helpers import _f32_bits as _bits, _np
 from conftest import GOLDEN
 
 import make_interaction_goldens as goldens
@@ -36,14 +37,6 @@ class DescHead(C.Structure):   # the leading members of wf_scene_desc
 
 
 MATERIAL_WORDS = 25   # sizeof(wf_material) / 4; word 0 = type
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
 
 
 class Case:

@@ -11,6 +11,8 @@ import sys
 import numpy as np
 import pytest
 
+from boundary_helpers import (SIDE_OF, Camera, DescLights, _bits, _np, assert_rows_equal, average, begin_pass, download, emission, eval_on_host, open_scene,
+                              queue_size, renderer_before_torch, same, seeded, shade, stage, tables)  # noqa: F401 (the fixture)
 from conftest import GOLDEN, ROOT
 
 pytestmark = pytest.mark.gpu
@@ -26,10 +28,6 @@ TYPES = {"cornell64": [{AREA}], "materials_lights": [{POINT}, {DISTANT}, {SPOT},
          "quadrics": [{AREA}, {POINT}, {UNIFORM_INF, IMAGE_INF}], "bilinear_lights": [{AREA}], "arealight_image": [{AREA}, {UNIFORM_INF, IMAGE_INF}],
          "arealight_alpha": [{AREA}]}
 NON_TRIANGLE_EMITTERS = ("quadrics", "bilinear_lights")
-DIFFUSE, CONDUCTOR, DIELECTRIC, THIN_DIELECTRIC, DIFFUSE_TRANSMISSION, COATED_DIFFUSE, COATED_CONDUCTOR = range(1, 8)
-# the LightSampleContext's side by the material's BSDF (surfscatter.cpp:256-261): reflective only +1, reflective and transmissive -1
-SIDE_OF = {DIFFUSE: 1, CONDUCTOR: 1, COATED_DIFFUSE: 1, COATED_CONDUCTOR: 1, DIELECTRIC: -1, THIN_DIELECTRIC: -1, DIFFUSE_TRANSMISSION: -1}
-MATERIAL_WORDS, LIGHT_WORDS = 25, 25   # sizeof(wf_material) / 4, sizeof(wf_light) / 4; word 0 = type, word 4 of a light = tri
 SPECULAR_BOUNCE = 1
 
 TWO_SKIES = """
@@ -51,91 +49,21 @@ Shape "trianglemesh" "integer indices" [ 0 1 2 0 2 3 ] "point3 P" [ -3 0 -1  3 0
 """
 
 
-class DescLights(C.Structure):   # the leading members of wf_scene_desc, up to the light table
-    _fields_ = [("abi_version", C.c_int32), ("n_vertices", C.c_int32), ("n_triangles", C.c_int32), ("n_meshes", C.c_int32), ("n_bvh_nodes", C.c_int32),
-                ("P", C.c_void_p), ("N", C.c_void_p), ("UV", C.c_void_p), ("tri_indices", C.c_void_p), ("tri_mesh", C.c_void_p), ("meshes", C.c_void_p),
-                ("bvh_nodes", C.c_void_p), ("bvh_prims", C.c_void_p), ("scene_bounds", C.c_float * 6),
-                ("n_spectra", C.c_int32), ("n_spectrum_floats", C.c_int32), ("n_textures", C.c_int32), ("n_materials", C.c_int32),
-                ("spectra", C.c_void_p), ("spectrum_data", C.c_void_p), ("textures", C.c_void_p), ("materials", C.c_void_p),
-                ("n_lights", C.c_int32), ("n_infinite_lights", C.c_int32), ("n_light_bvh_nodes", C.c_int32), ("n_light_transforms", C.c_int32),
-                ("lights", C.c_void_p), ("infinite_lights", C.c_void_p)]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def renderer_before_torch(wfpt):
-    """The library's HIP runtime comes up (a first renderer) before this module imports torch, which brings a runtime of its own: the
-    order every test of the device-buffer calls has (scene first, tensors second), also when this file runs alone."""
-    s = wfpt.Scene(path=os.path.join(GOLDEN, "cornell64.pbrt"), spp=4)
-    s.create_renderer(0)
-    s.close()
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def same(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.tobytes() == b.tobytes()
-
-
-def open_scene(wfpt, name, text=None, spp=4):
-    s = wfpt.Scene(path=os.path.join(GOLDEN, name + ".pbrt"), spp=spp) if text is None else wfpt.Scene(text=text, spp=spp)
-    s.create_renderer(0, samples_per_pass=1)
-    assert s.query("pixels_per_pass") == s.width * s.height   # the image is one band
-    return s
-
-
-def tables(wfpt, s):
-    """(type of every light, tri of every light, type of every material, n_triangles, flags of every light) from the description the
-    host library built"""
-    host, _ = wfpt.libs()
-    h = DescLights.from_address(host.wfh_scene_desc(s.h))
-    lights = np.ctypeslib.as_array((C.c_int32 * (LIGHT_WORDS * max(h.n_lights, 1))).from_address(h.lights)).reshape(-1, LIGHT_WORDS)[:h.n_lights].copy() \
-        if h.n_lights else np.zeros((0, LIGHT_WORDS), np.int32)
-    mats = np.ctypeslib.as_array((C.c_int32 * (MATERIAL_WORDS * h.n_materials)).from_address(h.materials)).reshape(-1, MATERIAL_WORDS)[:, 0].copy()
-    assert h.n_lights == s.query("lights") and h.n_infinite_lights == s.query("infinite_lights")
-    return lights[:, 0], lights[:, 4], mats, h.n_triangles, lights[:, 1]
-
-
-def seeded(n, cols, seed, dev):
-    import torch
-    g = torch.Generator().manual_seed(seed)
-    return torch.rand((n, cols), generator=g, dtype=torch.float32).to(dev)
-
-
 def eval_host(name_or_path, call, planes_f, planes_i, lam, u4=None, side=None, rays=None, prev=None, index=0, tmp=None):
     """light_sample_check --eval on downloaded inputs -> the expected outputs (numpy)"""
     n = planes_f.shape[1]
     path = name_or_path if os.path.sep in name_or_path else os.path.join(GOLDEN, name_or_path + ".pbrt")
-    a, b = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
     head = np.array([0x4c534331, call, n, index, int(side is not None), int(prev is not None), 0, 0], np.int32)
     parts = [head, planes_f.astype(np.float32), planes_i.astype(np.int32), lam.astype(np.float32)]
     parts += [u4.astype(np.float32)] + ([side.astype(np.int32)] if side is not None else []) if call == 0 else \
         [rays.astype(np.float32)] + ([prev[:4].astype(np.float32)] if prev is not None else [])
-    with open(a, "wb") as f:
-        for x in parts:
-            f.write(np.ascontiguousarray(x).tobytes())
-    subprocess.run([CHECK, "--eval", path, a, b], check=True, capture_output=True)
-    raw = open(b, "rb").read()
+    raw = eval_on_host(CHECK, [], path, parts, tmp)
     if call == 0:
         assert len(raw) == n * 80
         return {"shadow_rays8": np.frombuffer(raw, np.float32, n * 8).reshape(n, 8), "L4": np.frombuffer(raw, np.float32, n * 4, n * 32).reshape(n, 4),
                 "wi_pdf4": np.frombuffer(raw, np.float32, n * 4, n * 48).reshape(n, 4), "light4": np.frombuffer(raw, np.int32, n * 4, n * 64).reshape(n, 4)}
     assert len(raw) == n * 32
     return {"Le4": np.frombuffer(raw, np.float32, n * 4).reshape(n, 4), "pmf_pdf4": np.frombuffer(raw, np.float32, n * 4, n * 16).reshape(n, 4)}
-
-
-def assert_rows_equal(got, want, keys, what):
-    for k in keys:
-        g, w = _np(got[k]) if not isinstance(got[k], np.ndarray) else got[k], want[k]
-        assert g.shape == w.shape, (what, k)
-        bad = np.nonzero((_bits(g) != _bits(w)).reshape(g.shape[0], -1).any(axis=1))[0]
-        assert bad.size == 0, "%s: %s differs in %d of %d rows, first row %d: %r / %r" % (what, k, bad.size, g.shape[0], bad[0], g[bad[0]], w[bad[0]])
 
 
 SAMPLE_KEYS = ("shadow_rays8", "L4", "wi_pdf4", "light4")
@@ -207,69 +135,6 @@ def test_both_calls_equal_the_host_composition(wfpt, name, tmp_path):
     if chosen & {AREA, IMAGE_INF}:
         assert with_pdf > 0
     s.close()
-
-
-# ---- the render's stages through the C ABI ----------------------------------------------------------------------------------------------
-def download(wfpt, s, queue, member, n, dtype, cols):
-    _, hip = wfpt.libs()
-    hip.wf_queue_download.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_uint64]
-    a = np.empty((n, cols), dtype)
-    if n:
-        wfpt._check(hip.wf_queue_download(s.ctx, queue.encode(), member.encode(), a.ctypes.data, a.nbytes), "wf_queue_download")
-    return a
-
-
-def queue_size(wfpt, s, queue):
-    _, hip = wfpt.libs()
-    hip.wf_queue_size.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int)]
-    v = C.c_int(0)
-    wfpt._check(hip.wf_queue_size(s.ctx, queue.encode(), C.byref(v)), "wf_queue_size")
-    return v.value
-
-
-def stage(wfpt, s, name, *args):
-    _, hip = wfpt.libs()
-    f = getattr(hip, name)
-    f.argtypes = [C.c_void_p] + [C.c_int] * len(args)
-    wfpt._check(f(s.ctx, *args), name)
-
-
-def begin_pass(wfpt, s):
-    """the unfused order of the render's pass (csrc/host/integrator.cpp), sample index 0, up to depth 0's closest hits"""
-    stage(wfpt, s, "wf_set_pass_samples", 1, 1)
-    stage(wfpt, s, "wf_reset_ray_queue", 0)
-    stage(wfpt, s, "wf_gen_camera_rays", s.info.y0, 0)
-    stage(wfpt, s, "wf_reset_stage_queues", 0)
-    stage(wfpt, s, "wf_gen_ray_samples", 0, 0)
-    stage(wfpt, s, "wf_intersect_closest", 0)
-
-
-def emission(wfpt, s, depth):
-    stage(wfpt, s, "wf_handle_escaped", depth)
-    stage(wfpt, s, "wf_handle_emissive", depth)
-    stage(wfpt, s, "wf_sync")
-
-
-def shade(wfpt, s, depth, mats):
-    for t in sorted(set(int(m) for m in mats) - {0, 11}):
-        stage(wfpt, s, "wf_eval_material", t, depth)
-    stage(wfpt, s, "wf_sync")
-
-
-class Camera:
-    """the camera samples of sample index 0, their first hits, and the row of every pixel index"""
-
-    def __init__(self, wfpt, s):
-        import torch
-        self.rays, self.pix, self.lam, self.pdf, self.cam_w, self.fw = s.camera_samples_device(0)
-        self.hits = s.trace_device(self.rays)
-        self.it = s.interactions_device(self.rays, self.hits)
-        torch.cuda.synchronize()
-        xy = _np(self.pix)
-        self.pixel_index = (xy[:, 1].astype(np.int64) - s.info.y0) * s.width + xy[:, 0]
-        assert len(np.unique(self.pixel_index)) == len(xy) == s.width * s.height
-        self.row_of = np.full(s.width * s.height, -1, np.int64)
-        self.row_of[self.pixel_index] = np.arange(len(xy))
 
 
 # ---- 2: depth-0 emission ---------------------------------------------------------------------------------------------------------------
@@ -347,15 +212,6 @@ def test_sample_rows_equal_the_renders_shadow_queue(wfpt, name):
 
 
 # ---- 4: the depth-1 MIS weights -----------------------------------------------------------------------------------------------------------
-def average(x):
-    """S4::Average (wf_math.h): s = v0; s += v1; s += v2; s += v3; s / 4"""
-    s = x[:, 0]
-    s = s + x[:, 1]
-    s = s + x[:, 2]
-    s = s + x[:, 3]
-    return (s / 4)[:, None]
-
-
 @pytest.mark.parametrize("name, kind", [("cornell64", "emitter"), ("envmap", "escape")])
 def test_emitted_pmf_and_pdf_give_the_renders_depth1_mis_weights(wfpt, name, kind):
     import torch

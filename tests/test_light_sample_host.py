@@ -11,7 +11,7 @@ import subprocess
 import pytest
 
 from conftest import GOLDEN, ROOT
-from test_abi import declared
+from suite_helpers import declared
 
 NEW_ABI = ["wf_light_sample_device", "wf_light_emitted_device"]
 SRC = os.path.join(ROOT, "pbrt-v4_amd")

@@ -30,7 +30,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, read_pfm, run_wf_cpu
-from test_gpu_parity import assert_image_parity
+from suite_helpers import assert_image_parity
 
 pytestmark = pytest.mark.gpu
 

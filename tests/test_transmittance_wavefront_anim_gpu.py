@@ -9,8 +9,8 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
-from test_device_trace_gpu import _dev, _launch_names, _rays8, _shadow_rays, _tr_device
-from test_gpu_parity import _check_image_vs_oracle_and_reference
+from boundary_helpers import _dev, _launch_names, _rays8, _shadow_rays, _tr_device
+from suite_helpers import _check_image_vs_oracle_and_reference
 
 pytestmark = pytest.mark.gpu
 

@@ -27,45 +27,13 @@
 #include <string>
 #include <vector>
 #include "../pbrt-v4_amd/csrc/hip/wf_boundary_bsdf.h"
-#include "../pbrt-v4_amd/csrc/host/scene.h"
+#include "check_common.h"
 
 using namespace wf;
 
 namespace {
 
 constexpr int32_t MAGIC = 0x42534431;
-
-// a scene description as a host SceneView: what the walk, the interactions, the textures and the materials reach
-SceneView MakeView(const wf_scene_desc &d) {
-    SceneView sv{};
-    sv.P = d.P; sv.N = d.N; sv.UV = d.UV; sv.S = d.S; sv.triIndices = d.tri_indices; sv.triMesh = d.tri_mesh; sv.meshes = d.meshes;
-    sv.bvhNodes = d.bvh_nodes; sv.bvhPrims = d.bvh_prims; sv.nTriangles = d.n_triangles; sv.nBvhNodes = d.n_bvh_nodes;
-    sv.spectra = d.spectra; sv.spectrumData = d.spectrum_data; sv.textures = d.textures; sv.materials = d.materials;
-    sv.lights = d.lights; sv.infiniteLights = d.infinite_lights; sv.lightBvh = d.light_bvh_nodes; sv.lightXforms = d.light_transforms;
-    sv.nLights = d.n_lights; sv.nInfiniteLights = d.n_infinite_lights; sv.nLightBvhNodes = d.n_light_bvh_nodes; sv.lightSampler = d.light_sampler;
-    sv.camera = d.camera; sv.film = d.film; sv.filter = d.filter; sv.sampler = d.sampler;   // (the texture footprint scales with the sampler's spp)
-    sv.texImages = d.tex_images;
-    sv.imageLights = d.image_lights; sv.tableData = d.table_data; sv.rgb2specCoeffs = d.rgb2spec_coeffs; sv.rgb2specZNodes = d.rgb2spec_znodes;
-    sv.noisePerm = d.noise_perm;
-    sv.csIlluminantOffset = d.cs_illuminant_offset;
-    sv.media = d.media; sv.mediumData = d.medium_data;
-    sv.maxDepth = d.max_depth; sv.regularize = d.regularize; sv.haveMedia = d.have_media; sv.options = d.options;
-    sv.quadrics = d.quadrics; sv.nQuadrics = d.n_quadrics;
-    sv.instances = d.instances; sv.instanceDefs = d.instance_defs; sv.nInstances = d.n_instances;
-    sv.animated = d.animated; sv.haveAnimated = d.n_animated > 0;
-    for (int i = 0; i < d.n_meshes; ++i) if (d.meshes[i].alpha_tex >= 0) sv.haveAlpha = 1;
-    for (int i = 0; i < d.n_quadrics; ++i) {
-        if (d.meshes[d.quadrics[i].mesh].alpha_tex >= 0) sv.haveQuadricAlpha = 1;
-        if (d.quadrics[i].type == WF_QUADRIC_CURVE) sv.haveCurves = 1;
-    }
-    for (int i = 0; i < d.n_materials; ++i) {
-        if (d.materials[i].type == WF_MAT_MIX) sv.haveMix = 1;
-        else if (d.materials[i].type == WF_MAT_SUBSURFACE) sv.haveSubsurface = 1;
-        if (d.materials[i].type != WF_MAT_MIX) sv.matTypeMask |= 1 << d.materials[i].type;
-    }
-    sv.texNeedsFootprint = 1;
-    return sv;
-}
 
 struct Rows {
     int n = 0;
@@ -370,10 +338,7 @@ int Self(const SceneView &sv, const wf_scene_desc &d, int n) {
         const float time = u();
         r.rays[2 * i] = F4{eye.x, eye.y, eye.z, dir.x};
         r.rays[2 * i + 1] = F4{dir.y, dir.z, WF_INFINITY, time};
-        F4 lam;
-        lam.x = 360.f + u() * 470.f;
-        { float *p = &lam.x; for (int k = 1; k < 4; ++k) { p[k] = p[k - 1] + 117.5f; if (p[k] > 830.f) p[k] = 360.f + (p[k] - 830.f); } }
-        r.lambda4[i] = lam;
+        r.lambda4[i] = check::RotatedWavelengths(u());
         r.u4[i] = F4{u(), u(), u(), u()};
         r.reg[i] = (int32_t)(i & 1);
         ArrayStack st;
@@ -439,10 +404,7 @@ int Self(const SceneView &sv, const wf_scene_desc &d, int n) {
 }
 
 // ---- --eval -------------------------------------------------------------------------------------------------------------------------
-template <typename T> bool ReadVec(FILE *f, std::vector<T> &v, size_t count) {
-    v.resize(count);
-    return count == 0 || fread(v.data(), sizeof(T), count, f) == count;
-}
+using check::ReadVec;
 int Eval(const SceneView &sv, int nMaterials, const char *inPath, const char *outPath) {
     FILE *f = fopen(inPath, "rb");
     if (!f) { perror(inPath); return 1; }
@@ -485,30 +447,12 @@ int main(int argc, char **argv) {
         fprintf(stderr, "usage: bsdf_check [--datadir <dir>] [--spp <pixel samples>] --self scene.pbrt N | --eval scene.pbrt in.bin out.bin\n");
         return 2;
     }
-    if (dataDir.empty()) {
-        // <repo>/pbrt-v4_amd/data relative to this binary's usual location pbrt-v4_amd/_build/bsdf_check
-        const std::string self = argv[0];
-        const size_t p = self.rfind('/');
-        dataDir = (p == std::string::npos ? std::string(".") : self.substr(0, p)) + "/../data";
-    }
-    try {
-        SpectralData::Init(dataDir, dataDir + "/cache");
-        RenderOptions opt;
-        opt.quiet = true;
-        if (spp > 0) opt.pixelSamples = spp;
-        ParsedScene parsed;
-        ParseFiles({scene}, &opt, &parsed);
-        SceneTables T;
-        BuildSceneTables(parsed, opt, &T);
-        SceneView sv = MakeView(T.desc);
-        sv.self = &sv;
-        static int32_t fatalWord = 0;
-        sv.fatal = &fatalWord;
-        const int rc = mode == "--self" ? Self(sv, T.desc, atoi(rest[0].c_str())) : Eval(sv, T.desc.n_materials, rest[0].c_str(), rest[1].c_str());
-        if (fatalWord != 0) fprintf(stderr, "note: a material function raised the scene's fatal word (%d), as the render would\n", fatalWord);
+    return check::Guarded(scene, [&] {
+        check::InitData(dataDir, argv[0], "/../data");   // (the binary's usual location: pbrt-v4_amd/_build/bsdf_check)
+        RenderOptions opt = check::QuietOptions(spp);
+        const check::HostScene hs(scene, &opt);
+        const int rc = mode == "--self" ? Self(hs.sv, hs.T.desc, atoi(rest[0].c_str())) : Eval(hs.sv, hs.T.desc.n_materials, rest[0].c_str(), rest[1].c_str());
+        if (hs.fatalWord != 0) fprintf(stderr, "note: a material function raised the scene's fatal word (%d), as the render would\n", hs.fatalWord);
         return rc;
-    } catch (const std::exception &e) {
-        fprintf(stderr, "%s: %s\n", scene.c_str(), e.what());
-        return 1;
-    }
+    });
 }

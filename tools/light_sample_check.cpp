@@ -22,33 +22,13 @@
 #include <string>
 #include <vector>
 #include "../pbrt-v4_amd/csrc/hip/wf_boundary_light.h"
-#include "../pbrt-v4_amd/csrc/host/scene.h"
+#include "check_common.h"
 
 using namespace wf;
 
 namespace {
 
 constexpr int32_t MAGIC = 0x4c534331;
-
-// the light-related tables of a scene description as a host SceneView (and what the light functions reach through them: the spectra,
-// the image tables, the textures of an emitter's alpha, the vertex tables of triangle emitters, the quadrics)
-SceneView MakeLightView(const wf_scene_desc &d) {
-    SceneView sv{};
-    sv.P = d.P; sv.N = d.N; sv.UV = d.UV; sv.S = d.S; sv.triIndices = d.tri_indices; sv.triMesh = d.tri_mesh; sv.meshes = d.meshes;
-    sv.nTriangles = d.n_triangles;
-    sv.spectra = d.spectra; sv.spectrumData = d.spectrum_data; sv.textures = d.textures; sv.materials = d.materials;
-    sv.lights = d.lights; sv.infiniteLights = d.infinite_lights; sv.lightBvh = d.light_bvh_nodes; sv.lightXforms = d.light_transforms;
-    sv.nLights = d.n_lights; sv.nInfiniteLights = d.n_infinite_lights; sv.nLightBvhNodes = d.n_light_bvh_nodes; sv.lightSampler = d.light_sampler;
-    for (int i = 0; i < 6; ++i) sv.allLightBounds[i] = d.all_light_bounds[i];
-    sv.powerAlias = d.power_alias;
-    sv.texImages = d.tex_images;
-    sv.imageLights = d.image_lights; sv.tableData = d.table_data; sv.rgb2specCoeffs = d.rgb2spec_coeffs; sv.rgb2specZNodes = d.rgb2spec_znodes;
-    sv.noisePerm = d.noise_perm;
-    sv.csIlluminantOffset = d.cs_illuminant_offset;
-    sv.haveMedia = d.have_media; sv.options = d.options;
-    sv.quadrics = d.quadrics; sv.nQuadrics = d.n_quadrics;
-    return sv;
-}
 
 struct Rows {
     int call = 0, n = 0, infiniteIndex = 0;
@@ -159,13 +139,7 @@ struct Gen {
     float u() { return uni(rng); }
     V3 point() { return V3{lo[0] + u() * (hi[0] - lo[0]), lo[1] + u() * (hi[1] - lo[1]), lo[2] + u() * (hi[2] - lo[2])}; }
     V3 dir() { return SampleUniformSphere(V2{u(), u()}); }
-    F4 lambda() {
-        F4 l;
-        l.x = 360.f + u() * 470.f;
-        float *p = &l.x;
-        for (int i = 1; i < 4; ++i) { p[i] = p[i - 1] + 117.5f; if (p[i] > 830.f) p[i] = 360.f + (p[i] - 830.f); }
-        return l;
-    }
+    F4 lambda() { return check::RotatedWavelengths(u()); }
 };
 
 // planes 0 - 4 and the two id planes of a row at p: a small position interval, a normal that is zero on every eighth row
@@ -278,10 +252,7 @@ int Self(const SceneView &sv, const wf_scene_desc &d, int n) {
 }
 
 // ---- --eval -------------------------------------------------------------------------------------------------------------------------
-template <typename T> bool ReadVec(FILE *f, std::vector<T> &v, size_t count) {
-    v.resize(count);
-    return count == 0 || fread(v.data(), sizeof(T), count, f) == count;
-}
+using check::ReadVec;
 int Eval(const SceneView &sv, const char *inPath, const char *outPath) {
     FILE *f = fopen(inPath, "rb");
     if (!f) { perror(inPath); return 1; }
@@ -337,29 +308,12 @@ int main(int argc, char **argv) {
         fprintf(stderr, "usage: light_sample_check [--datadir <dir>] --self scene.pbrt N | --eval scene.pbrt in.bin out.bin\n");
         return 2;
     }
-    if (dataDir.empty()) {
-        // <repo>/pbrt-v4_amd/data relative to this binary's usual location pbrt-v4_amd/_build/light_sample_check
-        const std::string self = argv[0];
-        const size_t p = self.rfind('/');
-        dataDir = (p == std::string::npos ? std::string(".") : self.substr(0, p)) + "/../data";
-    }
-    try {
-        SpectralData::Init(dataDir, dataDir + "/cache");
-        RenderOptions opt;
-        opt.quiet = true;
-        ParsedScene parsed;
-        ParseFiles({scene}, &opt, &parsed);
-        SceneTables T;
-        BuildSceneTables(parsed, opt, &T);
-        SceneView sv = MakeLightView(T.desc);
-        sv.self = &sv;
-        static int32_t fatalWord = 0;
-        sv.fatal = &fatalWord;
-        const int rc = mode == "--self" ? Self(sv, T.desc, atoi(rest[0].c_str())) : Eval(sv, rest[0].c_str(), rest[1].c_str());
-        if (fatalWord != 0) { fprintf(stderr, "a light function raised the scene's fatal word (%d)\n", fatalWord); return 1; }
+    return check::Guarded(scene, [&] {
+        check::InitData(dataDir, argv[0], "/../data");   // (the binary's usual location: pbrt-v4_amd/_build/light_sample_check)
+        RenderOptions opt = check::QuietOptions();
+        const check::HostScene hs(scene, &opt);
+        const int rc = mode == "--self" ? Self(hs.sv, hs.T.desc, atoi(rest[0].c_str())) : Eval(hs.sv, rest[0].c_str(), rest[1].c_str());
+        if (hs.fatalWord != 0) { fprintf(stderr, "a light function raised the scene's fatal word (%d)\n", hs.fatalWord); return 1; }
         return rc;
-    } catch (const std::exception &e) {
-        fprintf(stderr, "%s: %s\n", scene.c_str(), e.what());
-        return 1;
-    }
+    });
 }

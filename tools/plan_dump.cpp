@@ -13,10 +13,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <exception>
 #include <string>
-#include "../pbrt-v4_amd/csrc/host/scene.h"
-#include "../pbrt-v4_amd/csrc/host/spectra.h"
+#include "check_common.h"
 #include "../pbrt-v4_amd/csrc/hip/wf_plan.h"
 
 using namespace wf;
@@ -54,12 +52,9 @@ static void DumpTables(const SceneTables &T) {
 }
 
 static void DumpScene(const std::string &path, int nRays, bool tables) {
-    RenderOptions opt;
-    opt.quiet = true;
-    ParsedScene parsed;
-    ParseFiles({path}, &opt, &parsed);
+    RenderOptions opt = check::QuietOptions();
     SceneTables T;
-    BuildSceneTables(parsed, opt, &T);
+    check::LoadTables(path, &opt, &T);
     const size_t slash = path.rfind('/');
     printf("%s:", (slash == std::string::npos ? path : path.substr(slash + 1)).c_str());
     if (tables) DumpTables(T);
@@ -109,18 +104,9 @@ int main(int argc, char **argv) {
         else scenes.push_back(a);
     }
     if (scenes.empty()) { fprintf(stderr, "usage: plan_dump [--datadir <dir>] [--rays <n>] [--tables] scene.pbrt ...\n"); return 1; }
-    if (dataDir.empty()) {
-        // <repo>/pbrt-v4_amd/data relative to this binary's usual location pbrt-v4_amd/_build/plan_dump
-        const std::string self = argv[0];
-        const size_t p = self.rfind('/');
-        dataDir = (p == std::string::npos ? std::string(".") : self.substr(0, p)) + "/../data";
-    }
-    try {
-        SpectralData::Init(dataDir, dataDir + "/cache");
+    return check::Guarded("", [&] {
+        check::InitData(dataDir, argv[0], "/../data");   // (the binary's usual location: pbrt-v4_amd/_build/plan_dump)
         for (const std::string &s : scenes) { DumpScene(s, nRays, tables); fflush(stdout); }
-    } catch (const std::exception &e) {
-        fprintf(stderr, "%s\n", e.what());
-        return 1;
-    }
-    return 0;
+        return 0;
+    });
 }
