@@ -848,7 +848,8 @@ int wf_film_add_samples_device(wf_ctx *ctx, int n, const int32_t *n_device /* ma
    (wf_bsdf_make_device / wf_bsdf_eval_device below, which also answer `side`).  Both calls take the planes
    wf_hit_interaction_device writes (planes_f [WF_INTR_FPLANES][n][4], planes_i [WF_INTR_IPLANES][n][4], plane stride n), so its output
    feeds them as it is; a caller with points of its own fabricates the planes it needs: pi lower = pi upper = p and n = ns = 0 is the
-   reference's context of a point in a medium.  Both are launched on the context's stream (wf_stream) and NOT synchronised; every
+   reference's context of a point in a medium — such a row (n = 0) gets the shadow ray SampleMediumScattering spawns, {p, pLight - p}
+   with no offset at either end (media.cpp:300); p is pi's midpoint where the row's interval has a width.  Both are launched on the context's stream (wf_stream) and NOT synchronised; every
    argument is checked before anything is launched (4-float arrays and planes are aligned to 16 bytes, side and n_device to 4; all
    device pointers of the context's device; n <= 0 touches nothing); n_device is NULL or a device word: min(n, *n_device) rows are
    processed and the rows after them are not written.  They need an uploaded scene, no queues, and touch none of the render's queues,
@@ -950,7 +951,8 @@ int wf_light_emitted_device(wf_ctx *ctx, int n, const int32_t *n_device /* may b
      The kernels never follow an address read from the record, and the scene's tables are indexed by the header only after it is checked.
    NOT here: importance transport (TransportMode::Importance); rho / the GBuffer's albedo; the BSSRDF — a subsurface material's row is
    its dielectric boundary, a transmitted sample says so in its flags and the caller has no SampleSubsurface to continue it with;
-   Russian roulette, which is the caller's. */
+   Russian roulette, which is the caller's.  Participating media and the phase function are in a header of their own, wf_media.h
+   (wf_medium_sample_device, wf_phase_device): with them the path tracer is a volumetric one. */
 #define WF_BSDF_PLANES 10
 int wf_bsdf_make_device(wf_ctx *ctx, int n, const int32_t *n_device /* may be NULL */, const float *rays8 /* [n][8] */, const float *planes_f,
                         const int32_t *planes_i, const float *lambda4 /* [n][4] */, const int32_t *regularize /* [n], may be NULL: none */,
@@ -1045,6 +1047,8 @@ int wf_debug_counters(wf_ctx *ctx, uint64_t out[4], int reset);
    "light_sample_rare" (the kernel of wf_light_sample_device: 1 = the one that samples every light type, chosen as "rare_lights" is),
    "light_emitted_variant" (the kernel of wf_light_emitted_device: bit 0 portal infinite lights are reachable, bit 1 an emitter's alpha
    texture), "lights" / "infinite_lights" (the sizes of the scene's light table and of its list of infinite lights),
+   "medium_sample_variant" (the kernel of wf_medium_sample_device, wf_media.h: 1 = the lean one, chosen as "medium_lean" is), "media" (the
+   size of the scene's medium table: the medium ids a row may carry are -1 .. media - 1), "camera_medium" (the camera's medium, or -1),
    "pixels_per_pass" (the pixels of one band of wf_queues_alloc, 0 before it: the least n_max of wf_camera_rays_device),
    "stage_rounds" / "stage_grid_cap" (WF_STAGE_ROUNDS, WF_STAGE_GRID_CAP as the upload read them: the stage kernels' grids are
    min(one workgroup per block of the full queue, rounds x the workgroups the chip keeps resident of the kernel), at most the cap),
@@ -1073,7 +1077,7 @@ int wf_scene_check_instances(const wf_scene_desc *d, int64_t out[4]);
    wf_scene_upload on `d` under the current environment switches (every check of the description, the classification, the production
    trees) and answers the keys that follow from the description alone: "fast_ok", "gen_mode", "gen_tri", "defer_general", "anim_fast",
    "lean_shade", "lean_type_<material type>", "rare_lights", "medium_lean", "instances", "nested_animated", "tr_route", "intr_variant",
-   "camera_anim", "route_variant", "shade_variant_<material type>", and "stage_grid:<...>" (the grid rule, whatever the scene).  A description that
+   "camera_anim", "route_variant", "shade_variant_<material type>", "medium_sample_variant", "media", "camera_medium", and "stage_grid:<...>" (the grid rule, whatever the scene).  A description that
    wf_scene_upload would reject fails here with the same message.  Every call plans the scene anew, tree build included: meant for
    tests and tools on small scenes, not for asking many keys of a large one. */
 int wf_scene_plan_query(const wf_scene_desc *d, const char *key, int64_t *value);

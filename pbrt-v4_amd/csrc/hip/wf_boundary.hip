@@ -2,10 +2,12 @@
 // samples, in device buffers (wf_*_device) or host arrays (wf_trace_*_host), through the walks and stages of the uploaded scene, and the
 // plain device-memory calls.  No kernel lives here: the walks are wf_backend.hip's, launched through the pointers PickWalkKernels /
 // PickStageKernels left in the context (ctx->walk, ctx->stage), and the boundary's own kernels are behind the launchers of
-// wf_boundary_intr.hip, wf_film_add.hip, wf_boundary_light.hip and wf_boundary_bsdf.hip — so an edit to a call's argument checks leaves every device code object as it was.
+// wf_boundary_intr.hip, wf_film_add.hip, wf_boundary_light.hip, wf_boundary_bsdf.hip and wf_boundary_medium.hip — so an edit to a call's argument checks leaves every device code object as it was.
 // (A .hip unit for the LAUNCH* macros of wf_ctx.h; its device pass has nothing to emit.)
 #include "wf_ctx.h"
 #include "wf_boundary_bsdf.h"
+#include "wf_boundary_medium.h"
+#include "wf_media.h"
 
 extern "C" {
 
@@ -298,6 +300,62 @@ int wf_bsdf_eval_device(wf_ctx *ctx, int n, const int32_t *n_device, const float
         if (t != 0 && !ctx->plan.matPresent[t]) continue;
         if (const int e = kBsdfEval[t](ctx->stream, ctx->svDev, &a)) return fail(e, "%s: the launch for material type %d failed: %s", fn, t, hipGetErrorString((hipError_t)e));
     }
+    return 0;
+}
+// The scene's media and phase functions on a caller's device items (include/wf_media.h; kernels and launchers: wf_boundary_medium.hip).
+// Everything is checked before anything is launched; the calls read the uploaded scene and the caller's buffers, nothing of the
+// render's state.
+int wf_medium_sample_device(wf_ctx *ctx, int n, const int32_t *n_device, const float *rays8, const int32_t *medium, const float *lambda4, const float *beta4,
+                            const float *r_u4, const float *r_l4, const int32_t *flags, int32_t *event4, float *p_g4, float *out_beta4, float *out_r_u4,
+                            float *out_r_l4, float *L4) {
+    const char *fn = "wf_medium_sample_device";
+    if (!ctx) return fail(-1, "%s: null context", fn);
+    if (!ctx->sceneLoaded) return fail(-1, "%s: no scene uploaded", fn);
+    if (!ctx->svHost.haveMedia) return fail(-1, "%s: the scene has no media", fn);
+    if (n < 0) return fail(-1, "%s: n = %d", fn, n);
+    if (n == 0) return 0;
+    if (n > (1 << 30)) return fail(-1, "%s: n = %d is more than 2^30 items", fn, n);
+    if (const char *w = FirstNull({{"rays8", rays8}, {"medium", medium}, {"lambda4", lambda4}, {"beta4", beta4}, {"r_u4", r_u4}, {"r_l4", r_l4}, {"event4", event4},
+                                   {"p_g4", p_g4}, {"out_beta4", out_beta4}, {"out_r_u4", out_r_u4}, {"out_r_l4", out_r_l4}, {"L4", L4}}))
+        return fail(-1, "%s: null %s", fn, w);
+    if (const char *w = FirstMisaligned({{"rays8", rays8}, {"lambda4", lambda4}, {"beta4", beta4}, {"r_u4", r_u4}, {"r_l4", r_l4}, {"event4", event4}, {"p_g4", p_g4},
+                                         {"out_beta4", out_beta4}, {"out_r_u4", out_r_u4}, {"out_r_l4", out_r_l4}, {"L4", L4}}, 15u))
+        return fail(-1, "%s: %s is not aligned to 16 bytes (rays and rows are read and written 16 bytes at a time)", fn, w);
+    if (const char *w = FirstMisaligned({{"medium", medium}, {"flags", flags}, {"n_device", n_device}}, 3u)) return fail(-1, "%s: %s is not aligned to 4 bytes", fn, w);
+    useDevice(ctx);
+    bmedium::TrackArgs a;
+    a.n = n; a.nMedia = ctx->plan.nMedia; a.nDevice = n_device; a.rays8 = rays8; a.medium = medium; a.lambda4 = lambda4; a.beta4 = beta4; a.ru4 = r_u4; a.rl4 = r_l4;
+    a.flags = flags; a.event4 = event4; a.pG4 = p_g4; a.outBeta4 = out_beta4; a.outRu4 = out_r_u4; a.outRl4 = out_r_l4; a.L4 = L4;
+    Prof prof_(ctx, "Sample media (device items)");
+    const int e = bmedium::LaunchMediumTrack(ctx->stream, ctx->plan.mediumLean, ctx->svDev, a);
+    if (e) return fail(e, "%s: the launch failed: %s", fn, hipGetErrorString((hipError_t)e));
+    return 0;
+}
+int wf_phase_device(wf_ctx *ctx, int n, const int32_t *n_device, const float *rays8, const float *p_g4, const float *wi4, const float *u4, float *p_pdf4,
+                    float *sample4, float *next_rays8) {
+    const char *fn = "wf_phase_device";
+    if (!ctx) return fail(-1, "%s: null context", fn);
+    if (!ctx->sceneLoaded) return fail(-1, "%s: no scene uploaded", fn);
+    if (!ctx->svHost.haveMedia) return fail(-1, "%s: the scene has no media", fn);
+    if (n < 0) return fail(-1, "%s: n = %d", fn, n);
+    if (!wi4 && !u4) return fail(-1, "%s: neither wi4 nor u4 is given", fn);
+    if (n == 0) return 0;
+    if (n > (1 << 30)) return fail(-1, "%s: n = %d is more than 2^30 items", fn, n);
+    if (const char *w = FirstNull({{"rays8", rays8}, {"p_g4", p_g4}})) return fail(-1, "%s: null %s", fn, w);
+    if (wi4 && !p_pdf4) return fail(-1, "%s: wi4 is given and p_pdf4 is null", fn);
+    if (u4) if (const char *w = FirstNull({{"sample4", sample4}, {"next_rays8", next_rays8}})) return fail(-1, "%s: u4 is given and %s is null", fn, w);
+    // (the outputs of an absent half are not written: they are not looked at either)
+    if (!wi4) p_pdf4 = nullptr;
+    if (!u4) sample4 = next_rays8 = nullptr;
+    if (const char *w = FirstMisaligned({{"rays8", rays8}, {"p_g4", p_g4}, {"wi4", wi4}, {"u4", u4}, {"p_pdf4", p_pdf4}, {"sample4", sample4}, {"next_rays8", next_rays8}}, 15u))
+        return fail(-1, "%s: %s is not aligned to 16 bytes (rays and rows are read and written 16 bytes at a time)", fn, w);
+    if ((uintptr_t)n_device & 3u) return fail(-1, "%s: n_device is not aligned to 4 bytes", fn);
+    useDevice(ctx);
+    bmedium::PhaseArgs a;
+    a.n = n; a.nDevice = n_device; a.rays8 = rays8; a.pG4 = p_g4; a.wi4 = wi4; a.u4 = u4; a.pPdf4 = p_pdf4; a.sample4 = sample4; a.nextRays8 = next_rays8;
+    Prof prof_(ctx, "Phase functions (device items)");
+    const int e = bmedium::LaunchPhase(ctx->stream, a);
+    if (e) return fail(e, "%s: the launch failed: %s", fn, hipGetErrorString((hipError_t)e));
     return 0;
 }
 // room for n items in ctx->trScratch, the wavefront's arrays among them if the scene's plan routes through it.  Growth waits for the

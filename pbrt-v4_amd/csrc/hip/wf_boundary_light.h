@@ -74,7 +74,10 @@ WF_HD SampleRow SampleFinish(const SceneView &sv, const SampleItem &it, const Li
     row.light = I4{pick.lightId, (int32_t)FloatToBits(pick.pmf), IsDeltaLight(light) ? LIGHT_FLAG_DELTA : 0, -1};
     const LightLiSample &ls = pick.ls;
     if (!(ls.valid && ls.L && ls.pdf != 0)) return row;
-    const RayOD sr = SpawnRayTo(it.pi, it.n, ls.pLightPi, ls.pLightN);
+    // a row without a normal is a point in a medium (include/wf_abi.h; wfpt.Scene.medium_light_planes): its shadow ray is
+    // SampleMediumScattering's, Ray(p, pLight.p() - p) (wavefront/media.cpp:300) — no offset at either end; p = the interval's midpoint
+    const bool inMedium = it.n.x == 0 && it.n.y == 0 && it.n.z == 0;
+    const RayOD sr = inMedium ? RayOD{it.pi.mid(), ls.pLightPi.mid() - it.pi.mid()} : SpawnRayTo(it.pi, it.n, ls.pLightPi, ls.pLightN);
     if (sv.haveMedia) row.light.w = Dot(sr.d, it.n) > 0 ? it.mediumOutside : it.mediumInside;   // SurfaceMedium
     row.ray0 = F4{sr.o.x, sr.o.y, sr.o.z, sr.d.x};
     row.ray1 = F4{sr.d.y, sr.d.z, 1 - ShadowEpsilon, it.time};

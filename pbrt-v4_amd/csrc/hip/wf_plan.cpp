@@ -206,6 +206,8 @@ static void ClassifyScene(const wf_scene_desc *d, const Switches &sw, ScenePlan 
     plan->emittedVariant = EmittedVariant(plan->portalLights, emitterAlpha, plan->rareLights);
     plan->nLights = d->n_lights;
     plan->nInfiniteLights = d->n_infinite_lights;
+    plan->nMedia = d->n_media;
+    plan->cameraMedium = d->n_media > 0 && d->camera.medium >= 0 && d->camera.medium < d->n_media ? d->camera.medium : -1;
     plan->nMaterials = d->n_materials;
     if (d->n_quadrics > 0) plan->genMode = (plan->haveCurves || plan->haveQuadricAlpha) ? 3 : 2;
     {
@@ -328,6 +330,9 @@ bool wf::planning::PlanValue(const ScenePlan &plan, const char *key, int64_t *va
     else if (k == "light_emitted_variant") *value = plan.emittedVariant;  // k_light_emitted<PORTAL, ALPHA, AREA_RARE> (EmittedVariant, wf_plan.h)
     else if (k == "lights") *value = plan.nLights;
     else if (k == "infinite_lights") *value = plan.nInfiniteLights;
+    else if (k == "medium_sample_variant") *value = plan.mediumLean;   // k_medium_track<LEAN> (wf_boundary_medium.hip): chosen as k_medium_sample<LEAN> is
+    else if (k == "media") *value = plan.nMedia;
+    else if (k == "camera_medium") *value = plan.cameraMedium;
     else if (k == "bsdf_planes") *value = WF_BSDF_PLANES;          // the planes of a wf_bsdf_make_device record
     else if (k == "material_types") *value = plan.matTypeMask;     // bit t: the scene holds a material of type t — the k_bsdf_make / k_bsdf_eval launches of a call (wf_boundary_bsdf.hip)
     else if (k == "tr_route") *value = plan.trRoute;  // -1 no media, 0 k_shadow_tr, 1 k_shadow_tr_fast, 2 the transmittance wavefront

@@ -149,6 +149,7 @@ struct ScenePlan : SceneFacts {
     int emittedVariant = 0;
     int nLights = 0, nInfiniteLights = 0;   // the sizes of the light table and of the list of infinite lights ("lights", "infinite_lights")
     int nMaterials = 0;                     // the size of the material table: what wf_bsdf_make_device / wf_bsdf_eval_device check a row's material id against
+    int nMedia = 0, cameraMedium = -1;      // the size of the medium table (what wf_medium_sample_device checks a row's medium id against) and the camera's medium ("media", "camera_medium")
 };
 constexpr int EMITTED_PORTAL = 1, EMITTED_ALPHA = 2, EMITTED_AREA_RARE = 4;
 constexpr int EmittedVariant(bool portal, bool alpha, bool areaRare) {

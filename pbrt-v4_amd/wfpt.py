@@ -79,6 +79,10 @@ ABI_SYMBOLS = [
     "wf_camera_samples_device", "wf_film_add_samples_device", "wf_light_sample_device", "wf_light_emitted_device",
     "wf_bsdf_make_device", "wf_bsdf_eval_device",
 ]
+# every symbol include/wf_media.h declares (checked by tests/test_medium_host.py): an addition beside wf_abi.h, same library
+MEDIA_SYMBOLS = ["wf_medium_sample_device", "wf_phase_device"]
+# the event kinds of wf_medium_sample_device (event4 word 0)
+MEDIUM_NONE, MEDIUM_ARRIVED, MEDIUM_ENDED, MEDIUM_SCATTER = 0, 1, 2, 3
 # the planes of a wf_bsdf_make_device record (include/wf_abi.h: WF_BSDF_PLANES), and the bit of bsdf4 word 0 beside the BxDFFlags
 BSDF_PLANES = 10
 BSDF_TERMINATED = 1 << 8
@@ -759,6 +763,116 @@ class Scene:
         self._device_call("wf_bsdf_eval_device", hip.wf_bsdf_eval_device, [C.c_void_p, C.c_int] + [C.c_void_p] * 12, ts, n, p(n_device), rec.data_ptr(), F.data_ptr(),
                           I.data_ptr(), p(wi), p(u4), p(f4), p(pdf4), p(nxt), p(sf), p(sp), p(si))
         return r
+
+    def medium_sample_device(self, rays8, medium, lambda4, beta, r_u, r_l, flags=None, n_device=None, out=None):
+        """wf_medium_sample_device (include/wf_media.h): delta tracking along n device rays through the scene's media, by the render's
+        own functions — absorb, scatter or null-collide, with the media's emission.  rays8 float32 [n, 8] rows {o, d, tMax, time} with
+        tMax the closest hit's t (trace_device) or +inf; medium int32 [n] (-1: in no medium); lambda4, beta, r_u, r_l float32 [n, 4]
+        (the path's state on entry); flags int32 [n] (None: all 1): bit 0 = collect the emission (the render's depth < maxDepth).
+        Returns a dict: "event4" int32 [n, 4] and its views "kind" (MEDIUM_NONE 0: no row, all zeros; MEDIUM_ARRIVED 1: the ray reached
+        tMax, go on to the hit or the escape; MEDIUM_ENDED 2: the path ended; MEDIUM_SCATTER 3: a real scatter at "p") and "steps" (the
+        tentative collisions taken); "p_g4" float32 [n, 4] with views "p" [n, 3] and "g" [n]; "beta", "r_u", "r_l" float32 [n, 4]; "L"
+        float32 [n, 4], the emission collected along the ray (add it to the pixel's L).  out: a dict with "beta", "r_u", "r_l" (and
+        optionally the others) to write into — they may be the input tensors themselves: a row is read before it is written."""
+        import torch
+        _, hip = libs()
+        what = "medium_sample_device"
+        self._as(rays8, torch.float32, 8, what + " rays8")
+        self._as(medium, torch.int32, 0, what + " medium")
+        for t in (lambda4, beta, r_u, r_l):
+            self._as(t, torch.float32, 4, what + " lambda4 / beta / r_u / r_l")
+        if flags is not None:
+            self._as(flags, torch.int32, 0, what + " flags")
+        n = rays8.shape[0]
+        if any(t.shape[0] != n for t in (medium, lambda4, beta, r_u, r_l) + ((flags,) if flags is not None else ())):
+            raise WfError(what + ": the arrays hold different numbers of items")
+        self._count_arg(n_device, what)
+        dev = rays8.device
+        out = dict(out) if out is not None else {}
+        for k, dt in (("event4", torch.int32), ("p_g4", torch.float32), ("beta", torch.float32), ("r_u", torch.float32), ("r_l", torch.float32), ("L", torch.float32)):
+            if k not in out:
+                out[k] = torch.empty((n, 4), dtype=dt, device=dev)
+            self._as(out[k], dt, 4, what + " out[%r]" % k)
+            if out[k].shape[0] != n:
+                raise WfError(what + ": out is the dict of a call with the same number of items")
+        ev, pg = out["event4"], out["p_g4"]
+        r = {"event4": ev, "p_g4": pg, "beta": out["beta"], "r_u": out["r_u"], "r_l": out["r_l"], "L": out["L"], "kind": ev[:, 0], "steps": ev[:, 1],
+             "p": pg[:, :3], "g": pg[:, 3]}
+        ts = [rays8, medium, lambda4, beta, r_u, r_l, ev, pg, r["beta"], r["r_u"], r["r_l"], r["L"]] + [t for t in (flags, n_device) if t is not None]
+        p = lambda t: t.data_ptr() if t is not None else None
+        # (n = 0 still goes through: a scene without media is refused)
+        self._device_call("wf_medium_sample_device", hip.wf_medium_sample_device, [C.c_void_p, C.c_int] + [C.c_void_p] * 14, ts, n, p(n_device), rays8.data_ptr(),
+                          medium.data_ptr(), lambda4.data_ptr(), beta.data_ptr(), r_u.data_ptr(), r_l.data_ptr(), p(flags), ev.data_ptr(), pg.data_ptr(),
+                          r["beta"].data_ptr(), r["r_u"].data_ptr(), r["r_l"].data_ptr(), r["L"].data_ptr())
+        return r
+
+    def phase_device(self, rays8, p_g4, wi=None, u4=None, n_device=None):
+        """wf_phase_device (include/wf_media.h): the Henyey-Greenstein phase function at the scatter points of medium_sample_device.
+        rays8 float32 [n, 8]: the rays that scattered (wo = -d, and the time); p_g4 float32 [n, 4]: rows {p, g}.  wi float32 [n, 4]
+        rows {wi, unused}: "p" float32 [n] = phase.p(wo, wi), "pdf" float32 [n] = phase.PDF(wo, wi).  u4 float32 [n, 4] rows {u[0],
+        u[1], unused, unused}: phase.Sample_p — "sample_p", "sample_pdf" float32 [n], "next_rays8" float32 [n, 8] rows {p, wi, +inf, the
+        row's time} (ready for trace_device; the next ray's medium is the one the ray was in).  A sample with pdf 0 is zeros.  The
+        tensors themselves: "p_pdf4", "sample4".  Russian roulette and depth + 1 are the caller's."""
+        import torch
+        _, hip = libs()
+        self._as(rays8, torch.float32, 8, "phase_device rays8")
+        self._as(p_g4, torch.float32, 4, "phase_device p_g4")
+        n = rays8.shape[0]
+        if p_g4.shape[0] != n:
+            raise WfError("phase_device: the arrays hold different numbers of items")
+        if wi is None and u4 is None:
+            raise WfError("phase_device: give wi, u4 or both")
+        for t, what in ((wi, "wi"), (u4, "u4")):
+            if t is not None:
+                self._as(t, torch.float32, 4, "phase_device " + what)
+                if t.shape[0] != n:
+                    raise WfError("phase_device: the arrays hold different numbers of items")
+        self._count_arg(n_device, "phase_device")
+        dev = rays8.device
+        r = {}
+        ts = [rays8, p_g4]
+        pp = sm = nxt = None
+        if wi is not None:
+            pp = torch.empty((n, 4), dtype=torch.float32, device=dev)
+            r.update(p_pdf4=pp, p=pp[:, 0], pdf=pp[:, 1])
+            ts += [wi, pp]
+        if u4 is not None:
+            sm = torch.empty((n, 4), dtype=torch.float32, device=dev)
+            nxt = torch.empty((n, 8), dtype=torch.float32, device=dev)
+            r.update(sample4=sm, next_rays8=nxt, sample_p=sm[:, 0], sample_pdf=sm[:, 1])
+            ts += [u4, sm, nxt]
+        if n_device is not None:
+            ts.append(n_device)
+        p = lambda t: t.data_ptr() if t is not None else None
+        # (n = 0 still goes through: a scene without media is refused)
+        self._device_call("wf_phase_device", hip.wf_phase_device, [C.c_void_p, C.c_int] + [C.c_void_p] * 8, ts, n, p(n_device), rays8.data_ptr(), p_g4.data_ptr(),
+                          p(wi), p(u4), p(pp), p(sm), p(nxt))
+        return r
+
+    def medium_light_planes(self, p_g4, rays8, medium):
+        """The (planes_f float32 [11, n, 4], planes_i int32 [2, n, 4]) of n medium vertices for sample_lights_device: the reference's
+        LightSampleContext of a point in a medium — pi lower = pi upper = p, n = ns = 0 — with the ray's time in plane 2.w, valid = 1
+        and medium inside = outside = the ray's medium (the shadow ray's medium either way).  p_g4: the scatter points of
+        medium_sample_device; rays8: the rays that scattered; medium int32 [n]."""
+        import torch
+        self._as(p_g4, torch.float32, 4, "medium_light_planes p_g4")
+        self._as(rays8, torch.float32, 8, "medium_light_planes rays8")
+        self._as(medium, torch.int32, 0, "medium_light_planes medium")
+        n = p_g4.shape[0]
+        if rays8.shape[0] != n or medium.shape[0] != n:
+            raise WfError("medium_light_planes: the arrays hold different numbers of items")
+        F = torch.zeros((INTR_FPLANES, n, 4), dtype=torch.float32, device=p_g4.device)
+        I = torch.zeros((INTR_IPLANES, n, 4), dtype=torch.int32, device=p_g4.device)
+        F[0, :, :3] = p_g4[:, :3]
+        F[1, :, :3] = p_g4[:, :3]
+        F[2, :, 3] = rays8[:, 7]
+        I[0, :, 0] = -1
+        I[0, :, 1] = -1
+        I[0, :, 2] = medium
+        I[0, :, 3] = medium
+        I[1, :, 0] = -1
+        I[1, :, 1] = 1
+        return F, I
 
     def bounds(self):
         """WavefrontAggregate::Bounds() in rendering space: (pMin[3], pMax[3])"""

@@ -59,7 +59,8 @@ void DirectSample(const SceneView &sv, const Rows &r, size_t i, F4 out[4], I4 *l
     if (pk.lightId < 0) return;
     *light = I4{pk.lightId, (int32_t)FloatToBits(pk.pmf), IsDeltaLight(sv.lights[pk.lightId]) ? 1 : 0, -1};
     if (!pk.ls.valid || !pk.ls.L || pk.ls.pdf == 0) return;
-    const RayOD ray = SpawnRayTo(pi, n, pk.ls.pLightPi, pk.ls.pLightN);
+    // (a row without a normal is a point in a medium: KSampleMediumScattering's shadow ray, p to the light's point as it is)
+    const RayOD ray = n.x == 0 && n.y == 0 && n.z == 0 ? RayOD{pi.mid(), pk.ls.pLightPi.mid() - pi.mid()} : SpawnRayTo(pi, n, pk.ls.pLightPi, pk.ls.pLightN);
     if (sv.haveMedia) light->w = Dot(ray.d, n) > 0 ? r.planesI[i].w : r.planesI[i].z;
     out[0] = F4{ray.o.x, ray.o.y, ray.o.z, ray.d.x};
     out[1] = F4{ray.d.y, ray.d.z, 1 - ShadowEpsilon, nn.w};
